@@ -15,6 +15,11 @@ control collectives are a broadcast of rank 0's parameters, the barrier + max-ov
 region, and a sum of counters (frames, parity, kernel time) -- RCCL on GPU.  `--dry-run` runs the same
 rank logic on gloo without a GPU (CPU test of the launcher and the shard bookkeeping).
 
+A plain run sets up, warms up, times `--steps` steps, writes the last step's output if `--dump-outputs DIR` is
+given, and prints the result line.  `--full` adds every other leg after that: the per-kernel timing pass and the
+rooflines, the single-pair latency and the latency mode, config D's 32-pair shard, the parity check of the timed
+pass against the CPU oracle and the CPU baseline (their fields of the result line are null without it).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -54,6 +59,9 @@ CONFIGS = {
 METRIC = "MPix/s (and frames/sec) 1080p op-point-2; avg EPE vs CPU ref"
 # configs whose batch is the whole job's (sharded over the ranks) rather than each GPU's
 STRONG = {"D"}
+# --dump-outputs: bytes written at most (over all ranks) and the seed of the row sample of a larger output
+DUMP_BYTES = 48 * 1000 * 1000
+DUMP_SEED = 0
 
 
 def parse():
@@ -68,6 +76,16 @@ def parse():
     ap.add_argument("--total", type=int, default=0,
                     help="frame pairs per step over ALL GPUs, sharded over the ranks (strong scaling; 0 = the "
                          "config's: D 256, the others weak scaling at --batch per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the other legs: per-kernel timing and rooflines, single-pair "
+                         "latency, the latency mode, the strong-scaling shard, parity against the CPU oracle and the "
+                         "CPU baseline (the options below that tune or skip a leg act on a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's output (the flow / disparity the caller "
+                         "of the timed entry point receives) to DIR/flow.npy, float32 (flow_rank<r>.npy per rank with "
+                         "--gpus N > 1): the whole (pairs, H, W, nop) array when it fits DUMP_BYTES, else its rows "
+                         "(of the (pairs * H, W * nop) view) at a fixed sample drawn with seed DUMP_SEED, in "
+                         "ascending order")
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic pairs tiled over the batch")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="bounded CPU-baseline sample per leg (1 core, all cores; 0 = skip)")
@@ -85,7 +103,10 @@ def parse():
     ap.add_argument("--parity-frames", type=int, default=8,
                     help="distinct timed-pass frames re-checked against the CPU oracle on every rank (their tiles: "
                          "on the device)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def relaunch_as_ranks(args) -> int:
@@ -99,6 +120,27 @@ def relaunch_as_ranks(args) -> int:
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "1")
     return subprocess.run(cmd, env=env).returncode
+
+
+def dump_outputs(path, out, rank, world, torch):
+    """Write this rank's output of the last timed step as float32 .npy: whole when it fits the byte budget, else
+    a fixed sample of its rows (the same rows in every run with the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    B, H, W, nop = out.shape
+    rows = out.view(B * H, W * nop)
+    budget = DUMP_BYTES // world
+    keep = budget // (W * nop * out.element_size())
+    if keep < 1:
+        raise SystemExit(f"bench.py: one output row does not fit the --dump-outputs budget of {budget} bytes")
+    if keep >= B * H:
+        arr, sample = out.cpu().numpy(), None
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(B * H, size=keep, replace=False))
+        arr = rows[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+        sample = f"{keep} of {B * H} rows of the (pairs * H, W * nop) view, numpy default_rng({DUMP_SEED + rank}).choice"
+    name = "flow.npy" if world == 1 else f"flow_rank{rank}.npy"
+    np.save(os.path.join(path, name), np.ascontiguousarray(arr, dtype=np.float32))
+    return {"file": name, "shape": list(arr.shape), "dtype": "float32", "sample": sample}
 
 
 def config_tag(cfg, B):
@@ -434,14 +476,15 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     elapsed = odd.max_over_ranks(elapsed, dev) if world > 1 else elapsed
+    dumped = dump_outputs(args.dump_outputs, out, rank, world, torch) if args.dump_outputs else None
     # the timed pass's output of the distinct pairs, for the parity check below
-    timed_out = out[:nd].cpu().numpy()
+    timed_out = out[:nd].cpu().numpy() if args.full else None
     # every other frame of the timed pass is a tile of one of the nd distinct pairs: compare its bits on the device
     # with its tile source (frames nd.. against frames 0..nd-1, nd at a time), so the oracle check of the distinct
     # frames covers the whole batch
     tiles_equal = [0] * nd  # per distinct pair: the later frames equal to it bit for bit
     ov = out.view(B, -1).view(torch.int32)
-    for j in range(nd, B, nd):
+    for j in range(nd, B if args.full else 0, nd):
         m = min(nd, B - j)
         if torch.equal(ov[j:j + m], ov[:m]):
             for i in range(m):
@@ -460,7 +503,7 @@ def main():
     kernels = {}
     roofline = None
     roofline_sor = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # the same launches (chunk_eff pairs each), serialised on one stream: each kernel timed alone
         # (HIP events bracketing launches of two concurrent streams do not measure the kernels: they
         # measured 2x rocprofv3's kernel durations)
@@ -498,13 +541,13 @@ def main():
 
     # ---- single-pair latency (the drop-in CLI's case: one pair per call), device-resident and host buffers
     latency = None
-    if rank == 0 and world == 1 and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and not args.no_latency:
         latency = pair_latency(od, ctx, p, pairs[0], dev, torch)
 
     # ---- strong-scaling configs on one GPU: the per-GPU rate at the shard size 8 GPUs would run (config D: 32 of
     # the 256 pairs), so a 1-GPU D number is never read as the per-GPU throughput of the 8-GPU job
     shard8 = None
-    if scaling == "strong" and world == 1 and total >= 8:
+    if args.full and scaling == "strong" and world == 1 and total >= 8:
         n8 = total // 8
         ctx.set_option("streams", 0)
         ctx.set_option("chunk", 0)
@@ -528,7 +571,8 @@ def main():
     # each of 8 GPUs gets of BASELINE's 256) -- its end-point difference against the exact path is in "parity" below
     latency_mode = None
     rb_out = None
-    if rank == 0 and world == 1 and not args.no_latency and not any(o.startswith("sor_mode") for o in args.option):
+    if (args.full and rank == 0 and world == 1 and not args.no_latency
+            and not any(o.startswith("sor_mode") for o in args.option)):
         ctx.set_option("sor_mode", 1)
         lat_rb = pair_latency(od, ctx, p, pairs[0], dev, torch)
         n32 = min(32, B)
@@ -594,7 +638,7 @@ def main():
     # compared frames, sum of avg EPE, max avg EPE, bit-exact distinct frames, frames of the batch bit-exact (a
     # bit-exact distinct frame and every later tile of it that equals it on the device), frames in the batch
     sums = [0.0, 0.0, 0.0, 0.0, 0.0, float(B)]
-    if args.cpu_seconds > 0:
+    if args.full and args.cpu_seconds > 0:
         from oracle import pyoracle as O
         q = oracle_params(O, p)
         ncmp = max(1, min(nd, args.parity_frames))
@@ -615,7 +659,7 @@ def main():
                      "max": round(float(e.max()), 4)})
         if rank == 0 and world == 1:
             cpu = cpu_baseline(O, q, pairs, W, H, args.cpu_seconds, binary, args.config)
-    if world > 1:
+    if args.full and world > 1:
         tot = odd.sum_over_ranks([sums[0], sums[1], sums[3], sums[4], sums[5]], dev)
         sums = [tot[0], tot[1], odd.max_over_ranks(sums[2], dev), tot[2], tot[3], tot[4]]
     if sums[0]:
@@ -630,7 +674,7 @@ def main():
             "metric": METRIC,
             "value": round(mpix, 2), "unit": "MPix/s", "n_gpus": n_devices, "ranks": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "full": args.full, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "frames_per_sec": round(frames / elapsed, 2),
             "per_gpu_mpix_s": round(mpix / n_devices, 2),
             "config": {"workload": f"{binary} {W}x{H} op-point {op}" + (f" ({explicit})" if explicit else "")
@@ -644,7 +688,7 @@ def main():
                                                                    if rehearsal else "")},
             "roofline": roofline, "roofline_tv_sor": roofline_sor, "cpu_baseline": cpu, "parity": parity,
             "latency": latency, "latency_mode": latency_mode, "host_io": host_io, "shard_of_8": shard8,
-            "kernels": kernels,
+            "kernels": kernels, "dump_outputs": dumped,
         }
         if cpu:
             line["speedup_vs_cpu_1core"] = round(mpix / cpu["value"], 1)

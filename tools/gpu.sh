@@ -50,7 +50,7 @@ for spec in "$@"; do
     rocprof*)
       # shellcheck disable=SC2086
       step "$name" 900 rocprofv3 --kernel-trace --stats -d "$OUT/$name" -o run --output-format csv -- \
-        python -u bench.py ${arg:---steps 5 --warmup 2 --cpu-seconds 0 --no-latency} || exit 1 ;;
+        python -u bench.py ${arg:---full --steps 5 --warmup 2 --cpu-seconds 0 --no-latency} || exit 1 ;;
     pmc*)
       counters=${arg%%@*}
       bargs="--steps 2 --warmup 1 --no-kernel-timing --cpu-seconds 0 --no-latency"

@@ -15,7 +15,7 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 run() {  # name, args...
   local name=$1; shift
   echo "== $name: $*"; date
-  timeout -k 10 300 python bench.py --cpu-seconds 0 --no-latency "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout -k 10 300 python bench.py --full --cpu-seconds 0 --no-latency "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
   local rc=$?
   python -c "import json; d=json.load(open('$OUT/$name.json')); print(d['value'], d['ms_per_step'], {k:round(v['total_ms']/d['steps'],3) for k,v in d['kernels'].items()})" 2>/dev/null
   if [ $rc -ne 0 ]; then echo "stop rc=$rc"; tail -5 "$OUT/$name.err"; exit $rc; fi
