@@ -139,6 +139,7 @@ VARIANTS = [  # (option, value, default): non-default kernels
     ("up_form", 0, 3),         # flow upsample with the horizontal taps once per output row (round 4's kernel)
     ("up_form", 1, 3),         # ... once per source row, 4-row blocks
     ("up_form", 2, 3),         # ... once per source row, 8-row blocks
+    ("nt_store", 1, 0),        # full-resolution flow written with non-temporal stores
 ]
 
 

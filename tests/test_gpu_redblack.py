@@ -111,6 +111,69 @@ def test_redblack_uncaptured_bitexact(oracle, od, rbctx, w, h, noc, mode, op, ov
     _assert_bitexact(rbctx.run_host(a, b, p), ref, "full-resolution flow (no capture)")
 
 
+# (case, prepd): levels of at most 8192 pixels whose fused level launch is refused because prep and the derivative
+# filters run as separate launches (tv_level_rb_ok: prepd = 0, or colour images with prepd = 1) -- the refinement then
+# runs the system kernels and 2 x solverit global k_tv_sor_rb half-sweeps per inner iteration on small levels too
+RB_FALLBACK_CASES = [
+    ((160, 120, 1, 1, 2, {}), 0),                             # gray flow: 80x60, 40x30, 20x15
+    ((128, 64, 1, 1, 2, {"sc_l": 0, "sc_f": 1}), 0),          # ... exactly 8192 pixels
+    ((127, 63, 1, 1, 2, {"sc_l": 0, "sc_f": 0, "tv_solverit": 2, "tv_innerit": 2}), 0),  # ... odd x odd, 2 sweeps
+    ((128, 64, 1, 2, 2, {"sc_l": 0, "sc_f": 1}), 0),          # gray depth
+    ((33, 21, 1, 2, 2, {"sc_l": 0, "sc_f": 0}), 0),           # ... odd x odd
+    ((90, 90, 3, 1, 2, {"sc_l": 0, "sc_f": 1}), 1),           # RGB flow, 8100 and 2025 pixels
+    ((90, 90, 3, 1, 2, {"sc_l": 0, "sc_f": 1}), 0),
+    ((240, 120, 3, 2, 2, {}), 1),                             # RGB depth: 120x60, 60x30, 30x15
+]
+
+
+@pytest.mark.parametrize("case,prepd", RB_FALLBACK_CASES)
+def test_redblack_global_fallback_bitexact(oracle, od, rbctx, case, prepd):
+    """Small levels on the global half-sweeps (no fused level launch): the oracle's red-black bits, stage by stage."""
+    w, h, noc, mode, op, over = case
+    a, b = od.synth_pair(w, h, noc, 1, mode)
+    p, q = _params(od, oracle, w, noc, mode, op, over)
+    with oracle.sor_order(1):
+        ref, cap_d, cap_t = oracle.run_u8(a, b, q, capture=True)
+    dis = {s: np.zeros_like(v) for s, v in cap_d.items()}
+    tv = {s: np.zeros_like(v) for s, v in cap_t.items()}
+    rbctx.set_option("prepd", prepd)
+    rbctx.set_capture(dis, tv)
+    try:
+        got = rbctx.run_host(a, b, p)
+    finally:
+        rbctx.set_capture(None, None)
+        rbctx.set_option("prepd", 2)
+    assert max(d.shape[0] * d.shape[1] for d in cap_d.values()) <= 8192  # no level is on the global form by its size
+    for s in sorted(cap_d, reverse=True):
+        _assert_bitexact(dis[s], cap_d[s], f"prepd={prepd}: scale {s} after aggregation")
+        _assert_bitexact(tv[s], cap_t[s], f"prepd={prepd}: scale {s} after TV refinement")
+    _assert_bitexact(got, ref, f"prepd={prepd}: full-resolution flow")
+
+
+@pytest.mark.parametrize("fallback", [False, True], ids=["fused", "global"])
+@pytest.mark.parametrize("w,h,noc,mode,op,over", [
+    (100, 90, 3, 1, 2, {"sc_l": 0, "sc_f": 1}),               # RGB flow: 9000 pixels (global half-sweeps), 50x45 (fused)
+    (240, 120, 1, 2, 4, {"max_iter": 16, "min_iter": 16}),    # gray depth: 240x120 (global), 120x60 .. 30x15 (fused)
+])
+def test_redblack_batch_vs_oracle_rb(oracle, od, rbctx, w, h, noc, mode, op, over, fallback):
+    """Three distinct scenes in one call, colour flow and depth: each frame is the oracle's red-black flow for that
+    scene -- with the small levels on the fused level launch, and (prepd 0 / colour prepd 1) every level on the
+    global half-sweeps."""
+    frames = (5, 2, 7)  # distinct mod 8 (the synth scenes repeat with period 8)
+    pairs = [od.synth_pair(w, h, noc, f, mode) for f in frames]
+    p, q = _params(od, oracle, w, noc, mode, op, over)
+    if fallback:
+        rbctx.set_option("prepd", 1 if noc == 3 else 0)
+    try:
+        out = rbctx.run_host(np.stack([x[0] for x in pairs]), np.stack([x[1] for x in pairs]), p)
+    finally:
+        rbctx.set_option("prepd", 2)
+    for i, (a, b) in enumerate(pairs):
+        with oracle.sor_order(1):
+            ref = oracle.run_u8(a, b, q)
+        _assert_bitexact(out[i], ref, f"frame {i} (scene {frames[i]})")
+
+
 # (W, H, noc, mode, op, frame, gate): the 0.05 px gate of SURVEY §8(c) at the op-point-2 configs (A, B / D);
 # the finer op-points 3 / 4 (more levels, finest scale 1 or 2) are reported against a looser 0.1 px ceiling
 # (measured round 2: 640x480 RGB op3 0.054 px average).
