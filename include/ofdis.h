@@ -185,7 +185,8 @@ int ofdis_context_set_stage_capture(ofdis_context *ctx, float *const *dis_flow, 
  *   "agg_stage" (0/1, default 1): the aggregation stages the displacements of the patches covering each 64 x 16
  *                        tile in LDS (0: every pixel gathers them from the patch array);
  *   "prepd_df" (0/1, default 1): on those levels the prep launch warps a 2-pixel halo with every channel in one pass
- *                        and writes Ix, Iy, It only (k_tv_prepd_df; 0: k_tv_prepd's 4-pixel halo, channel by channel);
+ *                        and writes Ix, Iy, It only (k_tv_prepd_df; 0: intensity images run k_tv_prepd on its 4-pixel
+ *                        halo, colour images k_tv_prepd_c3, which writes all eight derivative planes);
  *   "smsys_march" (0/1, default 1): levels taller than 256 rows run smoothness + system as a register march
  *                        (one wave per 60 columns x 64 rows, no LDS; takes precedence over smsys2d);
  *   "prepd" (0..2, default 2): image warp, temporal images and the derivative filters of a level in one launch

@@ -5,20 +5,31 @@
 // defaults), so results are bit-identical to the CPU restatement in oracle/ and hence, for the
 // variational part, to the reference's own FDF1.0.1 code.
 //
-// Kernels (reference function they replace):
-//   k_pyr_base      run_dense.cpp:299-312 + :151 (divisibility pad + 2^l box mean, exact in fp32)
-//   k_pyr_down      run_dense.cpp:151 (cv::resize .5 = 2x2 mean)
-//   k_pyr_pad_grad  run_dense.cpp:157-178 (Sobel/8 reflect-101 + replicate / zero padding)
-//   k_patch         patch.cpp:55-295 (one wave64 per patch; Eigen-order reductions through LDS)
-//   k_aggregate     patchgrid.cpp:213-275,377-397 (gather form, serial patch order, no atomics)
-//   k_tv_prep       opticalflow_aux.c:31-75 + :88-99 (warp, mask, mean / temporal images)
-//   k_tv_deriv1/2   opticalflow_aux.c:101-107 (5-tap derivative filters)
-//   k_tv_smooth     opticalflow_aux.c:138-160 (robust smoothness weight)
-//   k_tv_system     opticalflow_aux.c:161-223,408-747 (diffusivities + data term + laplacian)
-//   k_tv_sor_pipe   solver.c:83-433 / :439-471 (exact lexicographic order: register-pipelined wavefront)
-//   k_tv_sor        same, generic global-memory wavefront (any size; also solver.c:34-78 fallback)
-//   k_tv_final      refine_variational.cpp:209-227,305-323
-//   k_upsample      run_dense.cpp:407-415 (x2^l, cv::resize INTER_LINEAR, crop)
+// Kernels, in file order (reference lines they replace).  Each stage's kernels are followed by the launch_* /
+// tv_*_ok functions that choose among them ("// ---- launch"), outside the anonymous namespace:
+//   pyramid      k_pyr_base, k_pyr_base_gray<L>, k_pyr_base_rgb<L>  run_dense.cpp:299-312 + :151 (pad + 2^l box mean)
+//                k_pyr_down          run_dense.cpp:151 (cv::resize .5 = 2x2 mean)
+//                k_pyr_gradmag       the gradient-magnitude input (SELECTCHANNEL 2)
+//                k_pyr_pad_grad, k_pyr_pad_grad_v<3>  run_dense.cpp:157-178 (Sobel/8 reflect-101 + padding)
+//   patches      patch.cpp:55-413, patchgrid.cpp:98-141,195-211 (inverse search), six families chosen by launch_patch:
+//                k_patch<NOP, JM>    one wave64 per patch, any shape up to 448 values
+//                k_patch8<NOP, PAIRS, ODD>  eight lanes per patch, the common shapes
+//                k_patchg<NOP>       eight lanes per patch, runtime value loops: any shape
+//                k_patchw / k_patchq / k_patchx<NOP, P, NOC, MINW, COST>  LDS-windowed, 8 / 4 / 16 lanes per patch
+//   aggregation  k_aggregate         patchgrid.cpp:213-275,277-375,377-397 (gather form, serial patch order)
+//   variational  k_tv_prep<NP, TH>   opticalflow_aux.c:31-75 + :88-99 (warp, mask, mean / temporal images)
+//                k_tv_prepd, k_tv_prepd_c3, k_tv_prepd_df<NOC, TH>  prep + derivatives in one launch (:31-132)
+//                k_tv_deriv1 / 2     opticalflow_aux.c:101-107 (5-tap derivative filters)
+//                k_tv_smooth<NOP>    opticalflow_aux.c:138-160 (robust smoothness weight)
+//                k_tv_system<NOP, NOC>  opticalflow_aux.c:161-223,408-747 (diffusivities + data term + laplacian)
+//                k_tv_smsys, k_tv_smsys_m<NOP, NOC, DF>, k_tv_smsys2d<NOP, NOC>  both in one launch
+//                k_tv_sor<MODE>      solver.c:83-433 / :439-471 / :34-78, generic global-memory wavefront
+//                k_tv_sor_rb<MODE>   the same update in red-black order (opt-in)
+//                k_tv_sor_pipe<S, MODE, MAXT>  exact order, register-pipelined wavefront
+//                k_tv_sor_lanes<S, MODE, NB, MAXT, CRING, R, CG, SEL>  exact order, one wave per sweep and row group
+//                k_tv_final<TH>      refine_variational.cpp:209-227,305-323
+//   output       k_upsample, k_upsample_rows, k_upsample_h<R>, k_upsample_rows1  run_dense.cpp:407-415
+//   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
 
@@ -40,6 +51,23 @@ namespace {
 #include "ofdis_agg_dev.inc"  // aggregation weights, slot planes, the own-grid gather
 
 inline unsigned ceil_div(long a, long b) { return (unsigned)((a + b - 1) / b); }
+
+// Runtime value -> template argument (host).  pick<Vs...>(v, f) calls f(Int<V>{}) for the V of Vs that equals v and
+// returns true, or calls nothing and returns false.  The argument converts to its value in constant expressions:
+// pick<1, 2>(n, [&](auto N) { k<N><<<...>>>(a); }).  Several arguments nest; a nest instantiates exactly the
+// combinations it spells out, so a launcher compiles the kernels it can launch and no others.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <int... Vs, class F>
+inline bool pick(int v, F &&f) {
+  return ((v == Vs && (f(Int<Vs>{}), true)) || ...);
+}
+// The two arguments most kernels take.  NOP: 2 = optical flow, every other value runs the depth form (1).
+// NOC: 1 = intensity images, every other value runs the colour form (3).
+template <class F>
+inline void pick_nop(int nop, F &&f) { pick<2, 1>(nop == 2 ? 2 : 1, f); }
+template <class F>
+inline void pick_noc(int noc, F &&f) { pick<1, 3>(noc == 1 ? 1 : 3, f); }
 
 // XCD-aware block order (T1 of the CDNA guide): the dispatcher deals workgroups to the 8 XCDs round robin by
 // linear id, each XCD with its own L2.  Linear id L runs block number L / 8 of the contiguous eighth of the
@@ -316,6 +344,28 @@ __global__ __launch_bounds__(256) void k_pyr_pad_grad_v(PyrPadGradArgs a) {
   }
 }
 
+}  // namespace
+// ---- launch
+void launch_pyr_base(const PyrBaseArgs &a, hipStream_t s) {
+  const unsigned blocks = ceil_div(2L * a.n * a.h * a.w, 256);
+  if (a.noc == 1 && pick<2, 3, 4, 5>(a.log2s, [&](auto L) { k_pyr_base_gray<L><<<blocks, 256, 0, s>>>(a); })) return;
+  if (a.noc == 3 && a.rgb_sad && pick<2, 3, 4>(a.log2s, [&](auto L) { k_pyr_base_rgb<L><<<blocks, 256, 0, s>>>(a); }))
+    return;
+  k_pyr_base<<<dim3(ceil_div(a.w, 256), a.h, 2 * a.n), 256, 0, s>>>(a);
+}
+void launch_pyr_gradmag(const PyrGradmagArgs &a, hipStream_t s) {
+  k_pyr_gradmag<<<dim3(ceil_div(a.Wp, 256), a.Hp, 2 * a.n), 256, 0, s>>>(a);
+}
+void launch_pyr_down(const PyrDownArgs &a, hipStream_t s) {
+  k_pyr_down<<<std::min(ceil_div((long)a.n2 * a.h * a.w * a.noc, 256), 1u << 22), 256, 0, s>>>(a);  // grid-stride beyond
+}
+void launch_pyr_pad_grad(const PyrPadGradArgs &a, hipStream_t s) {
+  const long px = (long)a.n2 * (a.h + 2 * a.pad) * (a.w + 2 * a.pad);  // grid-stride beyond 2^22 workgroups
+  if (a.noc == 3 && a.per_value) k_pyr_pad_grad_v<3><<<std::min(ceil_div(px * 3, 256), 1u << 22), 256, 0, s>>>(a);
+  else k_pyr_pad_grad<<<std::min(ceil_div(px, 256), 1u << 22), 256, 0, s>>>(a);
+}
+namespace {
+
 // ------------------------------------------------------------------------------------------------ DIS patches
 
 constexpr int kPatchWaves = 4;
@@ -465,6 +515,49 @@ __device__ __forceinline__ float llt1_solve_fast(float L, const LltRcp &rc, floa
   return x;
 }
 
+// ---- the preamble of every patch kernel (k_patch, k_patch8, k_patchg, k_patchw, k_patchq, k_patchx)
+
+// Patch gq of the batch (patchgrid.cpp:98-141): frame, cell of the patch grid, reference position in the level image.
+__device__ __forceinline__ void patch_decode(const PatchArgs &a, long gq, int &f, int &pxi, int &pyi, float &ptr0,
+                                             float &ptr1) {
+  const LevelGeom &g = a.g;
+  f = (int)(gq / g.npatch);
+  const int ip = (int)(gq % g.npatch);
+  pxi = ip / g.noph;
+  pyi = ip % g.noph;
+  ptr0 = (float)(pxi * a.steps + g.offw);
+  ptr1 = (float)(pyi * a.steps + g.offh);
+}
+// ComputeHessian's regularisation of a singular Hessian (patch.cpp:80-85), in double as upstream.
+template <int NOP>
+__device__ __forceinline__ void hessian_regularise(float &H00, float H01, float &H11) {
+  if (NOP == 2) {
+    if (H00 * H11 - H01 * H01 == 0.0f) {
+      H00 = (float)((double)H00 + 1e-10);
+      H11 = (float)((double)H11 + 1e-10);
+    }
+  } else if (H00 == 0.0f) {
+    H00 = (float)((double)H00 + 1e-10);
+  }
+}
+// InitializeFromCoarserOF (patchgrid.cpp:195-211): twice the coarser level's flow at the patch; 0 on the first level.
+template <int NOP>
+__device__ __forceinline__ void patch_init_coarser(const PatchArgs &a, int f, float ptr0, float ptr1, float &pin0,
+                                                   float &pin1) {
+  pin0 = 0.0f;
+  pin1 = 0.0f;
+  if (a.prev) {
+    const int x = (int)floorf(ptr0 / 2), y = (int)floorf(ptr1 / 2);
+    const float *pv = a.prev + (long)f * a.prev_frame_stride + (long)(y * a.prev_w + x) * a.prev_elem_stride;
+    pin0 = pv[0] * 2;
+    if (NOP == 2) pin1 = pv[a.prev_comp_stride] * 2;
+  }
+}
+// What the timing diagnostics a.stage = 1 / 2 store in place of the result (2 adds pin0 + pin1): keeps the work alive.
+__device__ __forceinline__ float patch_stage_value(const Llt2 &fac, float fac1, float t) {
+  return fac.L00 + fac.L10 + fac.L11 + fac1 + t;
+}
+
 template <int JM>
 struct PatchCtx {
   const float *B;
@@ -540,9 +633,9 @@ __global__ __launch_bounds__(256) void k_patch(PatchArgs a) {
   const LevelGeom &g = a.g;
   const long gp = (long)blockIdx.x * kPatchWaves + wid;
   if (gp >= (long)a.n * g.npatch) return;  // whole wave exits; the kernel has no block barrier
-  const int f = (int)(gp / g.npatch), ip = (int)(gp % g.npatch);
-  const int pxi = ip / g.noph, pyi = ip % g.noph;
-  const float ptr0 = (float)(pxi * a.steps + g.offw), ptr1 = (float)(pyi * a.steps + g.offh);
+  int f, pxi, pyi;
+  float ptr0, ptr1;
+  patch_decode(a, gp, f, pxi, pyi, ptr0, ptr1);
   const long fs = (long)g.W * g.H * a.noc;
 
   PatchCtx<JM> c;
@@ -600,7 +693,7 @@ __global__ __launch_bounds__(256) void k_patch(PatchArgs a) {
       float hh[3];
       eigen_reduce<3, JM>(c.lds, c.rs, a.novals, lane, hh);
       H00 = hh[0]; H01 = hh[1]; H11 = hh[2];
-      if (H00 * H11 - H01 * H01 == 0.0f) {
+      if (H00 * H11 - H01 * H01 == 0.0f) {  // hessian_regularise, spelled out: the helper changes this kernel's code
         H00 = (float)((double)H00 + 1e-10);
         H11 = (float)((double)H11 + 1e-10);
       }
@@ -615,19 +708,19 @@ __global__ __launch_bounds__(256) void k_patch(PatchArgs a) {
   const float fac1 = llt1_factor(H00);
   const LltRcp lrc = llt_rcp<NOP>(fac, fac1, a.fdiv != 0);
   if (a.stage == 1) {  // timing diagnostic "pconst": construction only; one store keeps the work alive
-    if (lane == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[JM - 1];
+    if (lane == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[JM - 1]);
     return;
   }
   // ---- initial parameters (InitializeFromCoarserOF, patchgrid.cpp:195-211)
   float pin0 = 0.0f, pin1 = 0.0f;
-  if (a.prev) {
+  if (a.prev) {  // patch_init_coarser, spelled out: the helper changes this kernel's code
     const int x = (int)floorf(ptr0 / 2), y = (int)floorf(ptr1 / 2);
     const float *pv = a.prev + (long)f * a.prev_frame_stride + (long)(y * a.prev_w + x) * a.prev_elem_stride;
     pin0 = pv[0] * 2;
     if (NOP == 2) pin1 = pv[a.prev_comp_stride] * 2;
   }
   if (a.stage == 2) {  // "pconst + pinit": construction and initialisation
-    if (lane == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[JM - 1] + pin0 + pin1;
+    if (lane == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[JM - 1]) + pin0 + pin1;
     return;
   }
   // ---- OptimizeStart (patch.cpp:117-154)
@@ -735,9 +828,9 @@ __global__ __launch_bounds__(256) void k_patch8(PatchArgs a) {
   const long gp = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
   const bool live = gp < (long)a.n * g.npatch;
   const long gq = live ? gp : 0;
-  const int f = (int)(gq / g.npatch), ip = (int)(gq % g.npatch);
-  const int pxi = ip / g.noph, pyi = ip % g.noph;
-  const float ptr0 = (float)(pxi * a.steps + g.offw), ptr1 = (float)(pyi * a.steps + g.offh);
+  int f, pxi, pyi;
+  float ptr0, ptr1;
+  patch_decode(a, gq, f, pxi, pyi, ptr0, ptr1);
   const long fs = (long)g.W * g.H * a.noc;
   const int noc = a.noc, P = a.p, W = g.W;
   const float inv_n = 1.0f / (float)a.novals;
@@ -783,7 +876,7 @@ __global__ __launch_bounds__(256) void k_patch8(PatchArgs a) {
     if (NOP == 2) {
       H01 = grp_eigen_sum<PAIRS, ODD>(q1);
       H11 = grp_eigen_sum<PAIRS, ODD>(q2);
-      if (H00 * H11 - H01 * H01 == 0.0f) {
+      if (H00 * H11 - H01 * H01 == 0.0f) {  // hessian_regularise, spelled out: the helper changes this kernel's code
         H00 = (float)((double)H00 + 1e-10);
         H11 = (float)((double)H11 + 1e-10);
       }
@@ -795,19 +888,19 @@ __global__ __launch_bounds__(256) void k_patch8(PatchArgs a) {
   const float fac1 = llt1_factor(H00);
   const LltRcp lrc = llt_rcp<NOP>(fac, fac1, a.fdiv != 0);
   if (a.stage == 1) {  // timing diagnostic "pconst": construction only; one store keeps the work alive
-    if (live && s8 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[V - 1];
+    if (live && s8 == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[V - 1]);
     return;
   }
   // ---- initial parameters (InitializeFromCoarserOF, patchgrid.cpp:195-211)
   float pin0 = 0.0f, pin1 = 0.0f;
-  if (a.prev) {
+  if (a.prev) {  // patch_init_coarser, spelled out: the helper changes this kernel's code
     const int x = (int)floorf(ptr0 / 2), y = (int)floorf(ptr1 / 2);
     const float *pv = a.prev + (long)f * a.prev_frame_stride + (long)(y * a.prev_w + x) * a.prev_elem_stride;
     pin0 = pv[0] * 2;
     if (NOP == 2) pin1 = pv[a.prev_comp_stride] * 2;
   }
   if (a.stage == 2) {  // "pconst + pinit": construction and initialisation
-    if (live && s8 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[V - 1] + pin0 + pin1;
+    if (live && s8 == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[V - 1]) + pin0 + pin1;
     return;
   }
   const float *Bimg = a.img_b + f * fs;
@@ -973,9 +1066,9 @@ __global__ __launch_bounds__(256) void k_patchg(PatchArgs a) {
   const long gp = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
   const bool live = gp < (long)a.n * g.npatch;
   const long gq = live ? gp : 0;
-  const int f = (int)(gq / g.npatch), ip = (int)(gq % g.npatch);
-  const int pxi = ip / g.noph, pyi = ip % g.noph;
-  const float ptr0 = (float)(pxi * a.steps + g.offw), ptr1 = (float)(pyi * a.steps + g.offh);
+  int f, pxi, pyi;
+  float ptr0, ptr1;
+  patch_decode(a, gq, f, pxi, pyi, ptr0, ptr1);
   const long fs = (long)g.W * g.H * a.noc;
   const int noc = a.noc, P = a.p, W = g.W, pn = P * noc;
   const int pairs = a.novals >> 3, odd = (a.novals >> 2) & 1;
@@ -1007,7 +1100,7 @@ __global__ __launch_bounds__(256) void k_patchg(PatchArgs a) {
     if (NOP == 2) {
       H01 = q1.total(pairs, odd);
       H11 = q2.total(pairs, odd);
-      if (H00 * H11 - H01 * H01 == 0.0f) {
+      if (H00 * H11 - H01 * H01 == 0.0f) {  // hessian_regularise, spelled out: the helper changes this kernel's code
         H00 = (float)((double)H00 + 1e-10);
         H11 = (float)((double)H11 + 1e-10);
       }
@@ -1019,18 +1112,14 @@ __global__ __launch_bounds__(256) void k_patchg(PatchArgs a) {
   const float fac1 = llt1_factor(H00);
   const LltRcp lrc = llt_rcp<NOP>(fac, fac1, a.fdiv != 0);
   const float tlast = A[0] - tmean;  // keeps the template work alive in the diagnostics below
+  // patch_stage_value, spelled out: the helper changes this kernel's code (here and at stage 2)
   if (a.stage == 1) {  // timing diagnostic "pconst": construction only
     if (live && s8 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tlast;
     return;
   }
   // ---- initial parameters (InitializeFromCoarserOF, patchgrid.cpp:195-211)
-  float pin0 = 0.0f, pin1 = 0.0f;
-  if (a.prev) {
-    const int x = (int)floorf(ptr0 / 2), y = (int)floorf(ptr1 / 2);
-    const float *pv = a.prev + (long)f * a.prev_frame_stride + (long)(y * a.prev_w + x) * a.prev_elem_stride;
-    pin0 = pv[0] * 2;
-    if (NOP == 2) pin1 = pv[a.prev_comp_stride] * 2;
-  }
+  float pin0, pin1;
+  patch_init_coarser<NOP>(a, f, ptr0, ptr1, pin0, pin1);
   if (a.stage == 2) {  // "pconst + pinit"
     if (live && s8 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tlast + pin0 + pin1;
     return;
@@ -1231,6 +1320,14 @@ __device__ __forceinline__ float div_by_const(float x) {
   if (__builtin_amdgcn_ballot_w64(slow) != 0) q = slow ? x / c : q;
   return q;
 }
+// x / n for a shape's value count n = p^2 noc (the mean of a patch): x * (1 / n) exactly for n = 2^k.
+template <int NV>
+__device__ __forceinline__ float div_by_n(float x) {
+  if constexpr ((NV & (NV - 1)) == 0)
+    return x * (1.0f / (float)NV);
+  else
+    return div_by_const<NV>(x);
+}
 
 // Compile-time loops (the index is a constant expression: template arguments, asm immediates).
 template <class F, int... Is>
@@ -1284,19 +1381,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
   const long gp = (long)xb.x * 32 + (threadIdx.x >> 3);
   const bool live = gp < (long)a.n * g.npatch;
   const long gq = live ? gp : 0;
-  const int f = (int)(gq / g.npatch), ip = (int)(gq % g.npatch);
-  const int pxi = ip / g.noph, pyi = ip % g.noph;
-  const float ptr0 = (float)(pxi * a.steps + g.offw), ptr1 = (float)(pyi * a.steps + g.offh);
+  int f, pxi, pyi;
+  float ptr0, ptr1;
+  patch_decode(a, gq, f, pxi, pyi, ptr0, ptr1);
   const long fs = (long)g.W * g.H * NOC;
   const int W = g.W;
-  constexpr float inv_n = 1.0f / (float)S::NV;
-  constexpr bool pow2 = (S::NV & (S::NV - 1)) == 0;  // x / n == x * (1/n) exactly for n = 2^k
-  auto div_n = [&](float x) {
-    if constexpr (pow2)
-      return x * inv_n;
-    else
-      return div_by_const<S::NV>(x);
-  };
+  auto div_n = [](float x) { return div_by_n<S::NV>(x); };
   // PK: the per-value arithmetic of an evaluation on value pairs (k, k + 1) in packed fp32 -- every lane of a
   // v_pk_mul_f32 / v_pk_add_f32 rounds like the scalar instruction, so the pairs keep each value's operation
   // order; the taps of a pair come straight from one ds_read2_b32 into a register pair
@@ -1355,7 +1445,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
     if (NOP == 2) {
       H01 = h1.total();
       H11 = h2.total();
-      if (H00 * H11 - H01 * H01 == 0.0f) {
+      if (H00 * H11 - H01 * H01 == 0.0f) {  // hessian_regularise, spelled out: the helper changes this kernel's code
         H00 = (float)((double)H00 + 1e-10);
         H11 = (float)((double)H11 + 1e-10);
       }
@@ -1367,19 +1457,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
   const float fac1 = llt1_factor(H00);
   const LltRcp lrc = llt_rcp<NOP>(fac, fac1, a.fdiv != 0);
   if (a.stage == 1) {  // timing diagnostic "pconst": construction only; one store keeps the work alive
-    if (live && s8 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[V - 1];
+    if (live && s8 == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[V - 1]);
     return;
   }
   // ---- initial parameters (InitializeFromCoarserOF, patchgrid.cpp:195-211)
-  float pin0 = 0.0f, pin1 = 0.0f;
-  if (a.prev) {
-    const int x = (int)floorf(ptr0 / 2), y = (int)floorf(ptr1 / 2);
-    const float *pv = a.prev + (long)f * a.prev_frame_stride + (long)(y * a.prev_w + x) * a.prev_elem_stride;
-    pin0 = pv[0] * 2;
-    if (NOP == 2) pin1 = pv[a.prev_comp_stride] * 2;
-  }
+  float pin0, pin1;
+  patch_init_coarser<NOP>(a, f, ptr0, ptr1, pin0, pin1);
   if (a.stage == 2) {  // "pconst + pinit": construction and initialisation
-    if (live && s8 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[V - 1] + pin0 + pin1;
+    if (live && s8 == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[V - 1]) + pin0 + pin1;
     return;
   }
   // template and gradients as value pairs for the packed form (register pairs; the scalar arrays die here)
@@ -1722,19 +1807,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
   const long gp = (long)xb.x * 64 + (threadIdx.x >> 2);
   const bool live = gp < (long)a.n * g.npatch;
   const long gq = live ? gp : 0;
-  const int f = (int)(gq / g.npatch), ip = (int)(gq % g.npatch);
-  const int pxi = ip / g.noph, pyi = ip % g.noph;
-  const float ptr0 = (float)(pxi * a.steps + g.offw), ptr1 = (float)(pyi * a.steps + g.offh);
+  int f, pxi, pyi;
+  float ptr0, ptr1;
+  patch_decode(a, gq, f, pxi, pyi, ptr0, ptr1);
   const long fs = (long)g.W * g.H * NOC;
   const int W = g.W;
-  constexpr float inv_n = 1.0f / (float)S::NV;
   constexpr bool pow2 = (S::NV & (S::NV - 1)) == 0;
-  auto div_n = [&](float x) {
-    if constexpr (pow2)
-      return x * inv_n;
-    else
-      return div_by_const<S::NV>(x);
-  };
+  auto div_n = [](float x) { return div_by_n<S::NV>(x); };
   float *win = win_all + (threadIdx.x >> 2) * S::WIN;
   // ---- template + gradients at the integer reference position (getPatchStaticNNGrad, patch.cpp:297-343)
   f2p tmp2[K], gx2[K], gy2[NOP == 2 ? K : 1];
@@ -1779,24 +1858,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
     if (NOP == 2) {
       H01 = quad_total(h1);
       H11 = quad_total(h2);
-      if (H00 * H11 - H01 * H01 == 0.0f) {
-        H00 = (float)((double)H00 + 1e-10);
-        H11 = (float)((double)H11 + 1e-10);
-      }
-    } else if (H00 == 0.0f) {
-      H00 = (float)((double)H00 + 1e-10);
     }
+    hessian_regularise<NOP>(H00, H01, H11);
   }
   const Llt2 fac = llt2_factor(H00, H01, H11);
   const float fac1 = llt1_factor(H00);
   const LltRcp lrc = llt_rcp<NOP>(fac, fac1, a.fdiv != 0);
   if (a.stage == 1) {  // timing diagnostic "pconst"
-    if (live && s4 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp2[K - 1].y;
+    if (live && s4 == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp2[K - 1].y);
     return;
   }
   // ---- initial parameters (InitializeFromCoarserOF, patchgrid.cpp:195-211)
   float pin0 = 0.0f, pin1 = 0.0f;
-  if (a.prev) {
+  if (a.prev) {  // patch_init_coarser, spelled out: the helper changes this kernel's code
     const int x = (int)floorf(ptr0 / 2), y = (int)floorf(ptr1 / 2);
     const float *pv = a.prev + (long)f * a.prev_frame_stride + (long)(y * a.prev_w + x) * a.prev_elem_stride;
     pin0 = pv[0] * 2;
@@ -1804,7 +1878,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
   }
   if (a.stage == 2) {  // "pconst + pinit"
     if (live && s4 == 0)
-      a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp2[K - 1].y + pin0 + pin1;
+      a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp2[K - 1].y) + pin0 + pin1;
     return;
   }
   const float *Bimg = a.img_b + f * fs;
@@ -2144,19 +2218,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
   const long gp = (long)xb.x * 16 + (threadIdx.x >> 4);
   const bool live = gp < (long)a.n * g.npatch;
   const long gq = live ? gp : 0;
-  const int f = (int)(gq / g.npatch), ip = (int)(gq % g.npatch);
-  const int pxi = ip / g.noph, pyi = ip % g.noph;
-  const float ptr0 = (float)(pxi * a.steps + g.offw), ptr1 = (float)(pyi * a.steps + g.offh);
+  int f, pxi, pyi;
+  float ptr0, ptr1;
+  patch_decode(a, gq, f, pxi, pyi, ptr0, ptr1);
   const long fs = (long)g.W * g.H * NOC;
   const int W = g.W;
-  constexpr float inv_n = 1.0f / (float)S::NV;
-  constexpr bool pow2 = (S::NV & (S::NV - 1)) == 0;
-  auto div_n = [&](float x) {
-    if constexpr (pow2)
-      return x * inv_n;
-    else
-      return div_by_const<S::NV>(x);
-  };
+  auto div_n = [](float x) { return div_by_n<S::NV>(x); };
   float *win = win_all + (threadIdx.x >> 4) * S::WIN;
   // window offset of the D tap of value m: dbase[m mod KP] + (m / KP) KROWS RS
   auto dtap = [&](int v) { return (v / S::ROWV) * RS + v % S::ROWV; };
@@ -2208,31 +2275,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
     if (NOP == 2) {
       H01 = h1.total();
       H11 = h2.total();
-      if (H00 * H11 - H01 * H01 == 0.0f) {
-        H00 = (float)((double)H00 + 1e-10);
-        H11 = (float)((double)H11 + 1e-10);
-      }
-    } else if (H00 == 0.0f) {
-      H00 = (float)((double)H00 + 1e-10);
     }
+    hessian_regularise<NOP>(H00, H01, H11);
   }
   const Llt2 fac = llt2_factor(H00, H01, H11);
   const float fac1 = llt1_factor(H00);
   const LltRcp lrc = llt_rcp<NOP>(fac, fac1, a.fdiv != 0);
   if (a.stage == 1) {  // timing diagnostic "pconst"
-    if (live && s16 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[M - 1];
+    if (live && s16 == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[M - 1]);
     return;
   }
   // ---- initial parameters (InitializeFromCoarserOF, patchgrid.cpp:195-211)
-  float pin0 = 0.0f, pin1 = 0.0f;
-  if (a.prev) {
-    const int x = (int)floorf(ptr0 / 2), y = (int)floorf(ptr1 / 2);
-    const float *pv = a.prev + (long)f * a.prev_frame_stride + (long)(y * a.prev_w + x) * a.prev_elem_stride;
-    pin0 = pv[0] * 2;
-    if (NOP == 2) pin1 = pv[a.prev_comp_stride] * 2;
-  }
+  float pin0, pin1;
+  patch_init_coarser<NOP>(a, f, ptr0, ptr1, pin0, pin1);
   if (a.stage == 2) {  // "pconst + pinit"
-    if (live && s16 == 0) a.p_iter[gp * NOP] = fac.L00 + fac.L10 + fac.L11 + fac1 + tmp[M - 1] + pin0 + pin1;
+    if (live && s16 == 0) a.p_iter[gp * NOP] = patch_stage_value(fac, fac1, tmp[M - 1]) + pin0 + pin1;
     return;
   }
   // the scaled FAST evaluation's condition (see evaluate): every nonzero gradient of the wave's patches >= 2^-51
@@ -2602,6 +2659,117 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MINW))) voi
   if (live && s16 < NOP) a.p_iter[gp * NOP + s16] = s16 == 0 ? p0 : p1;
 }
 
+}  // namespace
+// ---- launch
+template <int JM>
+static void patch_jm(const PatchArgs &a, hipStream_t s) {
+  const long waves = (long)a.n * a.g.npatch;
+  const int rs = JM == 1 ? 64 : ((a.novals + 31) / 32) * 32 + 8;
+  const size_t lds = sizeof(float) * 3 * rs * kPatchWaves;
+  pick_nop(a.nop, [&](auto NOP) {
+    k_patch<NOP, JM><<<ceil_div(waves, kPatchWaves), 64 * kPatchWaves, lds, s>>>(a);
+  });
+}
+template <int PAIRS, int ODD>
+static void patch8(const PatchArgs &a, hipStream_t s) {
+  const long patches = (long)a.n * a.g.npatch;
+  pick_nop(a.nop, [&](auto NOP) { k_patch8<NOP, PAIRS, ODD><<<ceil_div(patches, 32), 256, 0, s>>>(a); });
+}
+static void patchg(const PatchArgs &a, hipStream_t s) {
+  const long patches = (long)a.n * a.g.npatch;
+  pick_nop(a.nop, [&](auto NOP) { k_patchg<NOP><<<ceil_div(patches, 32), 256, 0, s>>>(a); });
+}
+// costfct x nop -> the (NOP, MINW, COST) arguments of a windowed family: f(Int<NOP>, Int<MINW>, Int<COST>).
+// MINW1 / MINW2: waves per SIMD for the depth (nop 1) / flow (nop 2) forms, chosen so that nothing spills
+// MINW0 (k_patchw only; 0 = none): waves per SIMD of the L2-cost (costfct 0) instances instead
+template <int MINW1, int MINW2, int MINW0 = 0, class F>
+static void pick_patch_form(const PatchArgs &a, F &&f) {
+  pick<0, 1, 2>(a.costfct == 0 || a.costfct == 1 ? a.costfct : 2, [&](auto COST) {
+    pick_nop(a.nop, [&](auto NOP) {
+      constexpr int MINW = COST == 0 && MINW0 ? MINW0 : NOP == 2 ? MINW2 : MINW1;
+      f(NOP, Int<MINW>{}, COST);
+    });
+  });
+}
+template <int P, int NOC, int MINW1, int MINW2, int MINW0 = 0>
+static void patchw(const PatchArgs &a, hipStream_t s) {
+  const dim3 grid(ceil_div((long)a.n * a.g.npatch, 32));
+  const size_t lds = sizeof(float) * 32 * PatchShape<P, NOC>::WIN;
+  pick_patch_form<MINW1, MINW2, MINW0>(a, [&](auto NOP, auto MINW, auto COST) {
+    k_patchw<NOP, P, NOC, MINW, COST><<<grid, 256, lds, s>>>(a);
+  });
+}
+template <int P, int NOC, int MINW1, int MINW2>
+static void patchq(const PatchArgs &a, hipStream_t s) {
+  const dim3 grid(ceil_div((long)a.n * a.g.npatch, 64));
+  const size_t lds = sizeof(float) * 64 * QuadShape<P, NOC>::WIN;
+  pick_patch_form<MINW1, MINW2>(a, [&](auto NOP, auto MINW, auto COST) {
+    k_patchq<NOP, P, NOC, MINW, COST><<<grid, 256, lds, s>>>(a);
+  });
+}
+template <int P, int NOC, int MINW>
+static void patchx(const PatchArgs &a, hipStream_t s) {
+  const dim3 grid(ceil_div((long)a.n * a.g.npatch, 16));
+  const size_t lds = sizeof(float) * XShape<P, NOC>::lds_floats(a.nop == 2 ? 2 : 1);
+  pick_patch_form<MINW, MINW>(a, [&](auto NOP, auto MW, auto COST) {
+    k_patchx<NOP, P, NOC, MW, COST><<<grid, 256, lds, s>>>(a);
+  });
+}
+void launch_patch_loss(const PatchArgs &a, hipStream_t s);
+bool launch_patch(const PatchArgs &a, hipStream_t s) {
+  if (a.window && a.x16 && !a.wave_per_patch && !a.generic && a.p == 12 && a.noc == 3) {  // sixteen lanes per patch
+    patchx<12, 3, 3>(a, s);
+    return a.absw != 0;
+  }
+  if (a.window && a.quad && !a.wave_per_patch && !a.generic && a.noc == 1 && (a.p == 8 || a.p == 12)) {
+    launch_patch_loss(a, s);  // k_patchq: the aggregation weights too
+    return a.absw != 0;
+  }
+  PatchArgs b = a;
+  b.absw = 0;  // the other kernels write the loss weights
+  launch_patch_loss(b, s);
+  return false;
+}
+void launch_patch_loss(const PatchArgs &a, hipStream_t s) {
+  if (a.window && a.quad && !a.wave_per_patch && !a.generic) {  // four lanes per patch: gray p = 8 / 12
+    switch (a.p * 4 + a.noc) {
+      case 8 * 4 + 1: patchq<8, 1, 4, 3>(a, s); return;
+      case 12 * 4 + 1: patchq<12, 1, 3, 2>(a, s); return;
+    }
+  }
+  if (a.window && !a.wave_per_patch && !a.generic) {  // LDS-windowed eight-lane form for the shapes of the op-points
+    switch (a.p * 4 + a.noc) {
+      case 8 * 4 + 1: patchw<8, 1, 4, 4>(a, s); return;
+      case 12 * 4 + 1: patchw<12, 1, 4, 3>(a, s); return;
+      case 8 * 4 + 3: patchw<8, 3, 2, 2>(a, s); return;
+      case 12 * 4 + 3: patchw<12, 3, 2, 2, 1>(a, s); return;  // L2 cost: samples kept, one wave per SIMD
+    }
+  }
+  if (!a.wave_per_patch && !a.generic) {
+    switch (a.novals) {  // eight lanes per patch for the common shapes
+      case 64: patch8<8, 0>(a, s); return;    // p 8, gray
+      case 144: patch8<18, 0>(a, s); return;  // p 12, gray
+      case 192: patch8<24, 0>(a, s); return;  // p 8, RGB
+      case 36: patch8<4, 1>(a, s); return;    // p 6, gray
+      case 100: patch8<12, 1>(a, s); return;  // p 10, gray
+      case 16: patch8<2, 0>(a, s); return;    // p 4, gray
+      case 4: patch8<0, 1>(a, s); return;     // p 2, gray
+    }
+  }
+  const int J = (a.novals + 63) / 64;
+  if (a.generic || J > 7) {  // any shape: runtime value loops (p^2 noc > 448, or forced by option patch_generic)
+    patchg(a, s);
+    return;
+  }
+  if (J <= 1)
+    patch_jm<1>(a, s);
+  else if (J <= 3)
+    patch_jm<3>(a, s);
+  else
+    patch_jm<7>(a, s);
+}
+namespace {
+
 // ------------------------------------------------------------------------------------------------ aggregation
 
 // Forward-backward merging (usefbcon, patchgrid.cpp:277-375): the complementary grid's patch q, at its
@@ -2737,11 +2905,16 @@ __global__ __launch_bounds__(256) void k_aggregate(AggArgs a) {
   }
 }
 
+}  // namespace
+// ---- launch
+void launch_aggregate(const AggArgs &a, hipStream_t s) {
+  k_aggregate<<<dim3(ceil_div(a.g.w, 64), ceil_div(a.g.h, 16), a.n), 256, 0, s>>>(a);
+}
+namespace {
+
 // ------------------------------------------------------------------------------------------------ variational
 
 
-// image_warp (opticalflow_aux.c:31-75) + the mean / temporal images of get_derivatives (:88-99), plus the
-// skewed copies of the level flow and du = dv = 0 (refine_variational.cpp:185-190).  Row-major threads.
 // image_warp (opticalflow_aux.c:31-75) + the t / It inputs of get_derivatives (:77-132) for pixel (x, y):
 // v = {mask, wx, wy, t[0..noc), dt[0..noc)}.
 __device__ __forceinline__ void tv_prep_values(const TvArgs &a, int x, int y, int f, float *v) {
@@ -2821,7 +2994,6 @@ __global__ __launch_bounds__(256) void k_tv_prep(TvArgs a) {
   }
 }
 
-
 // 5-tap filters (image.cpp:419-624 fast paths) with replicate border, on a skewed plane.
 __device__ __forceinline__ float conv5h(const float *s, int x, int y, int w, int h, int wr) {
   const float s0 = s[skw(clampi(x - 2, 0, w - 1), y, h, w, wr)], s1 = s[skw(clampi(x - 1, 0, w - 1), y, h, w, wr)];
@@ -2836,7 +3008,6 @@ __device__ __forceinline__ float conv5v(const float *s, int x, int y, int w, int
   return kK5[0] * s0 + ((kK5[1] * s1 + kK5[2] * s2) + (kK5[3] * s3 + kK5[4] * s4));
 }
 
-
 // ---- prep + derivatives in one launch: image_warp and get_derivatives' t / It (opticalflow_aux.c:31-132) on a
 // row-major tile with a 4-pixel halo in LDS, the first derivatives Ix, Iy of t on the tile with a 2-pixel halo, then
 // per core pixel the remaining 5-tap filters (Ixz, Iyz of It; Ixx, Ixy of Ix; Iyy of Iy) straight from LDS and every
@@ -2846,86 +3017,79 @@ __device__ __forceinline__ float conv5v(const float *s, int x, int y, int w, int
 // through memory.  Intensity images; colour images (color_image_convolve_hv filters every channel alike:
 // image.cpp:737-760) take k_tv_prepd_c3 below, every phase over the three channels.
 constexpr int kPdW = 64, kPdH = 16;
-template <int NOC>
 __global__ __launch_bounds__(256) void k_tv_prepd(TvArgs a) {
   const uint3 xb = xcd_block();
   constexpr int H4 = kPdH + 8, W4 = kPdW + 8, H2 = kPdH + 4, W2 = kPdW + 4;
   __shared__ float T[H4][W4], DT[H4][W4], IX[H2][W2], IY[H2][W2], WX[kPdH][kPdW], WY[kPdH][kPdW];
   const int x0 = xb.x * kPdW, y0 = xb.y * kPdH, f = xb.z;
   const int w = a.w, h = a.h;
-#pragma unroll 1
-  for (int ch = 0; ch < NOC; ++ch) {
-    if (ch > 0) __syncthreads();  // the previous channel's phase C has read the tiles
-    // phase A: t, It at every halo-4 position (the clamped pixel's values), the flow of the core
-    for (int i = threadIdx.x; i < H4 * W4; i += 256) {
-      const int ly = i / W4, lx = i - ly * W4;
-      const int xx = x0 - 4 + lx, yy = y0 - 4 + ly;
-      const int cx = clampi(xx, 0, w - 1), cy = clampi(yy, 0, h - 1);
-      float t, it, wx, wy;
-      tv_prep_values_ch(a, cx, cy, f, ch, t, it, wx, wy);
-      T[ly][lx] = t;
-      DT[ly][lx] = it;
-      const int cxl = lx - 4, cyl = ly - 4;
-      if (ch == 0 && cxl >= 0 && cxl < kPdW && cyl >= 0 && cyl < kPdH) {
-        WX[cyl][cxl] = wx;
-        WY[cyl][cxl] = wy;
-      }
+  // phase A: t, It at every halo-4 position (the clamped pixel's values), the flow of the core
+  for (int i = threadIdx.x; i < H4 * W4; i += 256) {
+    const int ly = i / W4, lx = i - ly * W4;
+    const int xx = x0 - 4 + lx, yy = y0 - 4 + ly;
+    const int cx = clampi(xx, 0, w - 1), cy = clampi(yy, 0, h - 1);
+    float t, it, wx, wy;
+    tv_prep_values_ch(a, cx, cy, f, 0, t, it, wx, wy);
+    T[ly][lx] = t;
+    DT[ly][lx] = it;
+    const int cxl = lx - 4, cyl = ly - 4;
+    if (cxl >= 0 && cxl < kPdW && cyl >= 0 && cyl < kPdH) {
+      WX[cyl][cxl] = wx;
+      WY[cyl][cxl] = wy;
     }
-    __syncthreads();
-    // phase B: Ix, Iy at every halo-2 position (of the clamped pixel): conv5h / conv5v of t
-    for (int i = threadIdx.x; i < H2 * W2; i += 256) {
-      const int ly = i / W2, lx = i - ly * W2;
-      const int cx = clampi(x0 - 2 + lx, 0, w - 1), cy = clampi(y0 - 2 + ly, 0, h - 1);
-      const int tx = cx - x0 + 4, ty = cy - y0 + 4;  // the clamped pixel in T (within the halo)
-      IX[ly][lx] = kK5[0] * T[ty][tx - 2] + ((kK5[1] * T[ty][tx - 1] + kK5[2] * T[ty][tx]) +
-                                            (kK5[3] * T[ty][tx + 1] + kK5[4] * T[ty][tx + 2]));
-      IY[ly][lx] = kK5[0] * T[ty - 2][tx] + ((kK5[1] * T[ty - 1][tx] + kK5[2] * T[ty][tx]) +
-                                            (kK5[3] * T[ty + 1][tx] + kK5[4] * T[ty + 2][tx]));
+  }
+  __syncthreads();
+  // phase B: Ix, Iy at every halo-2 position (of the clamped pixel): conv5h / conv5v of t
+  for (int i = threadIdx.x; i < H2 * W2; i += 256) {
+    const int ly = i / W2, lx = i - ly * W2;
+    const int cx = clampi(x0 - 2 + lx, 0, w - 1), cy = clampi(y0 - 2 + ly, 0, h - 1);
+    const int tx = cx - x0 + 4, ty = cy - y0 + 4;  // the clamped pixel in T (within the halo)
+    IX[ly][lx] = kK5[0] * T[ty][tx - 2] + ((kK5[1] * T[ty][tx - 1] + kK5[2] * T[ty][tx]) +
+                                          (kK5[3] * T[ty][tx + 1] + kK5[4] * T[ty][tx + 2]));
+    IY[ly][lx] = kK5[0] * T[ty - 2][tx] + ((kK5[1] * T[ty - 1][tx] + kK5[2] * T[ty][tx]) +
+                                          (kK5[3] * T[ty + 1][tx] + kK5[4] * T[ty + 2][tx]));
+  }
+  __syncthreads();
+  // phase C: the core pixels in anti-diagonal order
+  constexpr int TD = kPdW + kPdH - 1;
+  for (int i = threadIdx.x; i < TD * kPdH; i += 256) {
+    const int yy = i & (kPdH - 1), dd = i / kPdH, xl = dd - yy;
+    const int x = x0 + xl, y = y0 + yy;
+    if (xl < 0 || xl >= kPdW || x >= w || y >= h) continue;
+    const int tx = xl + 4, ty = yy + 4, ix = xl + 2, iy = yy + 2;
+    const float ixz = kK5[0] * DT[ty][tx - 2] + ((kK5[1] * DT[ty][tx - 1] + kK5[2] * DT[ty][tx]) +
+                                               (kK5[3] * DT[ty][tx + 1] + kK5[4] * DT[ty][tx + 2]));
+    const float iyz = kK5[0] * DT[ty - 2][tx] + ((kK5[1] * DT[ty - 1][tx] + kK5[2] * DT[ty][tx]) +
+                                               (kK5[3] * DT[ty + 1][tx] + kK5[4] * DT[ty + 2][tx]));
+    const float ixx = kK5[0] * IX[iy][ix - 2] + ((kK5[1] * IX[iy][ix - 1] + kK5[2] * IX[iy][ix]) +
+                                               (kK5[3] * IX[iy][ix + 1] + kK5[4] * IX[iy][ix + 2]));
+    const float ixy = kK5[0] * IX[iy - 2][ix] + ((kK5[1] * IX[iy - 1][ix] + kK5[2] * IX[iy][ix]) +
+                                               (kK5[3] * IX[iy + 1][ix] + kK5[4] * IX[iy + 2][ix]));
+    const float iyy = kK5[0] * IY[iy - 2][ix] + ((kK5[1] * IY[iy - 1][ix] + kK5[2] * IY[iy][ix]) +
+                                               (kK5[3] * IY[iy + 1][ix] + kK5[4] * IY[iy + 2][ix]));
+    // lat: the colour-split entry layout of the fused red-black level launch, which keeps (du, dv) in LDS
+    const long sk = a.lat ? lat_idx(x, y, w, lat_entries(w, h)) : skw(x, y, h, w, a.wrap), k = (long)f * a.sp + sk;
+    a.wxs[k] = WX[yy][xl];
+    if (a.nop == 2) a.wys[k] = WY[yy][xl];
+    if (!a.lat) {
+      a.du[k] = 0.0f;
+      if (a.nop == 2) a.dv[k] = 0.0f;
     }
-    __syncthreads();
-    // phase C: the core pixels in anti-diagonal order
-    constexpr int TD = kPdW + kPdH - 1;
-    for (int i = threadIdx.x; i < TD * kPdH; i += 256) {
-      const int yy = i & (kPdH - 1), dd = i / kPdH, xl = dd - yy;
-      const int x = x0 + xl, y = y0 + yy;
-      if (xl < 0 || xl >= kPdW || x >= w || y >= h) continue;
-      const int tx = xl + 4, ty = yy + 4, ix = xl + 2, iy = yy + 2;
-      const float ixz = kK5[0] * DT[ty][tx - 2] + ((kK5[1] * DT[ty][tx - 1] + kK5[2] * DT[ty][tx]) +
-                                                 (kK5[3] * DT[ty][tx + 1] + kK5[4] * DT[ty][tx + 2]));
-      const float iyz = kK5[0] * DT[ty - 2][tx] + ((kK5[1] * DT[ty - 1][tx] + kK5[2] * DT[ty][tx]) +
-                                                 (kK5[3] * DT[ty + 1][tx] + kK5[4] * DT[ty + 2][tx]));
-      const float ixx = kK5[0] * IX[iy][ix - 2] + ((kK5[1] * IX[iy][ix - 1] + kK5[2] * IX[iy][ix]) +
-                                                 (kK5[3] * IX[iy][ix + 1] + kK5[4] * IX[iy][ix + 2]));
-      const float ixy = kK5[0] * IX[iy - 2][ix] + ((kK5[1] * IX[iy - 1][ix] + kK5[2] * IX[iy][ix]) +
-                                                 (kK5[3] * IX[iy + 1][ix] + kK5[4] * IX[iy + 2][ix]));
-      const float iyy = kK5[0] * IY[iy - 2][ix] + ((kK5[1] * IY[iy - 1][ix] + kK5[2] * IY[iy][ix]) +
-                                                 (kK5[3] * IY[iy + 1][ix] + kK5[4] * IY[iy + 2][ix]));
-      // lat: the colour-split entry layout of the fused red-black level launch, which keeps (du, dv) in LDS
-      const long sk = a.lat ? lat_idx(x, y, w, lat_entries(w, h)) : skw(x, y, h, w, a.wrap), k = (long)f * a.sp + sk;
-      if (ch == 0) {
-        a.wxs[k] = WX[yy][xl];
-        if (a.nop == 2) a.wys[k] = WY[yy][xl];
-        if (!a.lat) {
-          a.du[k] = 0.0f;
-          if (a.nop == 2) a.dv[k] = 0.0f;
-        }
-      }
-      const long q = ((long)f * NOC + ch) * a.sp + sk;
-      a.Iz[q] = DT[ty][tx];
-      a.Ix[q] = IX[iy][ix];
-      a.Iy[q] = IY[iy][ix];
-      if (a.smsys_deriv) continue;  // the system kernel filters Ix, Iy, Iz itself
-      a.Ixx[q] = ixx;
-      a.Ixy[q] = ixy;
-      a.Iyy[q] = iyy;
-      a.Ixz[q] = ixz;
-      a.Iyz[q] = iyz;
-    }
+    const long q = k;  // one channel: the derivative planes are indexed like the flow
+    a.Iz[q] = DT[ty][tx];
+    a.Ix[q] = IX[iy][ix];
+    a.Iy[q] = IY[iy][ix];
+    if (a.smsys_deriv) continue;  // the system kernel filters Ix, Iy, Iz itself
+    a.Ixx[q] = ixx;
+    a.Ixy[q] = ixy;
+    a.Iyy[q] = iyy;
+    a.Ixz[q] = ixz;
+    a.Iyz[q] = iyz;
   }
 }
 
-// Colour images, all eight planes (levels whose system kernel reads them): k_tv_prepd<3> with the three channels in
-// each phase instead of the phases once per channel -- the flow, warp position and bilinear weights once per halo
+// Colour images, all eight planes (levels whose system kernel reads them): k_tv_prepd's phases with the three
+// channels in each phase -- the flow, warp position and bilinear weights once per halo
 // position (tv_prep_values_all), It kept on the 2-pixel halo only (Ixz / Iyz), and two barriers instead of eight.
 // 78 KB of LDS: two workgroups per CU.  Same expressions, same bits.  Config C: 3.36 -> 3.15 ms of prep per
 // 512-pair step (r06_s11), the 240 x 135 level 554 -> 471 us per 256 pairs (r06_s12).
@@ -3124,6 +3288,39 @@ __global__ __launch_bounds__(256) void k_tv_deriv2(TvArgs a) {
   if (kk < a.sp) tv_deriv2_px(a, b.y, kk);
 }
 
+}  // namespace
+// ---- launch
+void launch_tv_prep(const TvArgs &a, hipStream_t s) {  // NP = 3 + 2 noc values per pixel, tile rows to fit the LDS
+  if (a.noc == 1)
+    k_tv_prep<5, 32><<<dim3(ceil_div(a.w, kTileW), ceil_div(a.h, 32), a.n), 256, 0, s>>>(a);
+  else
+    k_tv_prep<9, 16><<<dim3(ceil_div(a.w, kTileW), ceil_div(a.h, 16), a.n), 256, 0, s>>>(a);
+}
+// prep + derivatives in one launch: intensity images (option prepd), colour images too with prepd = 2 (default)
+bool tv_prepd_ok(const TvArgs &a) { return a.prepd && (a.noc == 1 || a.prepd == 2); }
+void launch_tv_prepd(const TvArgs &a, hipStream_t s) {
+  const dim3 grid(ceil_div(a.w, kPdW), ceil_div(a.h, kPdH), a.n);
+  if (a.smsys_deriv && !a.lat && a.prepd_df) {  // tv_deriv_fused(): Ix, Iy, Iz only
+    // tall levels (the march's, h >= 256) on 64 x 32 tiles, 512 threads: halo 1.33x -> 1.2x the core, the same
+    // occupancy; config E's prep 3.06 -> 2.61 ms per step, C's 3.16 -> 3.04 (profiles/r06/s29); short levels keep
+    // 16 rows (B's 68-row levels would compute 96)
+    pick<kPdH, 32>(a.h >= 256 ? 32 : kPdH, [&](auto TH) {
+      const dim3 g(ceil_div(a.w, kPdW), ceil_div(a.h, TH), a.n);
+      pick_noc(a.noc, [&](auto NOC) { k_tv_prepd_df<NOC, TH><<<g, 16 * TH, 0, s>>>(a); });
+    });
+    return;
+  }
+  // intensity images: Ix, Iy, Iz only where a.smsys_deriv (prepd_df = 0, lat); colour images: always all eight planes
+  if (a.noc == 1) k_tv_prepd<<<grid, 256, 0, s>>>(a);
+  else k_tv_prepd_c3<<<grid, 256, 0, s>>>(a);
+}
+void launch_tv_deriv1(const TvArgs &a, hipStream_t s) {
+  k_tv_deriv1<<<dim3(ceil_div(a.sp, 256), a.n * a.noc), 256, 0, s>>>(a);
+}
+void launch_tv_deriv2(const TvArgs &a, hipStream_t s) {
+  k_tv_deriv2<<<dim3(ceil_div(a.sp, 256), a.n * a.noc), 256, 0, s>>>(a);
+}
+namespace {
 
 // compute_smoothness (opticalflow_aux.c:138-160): s = (alpha/4) / sqrt(eps + |grad u|^2 + |grad v|^2)
 template <int NOP>
@@ -3149,7 +3346,6 @@ __device__ __forceinline__ void tv_smooth_px(const TvArgs &a, long fr, int kk, b
   }
   a.s[idx] = smooth_compute<NOP>(a, first, wx5, du5, wy5, dv5);
 }
-
 
 // One TV inner iteration's system (refine_variational.cpp:195-199): diffusivities from s
 // (opticalflow_aux.c:161-184), data term (:408-747) and sub_laplacian (:194-223).
@@ -3245,14 +3441,20 @@ __host__ __device__ __forceinline__ int smsys_rb_n(int h, int rows, int n, int s
 __host__ __device__ __forceinline__ size_t smsys_lds_df(int h, int rb, bool df) {
   return smsys_lds_rb(h, rb) + (df ? (size_t)3 * (rb + 4) * h * 4 : 0);
 }
+// Rows per workgroup of the DF form: four workgroups per CU (five, at 32 KB: slower, r03_s49).  The launch and
+// tv_deriv_fused take it from here; k_tv_smsys spells the same loop out.
 constexpr size_t kSmsysDfCap = 40 * 1024;
+__host__ __device__ __forceinline__ int smsys_rb_df(int h, int rb) {
+  while (rb > 1 && smsys_lds_df(h, rb, true) > kSmsysDfCap) --rb;
+  return rb;
+}
 template <int NOP, int NOC, bool DF = false>
 __global__ __launch_bounds__(256) void k_tv_smsys(TvArgs a) {
   extern __shared__ float4 st[];  // [(RB + 4) * h] (wx, wy, du, dv), then float s[(RB + 2) * h] (DF: Ix, Iy, Iz)
   static_assert(!DF || NOC == 1, "staged derivatives: intensity images");
   const int w = a.w, h = a.h, rows = smsys_rows(w, h, a.wrap);
   int rb = smsys_rb_n(h, rows, a.n, a.smsys_small);
-  if (DF)  // four workgroups per CU (five, at 32 KB: slower, r03_s49); the launcher applies the same rule
+  if (DF)  // smsys_rb_df, spelled out: calling it here changes this kernel's code
     while (rb > 1 && smsys_lds_df(h, rb, true) > kSmsysDfCap) --rb;
   float *sl = reinterpret_cast<float *>(st + (rb + 4) * h);
   float *gIx = sl + (rb + 2) * h, *gIy = gIx + (rb + 4) * h, *gIz = gIy + (rb + 4) * h;  // DF
@@ -3718,6 +3920,69 @@ __global__ __launch_bounds__(256) void k_tv_smsys2d(TvArgs a) {
   }
 }
 
+}  // namespace
+// ---- launch
+void launch_tv_smooth(const TvArgs &a, hipStream_t s) {
+  pick_nop(a.nop, [&](auto NOP) { k_tv_smooth<NOP><<<dim3(ceil_div(a.sp, 256), a.n), 256, 0, s>>>(a); });
+}
+void launch_tv_system(const TvArgs &a, hipStream_t s) {
+  const dim3 grid(ceil_div(a.sp, 256), a.n);
+  pick_nop(a.nop, [&](auto NOP) {
+    pick_noc(a.noc, [&](auto NOC) { k_tv_system<NOP, NOC><<<grid, 256, 0, s>>>(a); });
+  });
+}
+// The fused form stages RB + 4 rows for RB computed ones: below RB = 4 (h > 256) the halo re-reads cost
+// more than the smoothness round trip saves (config E, h = 544 / 272: 518 vs 299 us per launch).
+// Tall levels take the 2-D tiled form (k_tv_smsys2d) unless a.smsys2d = 0 (A/B: two launches there).
+static bool smsys_rowblock_fits(int h) { return smsys_rb(h) >= 4 && smsys_lds(h) <= 64 * 1024; }
+// The register march for a level: tall levels (no row block fits).  (Colour levels of 135 rows on the march too: prep
+// -0.50 ms, system +0.62 ms per config-C step, r06_s13: not taken.)
+static bool smsys_use_march(const TvArgs &a) { return a.smsys_march && !smsys_rowblock_fits(a.h); }
+bool tv_smsys_ok(const TvArgs &a) { return a.smsys && (smsys_rowblock_fits(a.h) || a.smsys2d || a.smsys_march); }
+// The derivative filters move into the system kernel where the level runs k_tv_prepd (intensity images) and the
+// row-block k_tv_smsys or the march k_tv_smsys_m (round 4); the 2-D tiles and the two-launch form read all eight planes.
+// Not where the 40 KB LDS cap of the DF form leaves fewer than 3 rows per block (levels of ~180-256 rows): a
+// block would then stage 5-6 rows of seven planes for 1-2 computed ones, 3-5x redundant staging.
+bool tv_deriv_fused(const TvArgs &a) {
+  if (!(a.smsys_deriv && tv_prepd_ok(a) && a.smsys)) return false;
+  if (smsys_use_march(a)) return true;  // the march filters them too
+  if (!smsys_rowblock_fits(a.h)) return false;
+  if (a.noc != 1) return false;  // colour images: the march only (a row block would stage 9 derivative planes)
+  return smsys_rb_df(a.h, smsys_rb_n(a.h, smsys_rows(a.w, a.h, a.wrap), a.n, a.smsys_small)) >= 3;
+}
+void launch_tv_smsys(const TvArgs &a, hipStream_t s) {
+  const int rows = smsys_rows(a.w, a.h, a.wrap);
+  if (smsys_use_march(a)) {
+    const unsigned grid = ceil_div((long)a.n * march_segments(rows) * march_strips(a.h), 4);
+    pick_nop(a.nop, [&](auto NOP) {
+      pick_noc(a.noc, [&](auto NOC) {
+        if (a.smsys_deriv) k_tv_smsys_m<NOP, NOC, true><<<grid, 256, 0, s>>>(a);  // tv_deriv_fused(): Ix, Iy, Iz only
+        else k_tv_smsys_m<NOP, NOC><<<grid, 256, 0, s>>>(a);
+      });
+    });
+    return;
+  }
+  if (!smsys_rowblock_fits(a.h)) {
+    const dim3 g2(a.n, ceil_div(rows, kS2R), ceil_div(a.h, kS2C));
+    pick_nop(a.nop, [&](auto NOP) {
+      pick_noc(a.noc, [&](auto NOC) { k_tv_smsys2d<NOP, NOC><<<g2, 256, 0, s>>>(a); });
+    });
+    return;
+  }
+  const int rb0 = smsys_rb_n(a.h, rows, a.n, a.smsys_small);
+  if (a.smsys_deriv) {  // tv_deriv_fused(): intensity images only
+    const int rb = smsys_rb_df(a.h, rb0);
+    const size_t lds = smsys_lds_df(a.h, rb, true);
+    pick_nop(a.nop, [&](auto NOP) { k_tv_smsys<NOP, 1, true><<<dim3(a.n, ceil_div(rows, rb)), 256, lds, s>>>(a); });
+    return;
+  }
+  const size_t lds = smsys_lds_rb(a.h, rb0);
+  pick_nop(a.nop, [&](auto NOP) {
+    pick_noc(a.noc, [&](auto NOC) { k_tv_smsys<NOP, NOC><<<dim3(a.n, ceil_div(rows, rb0)), 256, lds, s>>>(a); });
+  });
+}
+namespace {
+
 // Generic exact-order SOR (any size / sweep count): one workgroup per frame, in-place skewed arrays in
 // global memory, one barrier per wavefront step.  Pixel (x, y) of sweep s runs at step t = x + y + 2 s:
 // its left/top neighbours of the same sweep ran at t-1, its right/bottom neighbours of the previous
@@ -3801,7 +4066,6 @@ __global__ __launch_bounds__(256) void k_tv_sor(TvArgs a) {
 #undef SH_
 #undef SV_
 }
-
 
 #ifdef OFDIS_SOR_PROBE
 // Step-timing probe of the sweep-per-wave SOR (a separate build, tools/sor_probe.py; never in libofdis.so):
@@ -4129,7 +4393,6 @@ __device__ __forceinline__ int sor_row2(int d, int lim, int rmax) {
   return min(dd >= lim ? dd - lim : dd, rmax);
 }
 
-
 // Sweep-per-wave exact-order SOR, one row per lane.  Same wavefront as SorPipe (pixel (x, y) of sweep s at
 // step t = x + y + 2 s), but the S sweeps run on S different waves of the workgroup: wave (g, s) owns rows
 // 64 g .. 64 g + 63 of sweep s.  Per step every wave computes ONE pixel per lane and publishes its values
@@ -4416,7 +4679,7 @@ __host__ __device__ constexpr int sor_crn(int S, int MAXT, int R = 1) {
 
 // LDS of the lean SOR: S (u, v) rings of NR = 64 R G + 2 entries x 3 slots of float2, then S sv rings
 // (CRN = 0) or the coefficient ring (16-byte aligned): 6 slots x CRN entries of 32 (OF, cw = 2) / 16 (DE) bytes.
-__host__ __device__ __forceinline__ size_t sor_cring_bytes(int crn, int cw) { return (size_t)6 * crn * (cw == 2 ? 32 : 16); }
+__host__ __device__ constexpr size_t sor_cring_bytes(int crn, int cw) { return (size_t)6 * crn * (cw == 2 ? 32 : 16); }
 __host__ __device__ __forceinline__ size_t sor_lanes_lds(int S, int h, int crn, int cw, int R = 1) {
   const size_t nr = (size_t)((h + 64 * R - 1) / (64 * R)) * 64 * R + 2;
   const size_t uv = sizeof(float) * 2 * 3 * (size_t)S * nr;
@@ -4508,6 +4771,96 @@ __global__ __launch_bounds__(MAXT) void k_tv_sor_lanes(TvArgs a) {
   sor_lanes_frame<S, MODE, NB, crn, R, SEL>(a, blockIdx.x, ring_uv);
 }
 
+}  // namespace
+// ---- launch
+// MODE of the exact-order kernels: 0 = optical flow (sor_coupled), 2 = depth (sor_coupled_slow_but_readable_DE)
+template <class F>
+static void pick_mode(int nop, F &&f) { pick<0, 2>(nop == 2 ? 0 : 2, f); }
+template <int S>
+static void sor_pipe(const TvArgs &a, hipStream_t s) {
+  const int threads = ((a.h + 63) / 64) * 64;
+  pick<256, 512, 1024>(threads <= 256 ? 256 : threads <= 512 ? 512 : 1024, [&](auto MAXT) {
+    pick_mode(a.nop, [&](auto MODE) { k_tv_sor_pipe<S, MODE, MAXT><<<a.n, threads, 0, s>>>(a); });
+  });
+}
+// Sweep-per-wave SOR (k_tv_sor_lanes): 64 * ceil(h / (64 R)) * S threads, one workgroup per frame.  With S <= 3
+// sweep 0 hands the coefficients to the later sweeps through an LDS ring (option sor_cring, default on) while
+// it fits the LDS.  False (nothing launched) for a form that is not compiled: launch_tv_sor then takes the pipeline.
+template <int S, int MAXT, int R>
+static bool sor_lanes(const TvArgs &a, hipStream_t s) {
+  const int G = (a.h + 64 * R - 1) / (64 * R);
+  constexpr int crn = sor_crn(S, MAXT, R);
+  const int cw = a.nop == 2 ? 2 : 1;
+  const bool cring = crn > 0 && a.sor_cring && sor_lanes_lds(S, a.h, crn, cw, R) <= kSorLds;
+  // the clamped in-frame load form in throughput launches -- more frames than CUs -- and the lane-constant slots in
+  // latency launches, where the per-step v_med3 would sit on the wavefront's critical path (sor_cring 3: everywhere,
+  // parity).  Measured (profiles/r06/s5, s21): B's tv_sor 4.16 -> 4.00 ms per step and its counted bytes 1.33x ->
+  // 1.23x the compulsory ones, A's 1.82x -> 1.27x; the single pair 0.84 -> 0.91 ms with it everywhere.  Every form
+  // takes the same rule.
+  const bool sel = a.sor_cring >= 3 || (long)a.n > device_cus();
+  bool launched = false;
+  auto go = [&](auto CG, auto CR, size_t lds) {
+    // no ring at S == 4: sor_crn(4, ..) = 0, so cring is false and CRING = true would be the same code again
+    if constexpr (!(CR && crn == 0)) {
+      pick<0, 1>(sel, [&](auto SEL) {
+        pick_mode(a.nop, [&](auto MODE) {
+          // a ring that alone exceeds the LDS (S 2, R 2, optical flow: 6 * 1026 * 32 B): cring is false above
+          if constexpr (!(CR && sor_cring_bytes(crn, MODE == 0 ? 2 : 1) > kSorLds)) {
+            k_tv_sor_lanes<S, MODE, 3, MAXT, CR != 0, R, CG, SEL != 0><<<a.n, 64 * G * S, lds, s>>>(a);
+            launched = true;
+          }
+        });
+      });
+    }
+  };
+  if constexpr (S == 3 && R == 1) {  // the only forms with CG: the ring sized to the level's G row groups
+    if (cring && a.sor_cring >= 2) {
+      const size_t ldsg = sor_lanes_lds(S, a.h, 64 * G + 2, cw, R);
+      auto ring_g = [&](auto CG) { go(CG, Int<1>{}, ldsg); };
+      if constexpr (MAXT == 512) {  // 192 G threads: G = 1, 2 in 512, G = 3 .. 5 in 1024 (sor_lanes_s)
+        if (pick<1, 2>(G, ring_g)) return launched;
+      } else {
+        if (pick<3, 4, 5>(G, ring_g)) return launched;
+      }
+    }
+  }
+  pick<0, 1>(cring, [&](auto CR) { go(Int<0>{}, CR, sor_lanes_lds(S, a.h, CR ? crn : 0, cw, R)); });
+  return launched;
+}
+template <int S>
+static bool sor_lanes_s(const TvArgs &a, hipStream_t s) {
+  const int th = 64 * S * ((a.h + 63) / 64);  // at one row per lane
+  if (th <= 512) return sor_lanes<S, 512, 1>(a, s);
+  if (th <= 1024) return sor_lanes<S, 1024, 1>(a, s);
+  // two rows per lane: launch_tv_sor's lanes_fit admits S == 4 with G * 4 <= 16 only, which is th <= 1024
+  if constexpr (S <= 3) return sor_lanes<S, 1024, 2>(a, s);
+  return false;
+}
+// Exact-order SOR dispatch: the sweep-per-wave form while its S * ceil(h / 64) waves fit one workgroup,
+// the register pipeline (one wave per row group runs all sweeps) for taller levels, the generic
+// global-memory wavefront for the point SOR of the OpenMP build and degenerate sizes.
+void launch_tv_sor(const TvArgs &a, hipStream_t s) {
+  if (a.solverit < 1) return;
+  const bool tiny = a.nop == 2 && (a.w < 2 || a.h < 2 || a.sor_point);  // point SOR (solver.c:34-78)
+  if (a.sor_redblack && !tiny) {  // opt-in red-black order (not the reference's bits), levels over kLvPix pixels
+    const dim3 grid(ceil_div(a.w * a.h, 256), a.n);
+    pick_mode(a.nop, [&](auto MODE) {
+      for (int it = 0; it < 2 * a.solverit; ++it) k_tv_sor_rb<MODE><<<grid, 256, 0, s>>>(a, it & 1);
+    });
+    return;
+  }
+  const int G = (a.h + 63) / 64, G2 = (a.h + 127) / 128;  // row groups at one / two rows per lane
+  const bool lanes_fit = G * a.solverit <= 16 || (a.solverit <= 3 && G2 * a.solverit <= 16 && a.sor_rows2);
+  bool done = false;
+  if (!tiny && !a.sor_generic && a.sor_variant != 1 && lanes_fit)
+    pick<2, 3, 4>(a.solverit, [&](auto S) { done = sor_lanes_s<S>(a, s); });
+  if (done) return;
+  if (!tiny && a.h <= 1024 && !a.sor_generic && pick<1, 2, 3, 4>(a.solverit, [&](auto S) { sor_pipe<S>(a, s); }))
+    return;
+  pick<0, 1, 2>(a.nop == 1 ? 2 : tiny ? 1 : 0, [&](auto MODE) { k_tv_sor<MODE><<<a.n, 256, 0, s>>>(a); });
+}
+namespace {
+
 template <int TH>
 __global__ __launch_bounds__(256) void k_tv_final(TvArgs a) {
   const uint3 xb = xcd_block();
@@ -4539,6 +4892,13 @@ __global__ __launch_bounds__(256) void k_tv_final(TvArgs a) {
     if (a.nop == 2) WX[plane + o] = sm[1][yl][tx];
   }
 }
+
+}  // namespace
+// ---- launch
+void launch_tv_final(const TvArgs &a, hipStream_t s) {
+  k_tv_final<32><<<dim3(ceil_div(a.w, kTileW), ceil_div(a.h, 32), a.n), 256, 0, s>>>(a);
+}
+namespace {
 
 // ------------------------------------------------------------------------------------------------ output
 
@@ -4917,175 +5277,21 @@ __global__ __launch_bounds__(256) void k_upsample(UpArgs a) {
 }
 
 }  // namespace
-
-// ------------------------------------------------------------------------------------------------ launchers
-
-void launch_pyr_base(const PyrBaseArgs &a, hipStream_t s) {
-  const long total = 2L * a.n * a.h * a.w;
-  if (a.noc == 1 && a.log2s >= 2 && a.log2s <= 5) {
-    const unsigned blocks = (unsigned)ceil_div(total, 256);
-    switch (a.log2s) {
-      case 2: k_pyr_base_gray<2><<<blocks, 256, 0, s>>>(a); return;
-      case 3: k_pyr_base_gray<3><<<blocks, 256, 0, s>>>(a); return;
-      case 4: k_pyr_base_gray<4><<<blocks, 256, 0, s>>>(a); return;
-      case 5: k_pyr_base_gray<5><<<blocks, 256, 0, s>>>(a); return;
-    }
-  }
-  if (a.noc == 3 && a.rgb_sad && a.log2s >= 2 && a.log2s <= 4) {
-    const unsigned blocks = (unsigned)ceil_div(total, 256);
-    switch (a.log2s) {
-      case 2: k_pyr_base_rgb<2><<<blocks, 256, 0, s>>>(a); return;
-      case 3: k_pyr_base_rgb<3><<<blocks, 256, 0, s>>>(a); return;
-      case 4: k_pyr_base_rgb<4><<<blocks, 256, 0, s>>>(a); return;
-    }
-  }
-  k_pyr_base<<<dim3(ceil_div(a.w, 256), a.h, 2 * a.n), 256, 0, s>>>(a);
-}
-void launch_pyr_gradmag(const PyrGradmagArgs &a, hipStream_t s) {
-  k_pyr_gradmag<<<dim3(ceil_div(a.Wp, 256), a.Hp, 2 * a.n), 256, 0, s>>>(a);
-}
-void launch_pyr_down(const PyrDownArgs &a, hipStream_t s) {
-  k_pyr_down<<<std::min(ceil_div((long)a.n2 * a.h * a.w * a.noc, 256), 1u << 22), 256, 0, s>>>(a);  // grid-stride beyond
-}
-void launch_pyr_pad_grad(const PyrPadGradArgs &a, hipStream_t s) {
-  if (a.noc == 3 && a.per_value) {
-    k_pyr_pad_grad_v<3><<<std::min(ceil_div((long)a.n2 * (a.h + 2 * a.pad) * (a.w + 2 * a.pad) * 3, 256), 1u << 22),
-                          256, 0, s>>>(a);
-    return;
-  }
-  k_pyr_pad_grad<<<std::min(ceil_div((long)a.n2 * (a.h + 2 * a.pad) * (a.w + 2 * a.pad), 256), 1u << 22), 256, 0,
-                   s>>>(a);  // grid-stride beyond 2^22 workgroups
-}
-template <int JM>
-static void patch_jm(const PatchArgs &a, hipStream_t s) {
-  const long waves = (long)a.n * a.g.npatch;
-  const int rs = JM == 1 ? 64 : ((a.novals + 31) / 32) * 32 + 8;
-  const size_t lds = sizeof(float) * 3 * rs * kPatchWaves;
-  if (a.nop == 2)
-    k_patch<2, JM><<<ceil_div(waves, kPatchWaves), 64 * kPatchWaves, lds, s>>>(a);
-  else
-    k_patch<1, JM><<<ceil_div(waves, kPatchWaves), 64 * kPatchWaves, lds, s>>>(a);
-}
-template <int PAIRS, int ODD>
-static void patch8(const PatchArgs &a, hipStream_t s) {
-  const long patches = (long)a.n * a.g.npatch;
-  if (a.nop == 2)
-    k_patch8<2, PAIRS, ODD><<<ceil_div(patches, 32), 256, 0, s>>>(a);
-  else
-    k_patch8<1, PAIRS, ODD><<<ceil_div(patches, 32), 256, 0, s>>>(a);
-}
-// MINW1 / MINW2: waves per SIMD for the depth (nop 1) / flow (nop 2) forms, chosen so that nothing spills
-// MINW0: waves per SIMD of the L2-cost (costfct 0) instances
-template <int P, int NOC, int MINW1, int MINW2, int MINW0 = 0>
-static void patchw(const PatchArgs &a, hipStream_t s) {
-  const long patches = (long)a.n * a.g.npatch;
-  const size_t lds = sizeof(float) * 32 * PatchShape<P, NOC>::WIN;
-  const dim3 grid(ceil_div(patches, 32));
-  constexpr int M01 = MINW0 ? MINW0 : MINW1, M02 = MINW0 ? MINW0 : MINW2;
-  switch (a.costfct * 2 + (a.nop == 2 ? 1 : 0)) {
-    case 0: k_patchw<1, P, NOC, M01, 0><<<grid, 256, lds, s>>>(a); return;
-    case 1: k_patchw<2, P, NOC, M02, 0><<<grid, 256, lds, s>>>(a); return;
-    case 2: k_patchw<1, P, NOC, MINW1, 1><<<grid, 256, lds, s>>>(a); return;
-    case 3: k_patchw<2, P, NOC, MINW2, 1><<<grid, 256, lds, s>>>(a); return;
-    case 4: k_patchw<1, P, NOC, MINW1, 2><<<grid, 256, lds, s>>>(a); return;
-    default: k_patchw<2, P, NOC, MINW2, 2><<<grid, 256, lds, s>>>(a); return;
-  }
-}
-template <int P, int NOC, int MINW1, int MINW2>
-static void patchq(const PatchArgs &a, hipStream_t s) {
-  const long patches = (long)a.n * a.g.npatch;
-  const size_t lds = sizeof(float) * 64 * QuadShape<P, NOC>::WIN;
-  const dim3 grid(ceil_div(patches, 64));
-  switch (a.costfct * 2 + (a.nop == 2 ? 1 : 0)) {
-    case 0: k_patchq<1, P, NOC, MINW1, 0><<<grid, 256, lds, s>>>(a); return;
-    case 1: k_patchq<2, P, NOC, MINW2, 0><<<grid, 256, lds, s>>>(a); return;
-    case 2: k_patchq<1, P, NOC, MINW1, 1><<<grid, 256, lds, s>>>(a); return;
-    case 3: k_patchq<2, P, NOC, MINW2, 1><<<grid, 256, lds, s>>>(a); return;
-    case 4: k_patchq<1, P, NOC, MINW1, 2><<<grid, 256, lds, s>>>(a); return;
-    default: k_patchq<2, P, NOC, MINW2, 2><<<grid, 256, lds, s>>>(a); return;
-  }
-}
-template <int P, int NOC, int MINW>
-static void patchx(const PatchArgs &a, hipStream_t s) {
-  const long patches = (long)a.n * a.g.npatch;
-  const size_t lds = sizeof(float) * XShape<P, NOC>::lds_floats(a.nop == 2 ? 2 : 1);
-  const dim3 grid(ceil_div(patches, 16));
-  switch (a.costfct * 2 + (a.nop == 2 ? 1 : 0)) {
-    case 0: k_patchx<1, P, NOC, MINW, 0><<<grid, 256, lds, s>>>(a); return;
-    case 1: k_patchx<2, P, NOC, MINW, 0><<<grid, 256, lds, s>>>(a); return;
-    case 2: k_patchx<1, P, NOC, MINW, 1><<<grid, 256, lds, s>>>(a); return;
-    case 3: k_patchx<2, P, NOC, MINW, 1><<<grid, 256, lds, s>>>(a); return;
-    case 4: k_patchx<1, P, NOC, MINW, 2><<<grid, 256, lds, s>>>(a); return;
-    default: k_patchx<2, P, NOC, MINW, 2><<<grid, 256, lds, s>>>(a); return;
-  }
-}
-void launch_patch_loss(const PatchArgs &a, hipStream_t s);
-bool launch_patch(const PatchArgs &a, hipStream_t s) {
-  if (a.window && a.x16 && !a.wave_per_patch && !a.generic && a.p == 12 && a.noc == 3) {  // sixteen lanes per patch
-    patchx<12, 3, 3>(a, s);
-    return a.absw != 0;
-  }
-  if (a.window && a.quad && !a.wave_per_patch && !a.generic && a.noc == 1 && (a.p == 8 || a.p == 12)) {
-    launch_patch_loss(a, s);  // k_patchq: the aggregation weights too
-    return a.absw != 0;
-  }
-  PatchArgs b = a;
-  b.absw = 0;  // the other kernels write the loss weights
-  launch_patch_loss(b, s);
-  return false;
-}
-void launch_patch_loss(const PatchArgs &a, hipStream_t s) {
-  if (a.window && a.quad && !a.wave_per_patch && !a.generic) {  // four lanes per patch: gray p = 8 / 12
-    switch (a.p * 4 + a.noc) {
-      case 8 * 4 + 1: patchq<8, 1, 4, 3>(a, s); return;
-      case 12 * 4 + 1: patchq<12, 1, 3, 2>(a, s); return;
-    }
-  }
-  if (a.window && !a.wave_per_patch && !a.generic) {  // LDS-windowed eight-lane form for the shapes of the op-points
-    switch (a.p * 4 + a.noc) {
-      case 8 * 4 + 1: patchw<8, 1, 4, 4>(a, s); return;
-      case 12 * 4 + 1: patchw<12, 1, 4, 3>(a, s); return;
-      case 8 * 4 + 3: patchw<8, 3, 2, 2>(a, s); return;
-      case 12 * 4 + 3: patchw<12, 3, 2, 2, 1>(a, s); return;  // L2 cost: samples kept, one wave per SIMD
-    }
-  }
-  if (!a.wave_per_patch && !a.generic) {
-    switch (a.novals) {  // eight lanes per patch for the common shapes
-      case 64: patch8<8, 0>(a, s); return;    // p 8, gray
-      case 144: patch8<18, 0>(a, s); return;  // p 12, gray
-      case 192: patch8<24, 0>(a, s); return;  // p 8, RGB
-      case 36: patch8<4, 1>(a, s); return;    // p 6, gray
-      case 100: patch8<12, 1>(a, s); return;  // p 10, gray
-      case 16: patch8<2, 0>(a, s); return;    // p 4, gray
-      case 4: patch8<0, 1>(a, s); return;     // p 2, gray
-    }
-  }
-  const int J = (a.novals + 63) / 64;
-  if (a.generic || J > 7) {  // any shape: runtime value loops (p^2 noc > 448, or forced by option patch_generic)
-    const unsigned grid = ceil_div((long)a.n * a.g.npatch, 32);
-    if (a.nop == 2)
-      k_patchg<2><<<grid, 256, 0, s>>>(a);
+// ---- launch
+void launch_upsample(const UpArgs &a, hipStream_t s) {
+  if (a.nop == 2 && a.log2s >= 1 && a.log2s <= 9 && (a.W0 % 4) == 0 && ((uintptr_t)a.out % 16) == 0) {
+    if (a.form == 2)
+      k_upsample_h<8><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, 8), a.n), 256, 0, s>>>(a);
+    else if (a.form == 1)
+      k_upsample_h<4><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, 4), a.n), 256, 0, s>>>(a);
     else
-      k_patchg<1><<<grid, 256, 0, s>>>(a);
-    return;
-  }
-  if (J <= 1)
-    patch_jm<1>(a, s);
-  else if (J <= 3)
-    patch_jm<3>(a, s);
+      k_upsample_rows<<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, kUpRows), a.n), 256, 0, s>>>(a);
+  } else if (a.nop == 1 && a.log2s >= 1 && a.log2s <= 9 && (a.W0 % 4) == 0 && ((uintptr_t)a.out % 16) == 0)
+    k_upsample_rows1<<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, kUpRows), a.n), 256, 0, s>>>(a);
   else
-    patch_jm<7>(a, s);
+    k_upsample<<<dim3(ceil_div(a.W0, 256), a.H0, a.n), 256, 0, s>>>(a);
 }
-void launch_aggregate(const AggArgs &a, hipStream_t s) {
-  k_aggregate<<<dim3(ceil_div(a.g.w, 64), ceil_div(a.g.h, 16), a.n), 256, 0, s>>>(a);
-}
-void launch_tv_prep(const TvArgs &a, hipStream_t s) {
-  if (a.noc == 1)
-    k_tv_prep<5, 32><<<dim3(ceil_div(a.w, kTileW), ceil_div(a.h, 32), a.n), 256, 0, s>>>(a);
-  else
-    k_tv_prep<9, 16><<<dim3(ceil_div(a.w, kTileW), ceil_div(a.h, 16), a.n), 256, 0, s>>>(a);
-}
-// prep + derivatives in one launch: intensity images (option prepd), colour images too with prepd = 2 (default)
+
 // Code-object warm-up: HIP loads a translation unit's code object on the first launch of any of its kernels, which
 // in a one-pair-per-process CLI would land inside the reference's first timer (TIME (Pyramide+Gradients),
 // run_dense.cpp:315-353).  ofdis_context_create launches this empty kernel of each unit instead.
@@ -5094,256 +5300,6 @@ __global__ void k_warm_kernels(int *p) {
 }
 void warm_kernels_module(hipStream_t s) { k_warm_kernels<<<1, 64, 0, s>>>(nullptr); }
 
-bool tv_prepd_ok(const TvArgs &a) { return a.prepd && (a.noc == 1 || a.prepd == 2); }
-void launch_tv_prepd(const TvArgs &a, hipStream_t s) {
-  const dim3 grid(ceil_div(a.w, kPdW), ceil_div(a.h, kPdH), a.n);
-  if (a.smsys_deriv && !a.lat && a.prepd_df) {  // tv_deriv_fused(): Ix, Iy, Iz only
-    // tall levels (the march's, h >= 256) on 64 x 32 tiles, 512 threads: halo 1.33x -> 1.2x the core, the same
-    // occupancy; config E's prep 3.06 -> 2.61 ms per step, C's 3.16 -> 3.04 (profiles/r06/s29); short levels keep
-    // 16 rows (B's 68-row levels would compute 96)
-    if (a.h >= 256) {
-      const dim3 g32(ceil_div(a.w, kPdW), ceil_div(a.h, 32), a.n);
-      if (a.noc == 1) k_tv_prepd_df<1, 32><<<g32, 512, 0, s>>>(a);
-      else k_tv_prepd_df<3, 32><<<g32, 512, 0, s>>>(a);
-    } else if (a.noc == 1) k_tv_prepd_df<1><<<grid, 256, 0, s>>>(a);
-    else k_tv_prepd_df<3><<<grid, 256, 0, s>>>(a);
-    return;
-  }
-  if (a.noc == 1) k_tv_prepd<1><<<grid, 256, 0, s>>>(a);
-  else k_tv_prepd_c3<<<grid, 256, 0, s>>>(a);
-}
-void launch_tv_deriv1(const TvArgs &a, hipStream_t s) {
-  k_tv_deriv1<<<dim3(ceil_div(a.sp, 256), a.n * a.noc), 256, 0, s>>>(a);
-}
-void launch_tv_deriv2(const TvArgs &a, hipStream_t s) {
-  k_tv_deriv2<<<dim3(ceil_div(a.sp, 256), a.n * a.noc), 256, 0, s>>>(a);
-}
-void launch_tv_smooth(const TvArgs &a, hipStream_t s) {
-  if (a.nop == 2)
-    k_tv_smooth<2><<<dim3(ceil_div(a.sp, 256), a.n), 256, 0, s>>>(a);
-  else
-    k_tv_smooth<1><<<dim3(ceil_div(a.sp, 256), a.n), 256, 0, s>>>(a);
-}
-// The fused form stages RB + 4 rows for RB computed ones: below RB = 4 (h > 256) the halo re-reads cost
-// more than the smoothness round trip saves (config E, h = 544 / 272: 518 vs 299 us per launch).
-// Tall levels take the 2-D tiled form (k_tv_smsys2d) unless a.smsys2d = 0 (A/B: two launches there).
-// The register march for a level: tall levels (no row block fits).  (Colour levels of 135 rows on the march too: prep
-// -0.50 ms, system +0.62 ms per config-C step, r06_s13: not taken.)
-static bool smsys_use_march(const TvArgs &a) {
-  return a.smsys_march && !(smsys_rb(a.h) >= 4 && smsys_lds(a.h) <= 64 * 1024);
-}
-bool tv_smsys_ok(const TvArgs &a) {
-  return a.smsys && ((smsys_rb(a.h) >= 4 && smsys_lds(a.h) <= 64 * 1024) || a.smsys2d || a.smsys_march);
-}
-// The derivative filters move into the system kernel where the level runs k_tv_prepd (intensity images) and the
-// row-block k_tv_smsys or the march k_tv_smsys_m (round 4); the 2-D tiles and the two-launch form read all eight planes.
-// Not where the 40 KB LDS cap of the DF form leaves fewer than 3 rows per block (levels of ~180-256 rows): a
-// block would then stage 5-6 rows of seven planes for 1-2 computed ones, 3-5x redundant staging.
-bool tv_deriv_fused(const TvArgs &a) {
-  if (!(a.smsys_deriv && tv_prepd_ok(a) && a.smsys)) return false;
-  if (smsys_use_march(a)) return true;  // the march filters them too
-  if (!(smsys_rb(a.h) >= 4 && smsys_lds(a.h) <= 64 * 1024)) return false;
-  if (a.noc != 1) return false;  // colour images: the march only (a row block would stage 9 derivative planes)
-  int rb = smsys_rb_n(a.h, smsys_rows(a.w, a.h, a.wrap), a.n, a.smsys_small);
-  while (rb > 1 && smsys_lds_df(a.h, rb, true) > kSmsysDfCap) --rb;
-  return rb >= 3;
-}
-void launch_tv_smsys(const TvArgs &a, hipStream_t s) {
-  if (smsys_use_march(a)) {
-    const long waves = (long)a.n * march_segments(smsys_rows(a.w, a.h, a.wrap)) * march_strips(a.h);
-    const unsigned grid = ceil_div(waves, 4);
-    if (a.smsys_deriv) {  // tv_deriv_fused(): k_tv_prepd wrote Ix, Iy, Iz only
-      if (a.noc == 1) {
-        if (a.nop == 2) k_tv_smsys_m<2, 1, true><<<grid, 256, 0, s>>>(a);
-        else k_tv_smsys_m<1, 1, true><<<grid, 256, 0, s>>>(a);
-      } else {
-        if (a.nop == 2) k_tv_smsys_m<2, 3, true><<<grid, 256, 0, s>>>(a);
-        else k_tv_smsys_m<1, 3, true><<<grid, 256, 0, s>>>(a);
-      }
-    } else if (a.nop == 2) {
-      if (a.noc == 1) k_tv_smsys_m<2, 1><<<grid, 256, 0, s>>>(a);
-      else k_tv_smsys_m<2, 3><<<grid, 256, 0, s>>>(a);
-    } else {
-      if (a.noc == 1) k_tv_smsys_m<1, 1><<<grid, 256, 0, s>>>(a);
-      else k_tv_smsys_m<1, 3><<<grid, 256, 0, s>>>(a);
-    }
-    return;
-  }
-  if (!(smsys_rb(a.h) >= 4 && smsys_lds(a.h) <= 64 * 1024)) {
-    const dim3 g2(a.n, ceil_div(smsys_rows(a.w, a.h, a.wrap), kS2R), ceil_div(a.h, kS2C));
-    if (a.nop == 2) {
-      if (a.noc == 1) k_tv_smsys2d<2, 1><<<g2, 256, 0, s>>>(a);
-      else k_tv_smsys2d<2, 3><<<g2, 256, 0, s>>>(a);
-    } else {
-      if (a.noc == 1) k_tv_smsys2d<1, 1><<<g2, 256, 0, s>>>(a);
-      else k_tv_smsys2d<1, 3><<<g2, 256, 0, s>>>(a);
-    }
-    return;
-  }
-  const int rows = smsys_rows(a.w, a.h, a.wrap);
-  int rb = smsys_rb_n(a.h, rows, a.n, a.smsys_small);
-  if (a.smsys_deriv) {  // the kernel's rule: four workgroups per CU
-    while (rb > 1 && smsys_lds_df(a.h, rb, true) > kSmsysDfCap) --rb;
-    const dim3 grid(a.n, ceil_div(rows, rb));
-    const size_t lds = smsys_lds_df(a.h, rb, true);
-    if (a.nop == 2) k_tv_smsys<2, 1, true><<<grid, 256, lds, s>>>(a);
-    else k_tv_smsys<1, 1, true><<<grid, 256, lds, s>>>(a);
-    return;
-  }
-  const dim3 grid(a.n, ceil_div(rows, rb));
-  const size_t lds = smsys_lds_rb(a.h, rb);
-  if (a.nop == 2) {
-    if (a.noc == 1)
-      k_tv_smsys<2, 1><<<grid, 256, lds, s>>>(a);
-    else
-      k_tv_smsys<2, 3><<<grid, 256, lds, s>>>(a);
-  } else {
-    if (a.noc == 1)
-      k_tv_smsys<1, 1><<<grid, 256, lds, s>>>(a);
-    else
-      k_tv_smsys<1, 3><<<grid, 256, lds, s>>>(a);
-  }
-}
-void launch_tv_system(const TvArgs &a, hipStream_t s) {
-  const dim3 grid(ceil_div(a.sp, 256), a.n);
-  if (a.nop == 2) {
-    if (a.noc == 1)
-      k_tv_system<2, 1><<<grid, 256, 0, s>>>(a);
-    else
-      k_tv_system<2, 3><<<grid, 256, 0, s>>>(a);
-  } else {
-    if (a.noc == 1)
-      k_tv_system<1, 1><<<grid, 256, 0, s>>>(a);
-    else
-      k_tv_system<1, 3><<<grid, 256, 0, s>>>(a);
-  }
-}
-template <int S>
-static void sor_pipe(const TvArgs &a, hipStream_t s) {
-  const int threads = ((a.h + 63) / 64) * 64;
-  if (threads <= 256) {
-    if (a.nop == 2)
-      k_tv_sor_pipe<S, 0, 256><<<a.n, threads, 0, s>>>(a);
-    else
-      k_tv_sor_pipe<S, 2, 256><<<a.n, threads, 0, s>>>(a);
-  } else if (threads <= 512) {
-    if (a.nop == 2)
-      k_tv_sor_pipe<S, 0, 512><<<a.n, threads, 0, s>>>(a);
-    else
-      k_tv_sor_pipe<S, 2, 512><<<a.n, threads, 0, s>>>(a);
-  } else {
-    if (a.nop == 2)
-      k_tv_sor_pipe<S, 0, 1024><<<a.n, threads, 0, s>>>(a);
-    else
-      k_tv_sor_pipe<S, 2, 1024><<<a.n, threads, 0, s>>>(a);
-  }
-}
-// Sweep-per-wave SOR (k_tv_sor_lanes): 64 * ceil(h / (64 R)) * S threads, one workgroup per frame.  With S <= 3
-// sweep 0 hands the coefficients to the later sweeps through an LDS ring (option sor_cring, default on) while
-// it fits the LDS.
-template <int S, int MAXT, int R>
-static void sor_lanes(const TvArgs &a, hipStream_t s) {
-  const int G = (a.h + 64 * R - 1) / (64 * R);
-  constexpr int crn = sor_crn(S, MAXT, R);
-  const int cw = a.nop == 2 ? 2 : 1;
-  const bool cring = crn > 0 && a.sor_cring && sor_lanes_lds(S, a.h, crn, cw, R) <= kSorLds;
-  const size_t lds = sor_lanes_lds(S, a.h, cring ? crn : 0, cw, R);
-  const int th = 64 * G * S;
-  if constexpr (S == 3 && R == 1) {
-    if (cring && a.sor_cring >= 2) {  // the ring sized to the level's G row groups
-      const size_t ldsg = sor_lanes_lds(S, a.h, 64 * G + 2, cw, R);
-      // the clamped in-frame load form in throughput launches -- more frames than CUs -- and the lane-constant slots in
-      // latency launches, where the per-step v_med3 would sit on the wavefront's critical path (sor_cring 3: everywhere,
-      // parity).  Measured (profiles/r06/s5, s21): B's tv_sor 4.16 -> 4.00 ms per step and its counted bytes 1.33x ->
-      // 1.23x the compulsory ones, A's 1.82x -> 1.27x; the single pair 0.84 -> 0.91 ms with it everywhere.
-      const bool sel = a.sor_cring >= 3 || (long)a.n > device_cus();
-      auto go = [&](auto gc) {
-        constexpr int CG = decltype(gc)::value;
-        if (a.nop == 2) {
-          if (sel) k_tv_sor_lanes<S, 0, 3, MAXT, true, R, CG, true><<<a.n, th, ldsg, s>>>(a);
-          else k_tv_sor_lanes<S, 0, 3, MAXT, true, R, CG, false><<<a.n, th, ldsg, s>>>(a);
-        } else {
-          if (sel) k_tv_sor_lanes<S, 2, 3, MAXT, true, R, CG, true><<<a.n, th, ldsg, s>>>(a);
-          else k_tv_sor_lanes<S, 2, 3, MAXT, true, R, CG, false><<<a.n, th, ldsg, s>>>(a);
-        }
-      };
-      if constexpr (MAXT == 512) {
-        if (G == 1) return go(std::integral_constant<int, 1>{});
-        if (G == 2) return go(std::integral_constant<int, 2>{});
-      } else {
-        if (G == 3) return go(std::integral_constant<int, 3>{});
-        if (G == 4) return go(std::integral_constant<int, 4>{});
-        if (G == 5) return go(std::integral_constant<int, 5>{});
-      }
-    }
-  }
-  // every other form: the same rule for the clamped load form
-  const bool sel = a.sor_cring >= 3 || (long)a.n > device_cus();
-  auto go2 = [&](auto cr, auto sl) {
-    constexpr bool CR = decltype(cr)::value, SL = decltype(sl)::value;
-    if (a.nop == 2) k_tv_sor_lanes<S, 0, 3, MAXT, CR, R, 0, SL><<<a.n, th, lds, s>>>(a);
-    else k_tv_sor_lanes<S, 2, 3, MAXT, CR, R, 0, SL><<<a.n, th, lds, s>>>(a);
-  };
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  if (cring) {
-    if (sel) go2(T_{}, T_{});
-    else go2(T_{}, F_{});
-  } else {
-    if (sel) go2(F_{}, T_{});
-    else go2(F_{}, F_{});
-  }
-}
-template <int S>
-static void sor_lanes_s(const TvArgs &a, hipStream_t s) {
-  if (64 * S * ((a.h + 63) / 64) <= 512)
-    sor_lanes<S, 512, 1>(a, s);
-  else if (64 * S * ((a.h + 63) / 64) <= 1024)
-    sor_lanes<S, 1024, 1>(a, s);
-  else
-    sor_lanes<S, 1024, 2>(a, s);
-}
-// Exact-order SOR dispatch: the sweep-per-wave form while its S * ceil(h / 64) waves fit one workgroup,
-// the register pipeline (one wave per row group runs all sweeps) for taller levels, the generic
-// global-memory wavefront for the point SOR of the OpenMP build and degenerate sizes.
-void launch_tv_sor(const TvArgs &a, hipStream_t s) {
-  if (a.solverit < 1) return;
-  const bool tiny = a.nop == 2 && (a.w < 2 || a.h < 2 || a.sor_point);  // point SOR (solver.c:34-78)
-  if (a.sor_redblack && !tiny) {  // opt-in red-black order (not the reference's bits), levels over kLvPix pixels
-    const dim3 grid(ceil_div(a.w * a.h, 256), a.n);
-    for (int it = 0; it < 2 * a.solverit; ++it) {
-      if (a.nop == 2) k_tv_sor_rb<0><<<grid, 256, 0, s>>>(a, it & 1);
-      else k_tv_sor_rb<2><<<grid, 256, 0, s>>>(a, it & 1);
-    }
-    return;
-  }
-  const int G = (a.h + 63) / 64, G2 = (a.h + 127) / 128;  // row groups at one / two rows per lane
-  const bool lanes_fit = G * a.solverit <= 16 || (a.solverit <= 3 && G2 * a.solverit <= 16 && a.sor_rows2);
-  if (!tiny && !a.sor_generic && a.sor_variant != 1 && a.solverit >= 2 && a.solverit <= 4 && lanes_fit) {
-    switch (a.solverit) {
-      case 2: sor_lanes_s<2>(a, s); return;
-      case 3: sor_lanes_s<3>(a, s); return;
-      case 4: sor_lanes_s<4>(a, s); return;
-    }
-  }
-  if (!tiny && a.h <= 1024 && a.solverit <= 4 && !a.sor_generic) {
-    switch (a.solverit) {
-      case 1: sor_pipe<1>(a, s); return;
-      case 2: sor_pipe<2>(a, s); return;
-      case 3: sor_pipe<3>(a, s); return;
-      case 4: sor_pipe<4>(a, s); return;
-    }
-  }
-  if (a.nop == 1)
-    k_tv_sor<2><<<a.n, 256, 0, s>>>(a);
-  else if (tiny)
-    k_tv_sor<1><<<a.n, 256, 0, s>>>(a);
-  else
-    k_tv_sor<0><<<a.n, 256, 0, s>>>(a);
-}
-void launch_tv_final(const TvArgs &a, hipStream_t s) {
-  k_tv_final<32><<<dim3(ceil_div(a.w, kTileW), ceil_div(a.h, 32), a.n), 256, 0, s>>>(a);
-}
 // OpenCV resizeAreaFast for the initial flow (oracle: ofo_init_flow_area): one thread per output value,
 // the k x k block in row-major order, sum += ((a + b) + c) + d four at a time, then x 1/k^2.  The chain is
 // serial by definition (exact order); it runs once per batch on the coarsest grid (a few hundred values
@@ -5374,20 +5330,6 @@ __global__ __launch_bounds__(256) void k_init_area(InitArgs a) {
 void launch_init_area(const InitArgs &a, hipStream_t s) {
   const long total = (long)a.n * a.wo * a.ho * a.nop;
   k_init_area<<<dim3(ceil_div(total, 256)), 256, 0, s>>>(a);
-}
-
-void launch_upsample(const UpArgs &a, hipStream_t s) {
-  if (a.nop == 2 && a.log2s >= 1 && a.log2s <= 9 && (a.W0 % 4) == 0 && ((uintptr_t)a.out % 16) == 0) {
-    if (a.form == 2)
-      k_upsample_h<8><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, 8), a.n), 256, 0, s>>>(a);
-    else if (a.form == 1)
-      k_upsample_h<4><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, 4), a.n), 256, 0, s>>>(a);
-    else
-      k_upsample_rows<<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, kUpRows), a.n), 256, 0, s>>>(a);
-  } else if (a.nop == 1 && a.log2s >= 1 && a.log2s <= 9 && (a.W0 % 4) == 0 && ((uintptr_t)a.out % 16) == 0)
-    k_upsample_rows1<<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, kUpRows), a.n), 256, 0, s>>>(a);
-  else
-    k_upsample<<<dim3(ceil_div(a.W0, 256), a.H0, a.n), 256, 0, s>>>(a);
 }
 
 }  // namespace ofdis

@@ -98,7 +98,8 @@ struct ofdis_context {
   int opt_agg_stage = 1;       // k_aggregate: patch displacements of the tile staged in LDS (0: gathered from p_iter)
   int opt_pad_grad_v = 1;      // colour pyramid pad + gradients: one thread per value (0: per pixel, channels inside)
   int opt_pyr_rgb = 1;         // colour pyramid base by dword loads and masked v_sad_u8 (0: the byte loop)
-  int opt_prepd_df = 1;        // smsys_deriv levels: k_tv_prepd_df (Ix, Iy, Iz from a 2-pixel halo, channels in one pass)
+  int opt_prepd_df = 1;        // smsys_deriv levels: k_tv_prepd_df (Ix, Iy, Iz from a 2-pixel halo, channels in one pass);
+                               // 0: k_tv_prepd (intensity), k_tv_prepd_c3 (colour: all eight derivative planes)
   int opt_smsys_deriv = 1;     // fused smoothness + system (gray; colour: the march): second derivatives filtered from Ix, Iy, Iz
   int call_frames = 1;         // pairs of the current call (auto options)
   int call_lanes = 1;          // streams the current call's chunks run on (auto options)

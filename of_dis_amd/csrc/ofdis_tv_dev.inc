@@ -1,5 +1,6 @@
 // ofdis_tv_dev.inc -- device helpers of the variational refinement (included INSIDE namespace ofdis
-// { namespace { ... } } of the kernel translation units: every definition is internal to its unit).  Same expressions as the reference (FDF1.0.1), cited per function.
+// { namespace { ... } } of the kernel translation units, ofdis_kernels.hip and ofdis_tvrb.hip: every definition is
+// internal to its unit).  Same expressions as the reference (FDF1.0.1), cited per function.
 #pragma once
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -36,8 +37,9 @@ __device__ __forceinline__ float ldu(const float *base, unsigned idx) {
 
 // compute_data (opticalflow_aux.c:408-594) of an intensity image, one pixel, in its two halves: the colour
 // (brightness constancy) term, :457-509, and the gradient constancy term, :510-571 with the final x 3 (:572-577).
-// A11 .. B2 enter the colour half as 0 (the reference's zero-initialised a11 .. b2).  The fused system + SOR
-// launch (ofdis_tvsysor.hip) runs them in different barrier intervals; data_of runs them back to back.
+// A11 .. B2 enter the colour half as 0 (the reference's zero-initialised a11 .. b2).  data_of runs the halves back to
+// back for every caller: through sys_compute the system kernels (ofdis_kernels.hip) and the latency mode's level
+// launch k_tv_level_rb (ofdis_tvrb.hip).
 __device__ __forceinline__ void data_of_gray_colour(float u, float v, float m, float Ix, float Iy, float Iz, float hdo3,
                                                     float &A11, float &A12, float &A22, float &B1, float &B2) {
   A11 = 0.0f; A12 = 0.0f; A22 = 0.0f; B1 = 0.0f; B2 = 0.0f;
@@ -331,8 +333,8 @@ __device__ __forceinline__ void sys_compute(const TvArgs &a, int x, int y, const
 }
 
 // The rest of the system of one pixel once the data term (A11 .. B2) is known: sub_laplacian on wx / wy, then
-// (OF) the 2x2 inverse / (DE) the point-SOR diagonal.  Separate so that the fused system + SOR launch can run it
-// in its own barrier interval; sys_compute runs it right after the data term.
+// (OF) the 2x2 inverse / (DE) the point-SOR diagonal.  sys_compute runs it right after the data term, in the system
+// kernels and in k_tv_level_rb (ofdis_tvrb.hip) alike.
 template <int NOP>
 __device__ __forceinline__ void sys_finish(const TvArgs &a, int x, int y, const float (&S5)[5], const float (&X5)[5],
                                            const float (&Y5)[5], float A11, float A12, float A22, float B1, float B2,

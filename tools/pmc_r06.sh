@@ -3,7 +3,7 @@
 # do not fit one pass on gfx950), counters only, each pass its own run under its own time limit, at the pairs per
 # launch the bench config runs (bench.py config_tag).  Reduced by tools/pmc_traffic.py into gpurun_out/<out>/traffic.json
 # (copied to profiles/traffic.json afterwards, every entry carrying its source).
-#   tools/pmc_r05.sh <out> <config>:<batch>:<pairs-per-launch>[:<extra bench args, + for spaces>] ...
+#   tools/pmc_r06.sh <out> <config>:<batch>:<pairs-per-launch>[:<extra bench args, + for spaces>] ...
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${1:?out}; shift
