@@ -142,6 +142,56 @@ int ofdis_run_batch_u8_init_host(ofdis_context *ctx, const uint8_t *img_a, const
                                  const float *init_flow, int n, int width, int height, const ofdis_params *p,
                                  float *flow_out);
 
+/* ------------------------------------------------------------------ both directions and occlusion masks
+ *
+ * Not in the reference, which gives one field per pair and nothing that says where it can be trusted.  The
+ * forward-backward consistency check (Sundaram, Brox, Keutzer, ECCV 2010) follows each pixel along its flow,
+ * reads the opposite field there and asks whether the two cancel.
+ *
+ * ofdis_fb_check: the check on two full-resolution optical-flow fields (device pointers).
+ * flow_fw, flow_bw: float [n][height][width][2]; occ_*: u8 [n][height][width]; err_*: float [n][height][width].
+ * Any of the four outputs may be NULL (all NULL: OFDIS_OK, nothing enqueued).  Mask codes: 0 consistent,
+ * 1 inconsistent (occluded or wrong), 2 the flow leaves the frame (err = +inf there).
+ *
+ * Definition, direction fw (bw: F and B exchanged), pixel (x, y), F = flow_fw, B = flow_bw of the same frame; all
+ * arithmetic float32 in this order, every operation rounded on its own (no fused multiply-add):
+ *   u = F[y][x][0];  v = F[y][x][1];  px = (float)x + u;  py = (float)y + v
+ *   inside = px >= 0 && px <= (float)(W-1) && py >= 0 && py <= (float)(H-1)           (false for NaN)
+ *   if !inside: occ = 2, err = +inf
+ *   x0 = (int)floorf(px); y0 = (int)floorf(py); x1 = min(x0+1, W-1); y1 = min(y0+1, H-1)
+ *   ax = px - (float)x0;  ay = py - (float)y0
+ *   for k in 0, 1:  top = B[y0][x0][k] + ax*(B[y0][x1][k] - B[y0][x0][k])
+ *                   bot = B[y1][x0][k] + ax*(B[y1][x1][k] - B[y1][x0][k])
+ *                   b_k = top + ay*(bot - top)
+ *   du = u + b_0;  dv = v + b_1;  err = du*du + dv*dv
+ *   mag = (u*u + v*v) + (b_0*b_0 + b_1*b_1);  thr = alpha*mag + beta
+ *   occ = (err <= thr) ? 0 : 1                                                        (NaN err -> 1)
+ *   a NaN err is stored as the canonical quiet NaN 0x7fc00000 (IEEE 754 leaves a generated NaN's sign and payload open)
+ * Suggested thresholds: alpha = 0.01, beta = 0.5 (the paper's).  alpha or beta negative or not finite, NULL flows,
+ * n < 1, non-positive sizes or width * height >= 2^31 return OFDIS_ERR_INVALID_ARGUMENT before anything is
+ * enqueued.  Stream and ordering rules are those of ofdis_run_batch_u8.
+ */
+int ofdis_fb_check(ofdis_context *ctx, const float *flow_fw, const float *flow_bw, int n, int width, int height,
+                   float alpha, float beta, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw,
+                   void *stream);
+
+/* Both directions of n pairs from one pyramid, plus the check: flow_fw == ofdis_run_batch_u8(a, b) and
+ * flow_bw == ofdis_run_batch_u8(b, a), bit for bit, at less than the cost of the two calls -- the pyramid is built
+ * once, and with usefbcon = 1 the backward patch grid and refinement that a plain call already runs above the
+ * finest scale (and drops there, oflow.cpp:266,286) are run at the finest scale too instead of a second time from
+ * scratch.  flow_bw and the occ / err outputs may be NULL (masks without flow_bw: the backward field stays in the
+ * workspace; all five NULL: the plain call).  Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED (the
+ * depth path's right-camera clamp has no pinned counterpart), and so does a call while a stage capture is set.
+ * No initial flow.  verbosity is ignored (no TIME lines).  Argument errors as for ofdis_run_batch_u8 and
+ * ofdis_fb_check; stream, ordering, chunking and workspace rules are those of ofdis_run_batch_u8. */
+int ofdis_run_bidir_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                       const ofdis_params *p, float alpha, float beta, float *flow_fw, float *flow_bw,
+                       uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_bidir_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
+                            int height, const ofdis_params *p, float alpha, float beta, float *flow_fw,
+                            float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -248,7 +298,8 @@ int ofdis_max_frames_per_launch(const ofdis_params *p, int width, int height, in
 int ofdis_context_enable_kernel_timing(ofdis_context *ctx, int enable);
 /* Accumulated device time (ms) and launch count for kernel `name` since timing was enabled. */
 int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *total_ms, long *launches);
-/* Comma-separated list of kernel names known to the timer. */
+/* Comma-separated list of kernel names known to the timer.  The forward-backward check is timed as "fb_check"
+ * when it writes masks only and as "fb_check_err" when it also writes an error map. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload. */

@@ -157,6 +157,16 @@ struct InitArgs {
   float sc, scale;    // 2^-(sc_f+1), 1 / k^2
 };
 
+// Forward-backward consistency of two full-resolution flow fields (include/ofdis.h: ofdis_fb_check).
+struct FbArgs {
+  const float *fw, *bw;      // [n][H][W][2]
+  uint8_t *occ_fw, *occ_bw;  // [n][H][W] mask codes 0 / 1 / 2, or NULL
+  float *err_fw, *err_bw;    // [n][H][W] squared round-trip error, or NULL
+  int n, W, H;               // W * H < 2^31
+  float alpha, beta;
+};
+
+void launch_fb_check(const FbArgs &a, hipStream_t s);
 void launch_init_area(const InitArgs &a, hipStream_t s);
 void warm_kernels_module(hipStream_t s);  // one empty launch per kernel translation unit: loads its code object
 void warm_tvrb_module(hipStream_t s);

@@ -29,6 +29,7 @@
 //                k_tv_sor_lanes<S, MODE, NB, MAXT, CRING, R, CG, SEL>  exact order, one wave per sweep and row group
 //                k_tv_final<TH>      refine_variational.cpp:209-227,305-323
 //   output       k_upsample, k_upsample_rows, k_upsample_h<R>, k_upsample_rows1  run_dense.cpp:407-415
+//   fb check     k_fb_check<OCC, ERR, PX>  forward-backward consistency masks of two flow fields (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -5290,6 +5291,112 @@ void launch_upsample(const UpArgs &a, hipStream_t s) {
     k_upsample_rows1<<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, kUpRows), a.n), 256, 0, s>>>(a);
   else
     k_upsample<<<dim3(ceil_div(a.W0, 256), a.H0, a.n), 256, 0, s>>>(a);
+}
+
+// ------------------------------------------------------------------------------ forward-backward check
+// The consistency check of include/ofdis.h (ofdis_fb_check), both directions in one launch: blockIdx.z = 2 * frame +
+// direction, so the two directions of a frame, which read the same two fields, run next to each other.  Direction 0
+// walks the forward field F and gathers the backward field B at x + F(x); direction 1 the other way round.  The
+// definition fixes every operation and its order (float32, no contraction), so the masks and errors are a pure
+// function of the two fields.
+namespace {
+
+typedef float float2_u __attribute__((ext_vector_type(2), aligned(4)));
+
+// One pixel: (u, v) = its own flow, B = the other field of the same frame.  Returns the mask code, err by reference.
+__device__ __forceinline__ unsigned fb_pixel(const float *__restrict__ B, int W, int H, int x, int y, float u, float v,
+                                             float alpha, float beta, float &err) {
+  const float px = (float)x + u, py = (float)y + v;
+  const bool inside = px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);  // false for NaN
+  // no branch around the gather: a pixel that leaves the frame reads the taps of (0, 0) and drops the result, so the
+  // sixteen tap loads of a thread's four pixels are all in flight together
+  const float pxs = inside ? px : 0.f, pys = inside ? py : 0.f;
+  const int x0 = (int)floorf(pxs), y0 = (int)floorf(pys);  // in [0, W - 1] x [0, H - 1]
+  const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+  const float ax = pxs - (float)x0, ay = pys - (float)y0;
+  const long r0 = (long)y0 * W, r1 = (long)y1 * W;
+  const float2_u b00 = *reinterpret_cast<const float2_u *>(B + 2 * (r0 + x0));
+  const float2_u b01 = *reinterpret_cast<const float2_u *>(B + 2 * (r0 + x1));
+  const float2_u b10 = *reinterpret_cast<const float2_u *>(B + 2 * (r1 + x0));
+  const float2_u b11 = *reinterpret_cast<const float2_u *>(B + 2 * (r1 + x1));
+  const float top0 = b00.x + ax * (b01.x - b00.x), bot0 = b10.x + ax * (b11.x - b10.x);
+  const float top1 = b00.y + ax * (b01.y - b00.y), bot1 = b10.y + ax * (b11.y - b10.y);
+  const float bu = top0 + ay * (bot0 - top0), bv = top1 + ay * (bot1 - top1);
+  const float du = u + bu, dv = v + bv;
+  const float e = du * du + dv * dv;
+  const float mag = (u * u + v * v) + (bu * bu + bv * bv);
+  const float thr = alpha * mag + beta;
+  // a NaN error is stored as the canonical quiet NaN: the sign and payload an operation gives a NaN differ by platform
+  err = inside ? (e != e ? __builtin_nanf("") : e) : __builtin_inff();
+  return inside ? (e <= thr ? 0u : 1u) : 2u;  // NaN err -> 1
+}
+
+// PX = 4: four consecutive pixels of a row per thread -- its own flow as two 16-byte loads, the four mask bytes as
+// one dword, the errors as one 16-byte store (W % 4 == 0 and aligned pointers: launch_fb_check).  PX = 1: any width
+// and alignment.  OCC / ERR: some direction writes masks / errors; a direction's own NULL output is skipped.
+template <bool OCC, bool ERR, int PX>
+__global__ __launch_bounds__(256) void k_fb_check(FbArgs a) {
+  const int dir = blockIdx.z & 1, f = blockIdx.z >> 1;
+  uint8_t *occ = OCC ? (dir ? a.occ_bw : a.occ_fw) : nullptr;
+  float *errp = ERR ? (dir ? a.err_bw : a.err_fw) : nullptr;
+  if (!occ && !errp) return;
+  const unsigned wq = (unsigned)a.W / PX;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= wq * (unsigned)a.H) return;
+  const int y = (int)(q / wq), x = (int)(q - (unsigned)y * wq) * PX;
+  const long fo = (long)f * a.H * a.W, o = fo + (long)y * a.W + x;
+  const float *F = (dir ? a.bw : a.fw) + 2 * o;
+  const float *B = (dir ? a.fw : a.bw) + 2 * fo;
+  float uv[2 * PX], e[PX];
+  if constexpr (PX == 4) {
+    const float4_v lo = *reinterpret_cast<const float4_v *>(F), hi = *reinterpret_cast<const float4_v *>(F + 4);
+    uv[0] = lo.x, uv[1] = lo.y, uv[2] = lo.z, uv[3] = lo.w;
+    uv[4] = hi.x, uv[5] = hi.y, uv[6] = hi.z, uv[7] = hi.w;
+  } else {
+    uv[0] = F[0], uv[1] = F[1];
+  }
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < PX; ++i)
+    m |= fb_pixel(B, a.W, a.H, x + i, y, uv[2 * i], uv[2 * i + 1], a.alpha, a.beta, e[i]) << (8 * i);
+  if constexpr (PX == 4) {
+    if (occ) *reinterpret_cast<unsigned *>(occ + o) = m;
+    if (errp) *reinterpret_cast<float4_v *>(errp + o) = float4_v{e[0], e[1], e[2], e[3]};
+  } else {
+    if (occ) occ[o] = (uint8_t)m;
+    if (errp) errp[o] = e[0];
+  }
+}
+
+}  // namespace
+// ---- launch
+void launch_fb_check(const FbArgs &a0, hipStream_t s) {
+  const bool occ = a0.occ_fw || a0.occ_bw, err = a0.err_fw || a0.err_bw;
+  if (!occ && !err) return;
+  const bool vec = a0.W % 4 == 0 && ((uintptr_t)a0.fw | (uintptr_t)a0.bw | (uintptr_t)a0.err_fw | (uintptr_t)a0.err_bw) % 16 == 0 &&
+                   ((uintptr_t)a0.occ_fw | (uintptr_t)a0.occ_bw) % 4 == 0;
+  const long frame = (long)a0.W * a0.H;
+  const int kSlice = 32767;  // 2 * frames <= 65535 (grid z)
+  for (int f0 = 0; f0 < a0.n; f0 += kSlice) {
+    FbArgs a = a0;
+    a.n = std::min(kSlice, a0.n - f0);
+    a.fw += 2 * f0 * frame;
+    a.bw += 2 * f0 * frame;
+    if (a.occ_fw) a.occ_fw += f0 * frame;
+    if (a.occ_bw) a.occ_bw += f0 * frame;
+    if (a.err_fw) a.err_fw += f0 * frame;
+    if (a.err_bw) a.err_bw += f0 * frame;
+    const dim3 grid(ceil_div(frame / (vec ? 4 : 1), 256), 1, 2 * a.n);
+    auto go = [&](auto O, auto E) {
+      if (vec)
+        k_fb_check<O != 0, E != 0, 4><<<grid, 256, 0, s>>>(a);
+      else
+        k_fb_check<O != 0, E != 0, 1><<<grid, 256, 0, s>>>(a);
+    };
+    if (occ && err) go(Int<1>{}, Int<1>{});
+    else if (occ) go(Int<1>{}, Int<0>{});
+    else go(Int<0>{}, Int<1>{});
+  }
 }
 
 // Code-object warm-up: HIP loads a translation unit's code object on the first launch of any of its kernels, which

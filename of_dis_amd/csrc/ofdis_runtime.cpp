@@ -26,7 +26,8 @@ using namespace ofdis;
 namespace {
 
 const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "patch",    "aggregate", "tv_prep",
-                                    "tv_deriv", "tv_system", "tv_sor",       "tv_final", "upsample",  "tv_level"};
+                                    "tv_deriv", "tv_system", "tv_sor",       "tv_final", "upsample",  "tv_level",
+                                    "fb_check", "fb_check_err"};
 
 struct Plan {
   int n = 0, W0 = 0, H0 = 0, Wp = 0, Hp = 0, padl = 0, padt = 0, padw = 0, padh = 0;
@@ -37,6 +38,8 @@ struct Plan {
   size_t off_init = 0;  // initial flow at the coarsest scale - 1, [n][Hp >> (sc_f+1)][Wp >> (sc_f+1)][nop]
   bool init = false;    // an initial flow is given: divisibility 2^(sc_f+1) (run_dense.cpp:302)
   bool fb = false;      // usefbcon: backward grid, flow and refinement
+  bool bidir = false;   // ofdis_run_bidir_u8: the backward grid, flow and refinement at every level, sc_l included
+  size_t off_up_bw = 0; // bidir without a caller's flow_bw: the full-resolution backward flow [n][H0][W0][2]
   bool gradmag = false; // SELECTCHANNEL 2: float level 0 (gradient magnitude) halved down to sc_l
   size_t off_gm = 0;    // its scratch: [2n][Hp][Wp] + [2n][Hp/2][Wp/2] (ping-pong)
   size_t total = 0;
@@ -74,6 +77,9 @@ struct ofdis_context {
   int opt_graph = 1;           // replay the whole batch as one HIP graph (captured once per shape / pointers)
   struct GraphKey {
     const void *a = nullptr, *b = nullptr, *out = nullptr, *ws = nullptr, *init = nullptr;
+    const void *flow_bw = nullptr, *occ_fw = nullptr, *occ_bw = nullptr, *err_fw = nullptr, *err_bw = nullptr;
+    float alpha = 0.f, beta = 0.f;  // the bidirectional call's extra outputs and thresholds
+    int bidir = 0;
     int n = 0, w = 0, h = 0;
     ofdis_params p{};
   } gkey;
@@ -234,7 +240,7 @@ int steps_of(const ofdis_params *p) {
   return st0 > 1 ? st0 : 1;
 }
 
-Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init = false) {
+Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init = false, bool bidir = false) {
   Plan P;
   P.n = n;
   P.Wp = Wp;
@@ -253,6 +259,8 @@ Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init 
   P.off_flow.resize(nsc);
   P.off_flow_bw.resize(nsc);
   P.fb = p->usefbcon != 0;
+  P.bidir = bidir;
+  const bool bw = P.fb || bidir;  // a backward grid and flow
   size_t off = 0;
   const int novals = p->noc * p->p_samp_s * p->p_samp_s;
   size_t max_np = 0, max_plane = 0;
@@ -271,7 +279,7 @@ Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init 
     P.off_flow[i] = off;
     off = align_up(off + sizeof(float) * (size_t)n * P.nop * g.w * g.h);
     P.off_flow_bw[i] = off;
-    if (P.fb) off = align_up(off + sizeof(float) * (size_t)n * P.nop * g.w * g.h);
+    if (bw) off = align_up(off + sizeof(float) * (size_t)n * P.nop * g.w * g.h);
     if ((size_t)g.npatch > max_np) max_np = g.npatch;
     if ((size_t)g.w * g.h > max_plane) max_plane = (size_t)g.w * g.h;
   }
@@ -281,9 +289,10 @@ Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init 
   const size_t aslots = (size_t)((p->p_samp_s - 1) / steps_of(p) + 1);
   off = align_up(off + sizeof(float) * (size_t)n * std::max(max_np * novals, aslots * aslots * max_plane));
   P.off_piter_bw = off;
-  if (P.fb) off = align_up(off + sizeof(float) * (size_t)n * max_np * P.nop);
-  P.off_pw_bw = off;
+  if (bw) off = align_up(off + sizeof(float) * (size_t)n * max_np * P.nop);
+  P.off_pw_bw = off;  // usefbcon: loss weights; bidir without it: the backward patch launch may write slot planes too
   if (P.fb) off = align_up(off + sizeof(float) * (size_t)n * max_np * novals);
+  else if (bidir) off = align_up(off + sizeof(float) * (size_t)n * std::max(max_np * novals, aslots * aslots * max_plane));
   P.off_tv = off;
   size_t max_sp = 0;  // skewed TV plane
   for (const LevelGeom &g : P.lv) max_sp = std::max(max_sp, (size_t)skew_plane(g.w, g.h));
@@ -437,7 +446,9 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
     // usefbcon: the backward grid -- template on image b, target image a, right camera (camlr = 1),
     // initialised from the coarser backward flow (oflow.cpp:158-169, 193-196, 209-211, 231-233)
     PatchArgs pb = pa;
-    if (P.fb) {
+    const bool bw = P.fb || P.bidir;
+    bool absw_bw = false;
+    if (bw) {
       pb.img_a = img + (size_t)n * fsp;
       pb.dx_a = dxp + (size_t)n * fsp;
       pb.dy_a = dyp + (size_t)n * fsp;
@@ -447,7 +458,7 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
       pb.p_iter = (float *)(ws + P.off_piter_bw);
       pb.pweight = (float *)(ws + P.off_pw_bw);
       pb.camlr = 1;
-      timed(c, 3, s, [&] { launch_patch(pb, s); });
+      timed(c, 3, s, [&] { absw_bw = launch_patch(pb, s); });
     }
 
     AggArgs ag{};
@@ -531,13 +542,15 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
     };
     if (times) HIP_OK(hipEventRecord(ev[3], s));
     timed(c, 4, s, [&] { launch_aggregate(ag, s); });
-    const bool bw_level = P.fb && sl > p->sc_l;  // the backward flow is not needed after the last scale
+    // the backward flow is not needed after the last scale -- unless the caller asked for it (bidir)
+    const bool bw_level = bw && (sl > p->sc_l || P.bidir);
     if (bw_level) {                               // patchgrid.cpp:213-397 with the roles swapped
       AggArgs ab = ag;
       ab.p_iter = pb.p_iter;
       ab.pweight = pb.pweight;
-      ab.cg_p_iter = pa.p_iter;
-      ab.cg_pweight = pa.pweight;
+      ab.cg_p_iter = P.fb ? pa.p_iter : nullptr;
+      ab.cg_pweight = P.fb ? pa.pweight : nullptr;
+      ab.absw = absw_bw;
       ab.flow = flow_bw;
       timed(c, 4, s, [&] { launch_aggregate(ab, s); });
     }
@@ -705,10 +718,13 @@ int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, con
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
-Plan batch_plan(const ofdis_params *p, int n, int width, int height, bool init = false) {
+// bidir: 0 plain, 1 both directions, 2 both directions and the full-resolution backward flow kept in the workspace
+Plan batch_plan(const ofdis_params *p, int n, int width, int height, bool init = false, int bidir = 0) {
   const int d = 1 << (p->sc_f + (init ? 1 : 0));  // run_dense.cpp:301-302
   const int padw = (width % d) ? d - width % d : 0, padh = (height % d) ? d - height % d : 0;
-  Plan P = make_plan(p, n, width + padw, height + padh, p->p_samp_s, init);
+  Plan P = make_plan(p, n, width + padw, height + padh, p->p_samp_s, init, bidir != 0);
+  P.off_up_bw = P.total;
+  if (bidir == 2) P.total = align_up(P.total + sizeof(float) * (size_t)n * width * height * P.nop);
   P.W0 = width;
   P.H0 = height;
   P.padw = padw;
@@ -775,9 +791,10 @@ void ofdis_context_destroy(ofdis_context *c) {
 namespace {
 
 // x 2^sc_l + INTER_LINEAR upsample + crop of the finest level's flow in workspace ws (run_dense.cpp:407-415).
-int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, float *flow_out, hipStream_t s) {
+int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, float *flow_out, hipStream_t s,
+                 bool backward = false) {
   UpArgs up{};
-  up.flow = (const float *)(ws + P.off_flow[0]);
+  up.flow = (const float *)(ws + (backward ? P.off_flow_bw[0] : P.off_flow[0]));
   up.out = flow_out;
   up.n = P.n;
   up.nop = P.nop;
@@ -816,15 +833,57 @@ int run_init(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, c
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
-// One chunk of frames through the whole pipeline on stream s with workspace ws.
+// The outputs of a bidirectional call beyond the forward flow (ofdis_run_bidir_u8); at() is a chunk's share.
+struct BidirOut {
+  float *flow_bw = nullptr;
+  uint8_t *occ_fw = nullptr, *occ_bw = nullptr;
+  float *err_fw = nullptr, *err_bw = nullptr;
+  float alpha = 0.f, beta = 0.f;
+  bool checks() const { return occ_fw || occ_bw || err_fw || err_bw; }
+  BidirOut at(size_t f0, size_t px) const {
+    BidirOut o = *this;
+    if (flow_bw) o.flow_bw += f0 * px * 2;
+    if (occ_fw) o.occ_fw += f0 * px;
+    if (occ_bw) o.occ_bw += f0 * px;
+    if (err_fw) o.err_fw += f0 * px;
+    if (err_bw) o.err_bw += f0 * px;
+    return o;
+  }
+};
+
+// The consistency check of n frames (timer "fb_check_err" when an error map is written, else "fb_check").
+int run_fb_check(ofdis_context *c, const float *fw, const float *bw, int n, int width, int height, const BidirOut &o,
+                 hipStream_t s) {
+  FbArgs fa{};
+  fa.fw = fw;
+  fa.bw = bw;
+  fa.occ_fw = o.occ_fw;
+  fa.occ_bw = o.occ_bw;
+  fa.err_fw = o.err_fw;
+  fa.err_bw = o.err_bw;
+  fa.n = n;
+  fa.W = width;
+  fa.H = height;
+  fa.alpha = o.alpha;
+  fa.beta = o.beta;
+  timed(c, o.err_fw || o.err_bw ? 13 : 12, s, [&] { launch_fb_check(fa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// One chunk of frames through the whole pipeline on stream s with workspace ws.  bd (P.bidir): the backward flow
+// of the same pyramid upsampled too -- into the workspace when the caller wants only the masks -- and the check.
 int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
-              const uint8_t *img_b, const float *init, float *flow_out, hipStream_t s) {
+              const uint8_t *img_b, const float *init, float *flow_out, const BidirOut *bd, hipStream_t s) {
   int rc = run_pyramid(c, ws, P, img_a, img_b, s);
   if (rc) return rc;
   if (init && (rc = run_init(c, ws, P, p, init, s))) return rc;
   rc = run_levels(c, ws, P, p, s, init ? (const float *)(ws + P.off_init) : nullptr, nullptr);
   if (rc) return rc;
-  return run_upsample(c, ws, P, p, flow_out, s);
+  rc = run_upsample(c, ws, P, p, flow_out, s);
+  if (rc || !bd) return rc;
+  float *flow_bw = bd->flow_bw ? bd->flow_bw : (float *)(ws + P.off_up_bw);
+  if ((rc = run_upsample(c, ws, P, p, flow_bw, s, true))) return rc;
+  return bd->checks() ? run_fb_check(c, flow_out, flow_bw, P.n, P.W0, P.H0, *bd, s) : OFDIS_OK;
 }
 
 // k lanes (stream, done event, workspace of `bytes`).
@@ -876,7 +935,7 @@ struct CallPlan {
 };
 
 int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int height, bool init, bool capturing,
-            CallPlan &cp) {
+            CallPlan &cp, int bidir = 0) {
   cp.n = n;
   c->call_frames = n;
   c->call_lanes = 1;
@@ -894,12 +953,12 @@ int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int heigh
   if (cp.nchunks > 1 && capturing) return OFDIS_ERR_UNSUPPORTED;
   if (cp.nchunks == 1) {
     cp.kind = CallPlan::kSingle;
-    cp.whole = batch_plan(p, n, width, height, init);
+    cp.whole = batch_plan(p, n, width, height, init, bidir);
     return ensure_ws(c, cp.whole.total);
   }
   cp.kind = CallPlan::kRoundRobin;
   for (int ch = 0; ch < cp.nchunks; ++ch)
-    cp.parts.push_back(batch_plan(p, std::min(chunk, n - ch * chunk), width, height, init));
+    cp.parts.push_back(batch_plan(p, std::min(chunk, n - ch * chunk), width, height, init, bidir));
   cp.lanes = std::min(nstreams, cp.nchunks);
   c->call_lanes = cp.lanes;
   return ensure_lanes(c, cp.lanes, cp.parts[0].total);
@@ -907,7 +966,8 @@ int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int heigh
 
 // Chunks round-robin over the lanes, each chunk's whole pipeline on one lane (fork from s, join into s).
 int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p,
-                      const uint8_t *img_a, const uint8_t *img_b, const float *init, float *flow_out) {
+                      const uint8_t *img_a, const uint8_t *img_b, const float *init, float *flow_out,
+                      const BidirOut *bd) {
   const int k = cp.lanes;
   HIP_OK(hipEventRecord(c->entry, s));
   for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
@@ -916,8 +976,9 @@ int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const
   for (int ch = 0; ch < cp.nchunks; ++ch) {
     const size_t f0 = (size_t)ch * cp.chunk;
     auto &L = c->lanes[ch % k];
+    const BidirOut part = bd ? bd->at(f0, (size_t)cp.width * cp.height) : BidirOut();
     int rc = run_chunk(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b + f0 * in_frame,
-                       init ? init + f0 * out_frame : nullptr, flow_out + f0 * out_frame, L.s);
+                       init ? init + f0 * out_frame : nullptr, flow_out + f0 * out_frame, bd ? &part : nullptr, L.s);
     if (rc) return rc;
   }
   for (int i = 0; i < k; ++i) {
@@ -928,10 +989,10 @@ int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const
 }
 
 int issue(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *img_a,
-          const uint8_t *img_b, const float *init, float *flow_out) {
+          const uint8_t *img_b, const float *init, float *flow_out, const BidirOut *bd) {
   switch (cp.kind) {
-    case CallPlan::kRoundRobin: return issue_round_robin(c, cp, s, p, img_a, img_b, init, flow_out);
-    default: return run_chunk(c, c->ws, cp.whole, p, img_a, img_b, init, flow_out, s);
+    case CallPlan::kRoundRobin: return issue_round_robin(c, cp, s, p, img_a, img_b, init, flow_out, bd);
+    default: return run_chunk(c, c->ws, cp.whole, p, img_a, img_b, init, flow_out, bd, s);
   }
 }
 
@@ -970,15 +1031,15 @@ int validate_call(const ofdis_params *p, int width, int height, bool init) {
 
 // The whole-batch device path on stream s (call ordering done by the caller).
 int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
-              int width, int height, const ofdis_params *p, float *flow_out) {
+              int width, int height, const ofdis_params *p, float *flow_out, const BidirOut *bd = nullptr) {
   const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
   CallPlan cp;
-  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp);
+  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, bd ? (bd->flow_bw ? 1 : 2) : 0);
   if (rc) return rc;
   OFDIS_TRACE("run_batch: kind %d, %d chunks of %d, %d lanes", (int)cp.kind, cp.nchunks, cp.chunk, cp.lanes);
   // graph 1: capture single-stream batches; graph 2: also the multi-lane (fork / join) issues
   const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
-  if (!graph || capturing || c->timing) return issue(c, cp, s, p, img_a, img_b, init, flow_out);
+  if (!graph || capturing || c->timing) return issue(c, cp, s, p, img_a, img_b, init, flow_out, bd);
   // ~80 dependent launches per chunk: record them once as a HIP graph (on the context's own stream -- the
   // caller's may be the legacy NULL stream, which cannot capture) and replay it on the caller's stream while
   // the pointers, sizes, parameters and options stay the same (set_option drops the graph).  Multi-lane
@@ -987,11 +1048,15 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
   std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
   key.a = img_a; key.b = img_b; key.out = flow_out; key.ws = c->ws; key.init = init;
   key.n = n; key.w = width; key.h = height; key.p = *p;
+  if (bd) {  // a plain call after a bidirectional one on the same buffers records anew, and the other way round
+    key.bidir = 1; key.flow_bw = bd->flow_bw; key.occ_fw = bd->occ_fw; key.occ_bw = bd->occ_bw;
+    key.err_fw = bd->err_fw; key.err_bw = bd->err_bw; key.alpha = bd->alpha; key.beta = bd->beta;
+  }
   if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0) {
     if ((rc = drop_graph(c))) return rc;
     OFDIS_TRACE("graph: capture (kind %d, %d chunks of %d)", (int)cp.kind, cp.nchunks, cp.chunk);
     HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = issue(c, cp, c->stream, p, img_a, img_b, init, flow_out);
+    rc = issue(c, cp, c->stream, p, img_a, img_b, init, flow_out, bd);
     OFDIS_TRACE("graph: issued rc %d", rc);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
@@ -1121,6 +1186,108 @@ int ofdis_run_batch_u8_init_host(ofdis_context *c, const uint8_t *img_a, const u
   hipFree(db);
   hipFree(dout);
   hipFree(dinit);
+  return rc;
+}
+
+namespace {
+bool fb_thresholds_ok(float alpha, float beta) {
+  return std::isfinite(alpha) && std::isfinite(beta) && alpha >= 0.0f && beta >= 0.0f;
+}
+}  // namespace
+
+int ofdis_fb_check(ofdis_context *c, const float *flow_fw, const float *flow_bw, int n, int width, int height,
+                   float alpha, float beta, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw,
+                   void *stream) {
+  if (!c || !flow_fw || !flow_bw || n <= 0 || width <= 0 || height <= 0 || !fb_thresholds_ok(alpha, beta) ||
+      (long)width * height > 0x7fffffffL)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  BidirOut o;
+  o.occ_fw = occ_fw;
+  o.occ_bw = occ_bw;
+  o.err_fw = err_fw;
+  o.err_bw = err_bw;
+  o.alpha = alpha;
+  o.beta = beta;
+  if (!o.checks()) return OFDIS_OK;
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
+  if (rc) return rc;
+  rc = run_fb_check(c, flow_fw, flow_bw, n, width, height, o, s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_bidir_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                       const ofdis_params *p, float alpha, float beta, float *flow_fw, float *flow_bw,
+                       uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw, void *stream) {
+  if (!c || !img_a || !img_b || !flow_fw || n <= 0 || width <= 0 || height <= 0 || !p ||
+      !fb_thresholds_ok(alpha, beta) || (long)width * height > 0x7fffffffL)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // the depth path's right-camera clamp has no pinned counterpart
+  BidirOut o;
+  o.flow_bw = flow_bw;
+  o.occ_fw = occ_fw;
+  o.occ_bw = occ_bw;
+  o.err_fw = err_fw;
+  o.err_bw = err_bw;
+  o.alpha = alpha;
+  o.beta = beta;
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  // nothing but the forward flow asked for: the plain call
+  rc = run_batch(c, s, img_a, img_b, nullptr, n, width, height, p, flow_fw, flow_bw || o.checks() ? &o : nullptr);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_bidir_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                            const ofdis_params *p, float alpha, float beta, float *flow_fw, float *flow_bw,
+                            uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw) {
+  if (!c || !img_a || !img_b || !flow_fw || n <= 0 || width <= 0 || height <= 0 || !p)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)n * width * height, in = px * p->noc;
+  // one device block: the two images, then (each at a multiple of 256 bytes) the outputs the caller asked for
+  float *const host_f[4] = {flow_fw, flow_bw, err_fw, err_bw};
+  uint8_t *const host_u[2] = {occ_fw, occ_bw};
+  const size_t bytes_f[4] = {px * 2 * sizeof(float), px * 2 * sizeof(float), px * sizeof(float), px * sizeof(float)};
+  size_t off_f[4], off_u[2], total = align_up(in) * 2;
+  for (int k = 0; k < 4; ++k) {
+    off_f[k] = total;
+    if (host_f[k]) total += align_up(bytes_f[k]);
+  }
+  for (int k = 0; k < 2; ++k) {
+    off_u[k] = total;
+    if (host_u[k]) total += align_up(px);
+  }
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, total));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  auto dev_f = [&](int k) { return host_f[k] ? (float *)(d + off_f[k]) : nullptr; };
+  auto dev_u = [&](int k) { return host_u[k] ? (uint8_t *)(d + off_u[k]) : nullptr; };
+  if (step(hipMemcpyAsync(d, img_a, in, hipMemcpyHostToDevice, c->stream)) &&
+      step(hipMemcpyAsync(d + align_up(in), img_b, in, hipMemcpyHostToDevice, c->stream))) {
+    rc = ofdis_run_bidir_u8(c, (const uint8_t *)d, (const uint8_t *)(d + align_up(in)), n, width, height, p, alpha,
+                            beta, dev_f(0), dev_f(1), dev_u(0), dev_u(1), dev_f(2), dev_f(3), c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      for (int k = 0; k < 4; ++k)
+        if (host_f[k]) step(hipMemcpy(host_f[k], d + off_f[k], bytes_f[k], hipMemcpyDeviceToHost));
+      for (int k = 0; k < 2; ++k)
+        if (host_u[k]) step(hipMemcpy(host_u[k], d + off_u[k], px, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
   return rc;
 }
 
@@ -1291,6 +1458,9 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   }
   if (k == "pyr_base") b = 2.0 * width * height * noc + 2.0 * 4.0 * P.lv[0].w * P.lv[0].h * noc;
   if (k == "upsample") b = (double)width * height * nop * 4.0;
+  // both directions: the pixel's own flow and the gathered one (16 B), the mask byte, the error with "fb_check_err"
+  if (k == "fb_check") b = 2.0 * width * height * (16.0 + 1.0);
+  if (k == "fb_check_err") b = 2.0 * width * height * (16.0 + 1.0 + 4.0);
   *bytes = b;
   return OFDIS_OK;
 }

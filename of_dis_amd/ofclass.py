@@ -207,6 +207,80 @@ class Context:
                                                  out.ctypes.data), "ofdis_run_batch_u8_init_host")
         return out[0] if single else out
 
+    def fb_check_ptr(self, fw_ptr: int, bw_ptr: int, n: int, width: int, height: int, alpha: float, beta: float,
+                     occ_fw_ptr: int = 0, occ_bw_ptr: int = 0, err_fw_ptr: int = 0, err_bw_ptr: int = 0,
+                     stream: int = 0) -> None:
+        """``ofdis_fb_check`` on raw device pointers (0 = that output is not wanted)."""
+        check(lib().ofdis_fb_check(self._h, fw_ptr or None, bw_ptr or None, n, width, height, alpha, beta,
+                                   occ_fw_ptr or None, occ_bw_ptr or None, err_fw_ptr or None, err_bw_ptr or None,
+                                   stream or None), "ofdis_fb_check")
+
+    def fb_check(self, flow_fw, flow_bw, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False):
+        """Forward-backward consistency of two flow fields: float32 CUDA tensors [n, h, w, 2] (or [h, w, 2]) ->
+        (occ_fw, occ_bw[, err_fw, err_bw]); occ uint8 [n, h, w] with 0 consistent, 1 inconsistent, 2 the flow
+        leaves the frame; err float32 [n, h, w], the squared round-trip error (+inf where occ is 2)."""
+        import torch
+        single = flow_fw.dim() == 3
+        fw, bw = (flow_fw[None], flow_bw[None]) if single else (flow_fw, flow_bw)
+        if (fw.dim() != 4 or fw.shape[-1] != 2 or fw.shape != bw.shape or fw.dtype != torch.float32
+                or bw.dtype != torch.float32 or not (fw.is_cuda and bw.is_cuda)):
+            raise ValueError("expected two float32 CUDA tensors [n, h, w, 2] of one shape")
+        fw, bw = fw.contiguous(), bw.contiguous()
+        n, h, w = fw.shape[:3]
+        occ = [torch.empty((n, h, w), dtype=torch.uint8, device=fw.device) for _ in range(2)]
+        err = [torch.empty((n, h, w), dtype=torch.float32, device=fw.device) for _ in range(2 if want_err else 0)]
+        stream = torch.cuda.current_stream(fw.device).cuda_stream
+        self.fb_check_ptr(fw.data_ptr(), bw.data_ptr(), n, w, h, alpha, beta, occ[0].data_ptr(), occ[1].data_ptr(),
+                          err[0].data_ptr() if want_err else 0, err[1].data_ptr() if want_err else 0, stream)
+        out = tuple(occ + err)
+        return tuple(t[0] for t in out) if single else out
+
+    def run_bidir_ptr(self, a_ptr: int, b_ptr: int, n: int, width: int, height: int, p: Params, alpha: float,
+                      beta: float, fw_ptr: int, bw_ptr: int = 0, occ_fw_ptr: int = 0, occ_bw_ptr: int = 0,
+                      err_fw_ptr: int = 0, err_bw_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_run_bidir_u8`` on raw device pointers, asynchronous on `stream`; every output but the forward
+        flow is optional (0)."""
+        check(lib().ofdis_run_bidir_u8(self._h, a_ptr, b_ptr, n, width, height, C.byref(p), alpha, beta,
+                                       fw_ptr or None, bw_ptr or None, occ_fw_ptr or None, occ_bw_ptr or None,
+                                       err_fw_ptr or None, err_bw_ptr or None, stream or None), "ofdis_run_bidir_u8")
+
+    def run_bidir(self, a, b, p: Params, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False):
+        """Both directions of each pair from one pyramid, and their consistency check: torch.uint8 CUDA tensors
+        [n, h, w] or [n, h, w, noc] -> (flow_fw, flow_bw, occ_fw, occ_bw[, err_fw, err_bw]).  flow_fw is
+        run(a, b), flow_bw is run(b, a), bit for bit; masks and errors as in fb_check.  Optical flow only."""
+        import torch
+        if a.dim() == 3:
+            a, b = a.unsqueeze(-1), b.unsqueeze(-1)
+        n, h, w, noc = a.shape
+        if noc != p.noc or a.dtype != torch.uint8 or a.shape != b.shape or not (a.is_cuda and b.is_cuda):
+            raise ValueError("expected uint8 CUDA tensors with noc channels")
+        a, b = a.contiguous(), b.contiguous()
+        flow = [torch.empty((n, h, w, 2), dtype=torch.float32, device=a.device) for _ in range(2)]
+        occ = [torch.empty((n, h, w), dtype=torch.uint8, device=a.device) for _ in range(2)]
+        err = [torch.empty((n, h, w), dtype=torch.float32, device=a.device) for _ in range(2 if want_err else 0)]
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        self.run_bidir_ptr(a.data_ptr(), b.data_ptr(), n, w, h, p, alpha, beta, flow[0].data_ptr(),
+                           flow[1].data_ptr(), occ[0].data_ptr(), occ[1].data_ptr(),
+                           err[0].data_ptr() if want_err else 0, err[1].data_ptr() if want_err else 0, stream)
+        return tuple(flow + occ + err)
+
+    def run_bidir_host(self, a: np.ndarray, b: np.ndarray, p: Params, alpha: float = 0.01, beta: float = 0.5,
+                       want_err: bool = False):
+        """run_bidir on numpy u8 [n,h,w,noc] (or a single [h,w,noc] pair); synchronous."""
+        single = a.ndim == 3
+        a4 = np.ascontiguousarray(a[None] if single else a, np.uint8)
+        b4 = np.ascontiguousarray(b[None] if single else b, np.uint8)
+        n, h, w = a4.shape[:3]
+        flow = [np.empty((n, h, w, 2), _f32) for _ in range(2)]
+        occ = [np.empty((n, h, w), np.uint8) for _ in range(2)]
+        err = [np.empty((n, h, w), _f32) for _ in range(2 if want_err else 0)]
+        check(lib().ofdis_run_bidir_u8_host(self._h, a4.ctypes.data, b4.ctypes.data, n, w, h, C.byref(p), alpha, beta,
+                                            flow[0].ctypes.data, flow[1].ctypes.data, occ[0].ctypes.data,
+                                            occ[1].ctypes.data, err[0].ctypes.data if want_err else None,
+                                            err[1].ctypes.data if want_err else None), "ofdis_run_bidir_u8_host")
+        out = tuple(flow + occ + err)
+        return tuple(t[0] for t in out) if single else out
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
