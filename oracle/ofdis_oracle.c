@@ -301,6 +301,14 @@ typedef struct {
   float dp_thresh_sq, dr_thresh, res_thresh, outlierthresh;
 } opt_t;
 
+/* Branch statistics of the patch optimisation (TEST INFRASTRUCTURE: which fallbacks an input drives).  Plain
+ * unsynchronised increments in branch bodies; no float depends on them.  Read them from single-threaded callers. */
+enum { ST_HESS_REG, ST_LLT_FAILED, ST_LLT_NONPOS_H00, ST_OOB_START, ST_OUTLIER_RESET, ST_OOB_ITER, ST_EARLY_STOP,
+       ST_NONFINITE_DELTA, ST_N };
+static long g_patch_stats[ST_N];
+void ofo_patch_stats_reset(void) { memset(g_patch_stats, 0, sizeof g_patch_stats); }
+void ofo_patch_stats_get(long out[8]) { memcpy(out, g_patch_stats, sizeof g_patch_stats); }
+
 /* Eigen LLT<2x2>.solve (unblocked llt_inplace + unrolled triangular solves). */
 static void llt2_solve(float H00, float H01, float H11, float b0, float b1, float *x0, float *x1) {
   float L00 = H00, L10 = H01, L11 = H11;
@@ -309,6 +317,9 @@ static void llt2_solve(float H00, float H01, float H11, float b0, float b1, floa
     L10 = H01 / L00;
     float t = H11 - L10 * L10;
     if (!(t <= 0.0f)) L11 = sqrtf(t);
+    else g_patch_stats[ST_LLT_FAILED]++;
+  } else {
+    g_patch_stats[ST_LLT_NONPOS_H00]++;
   }
   float y0 = b0 / L00;
   float y1 = (b1 - L10 * y0) / L11;
@@ -321,6 +332,7 @@ static void llt2_solve(float H00, float H01, float H11, float b0, float b1, floa
 static float llt1_solve(float H, float b) {
   float L = H;
   if (!(H <= 0.0f)) L = sqrtf(H);
+  else g_patch_stats[ST_LLT_NONPOS_H00]++;
   float y = b / L;
   return y / L;
 }
@@ -396,7 +408,10 @@ static void patch_err(const cam_t *c, const opt_t *o, const float *im_b, patch_t
   int keep = (P->cnt < o->max_iter) & (P->mares > o->res_thresh) &
              ((P->cnt < o->min_iter) | (P->sq / P->sq_init >= o->dp_thresh_sq)) &
              ((P->cnt < o->min_iter) | (P->mares / P->mares_old <= o->dr_thresh));
-  if (!keep) P->converged = 1;
+  if (!keep) {
+    P->converged = 1;
+    if (P->cnt < o->max_iter) g_patch_stats[ST_EARLY_STOP]++;
+  }
 }
 
 static inline void paramtopt(const opt_t *o, patch_t *P) {
@@ -449,9 +464,13 @@ static void patch_run(const cam_t *c, const opt_t *o, const float *im_a, const f
     if (P->H00 * P->H11 - P->H01 * P->H01 == 0.0f) {
       P->H00 = (float)((double)P->H00 + 1e-10);
       P->H11 = (float)((double)P->H11 + 1e-10);
+      g_patch_stats[ST_HESS_REG]++;
     }
   } else {
-    if (P->H00 == 0.0f) P->H00 = (float)((double)P->H00 + 1e-10);
+    if (P->H00 == 0.0f) {
+      P->H00 = (float)((double)P->H00 + 1e-10);
+      g_patch_stats[ST_HESS_REG]++;
+    }
   }
   /* OptimizeStart */
   P->p_in[0] = P->p_iter[0] = p_init[0];
@@ -464,6 +483,7 @@ static void patch_run(const cam_t *c, const opt_t *o, const float *im_a, const f
     memcpy(P->pdiff, P->tmp, sizeof(float) * nv);
     /* pweight is never written upstream (uninitialised heap, patch.cpp:133-139): defined as 0 here */
     memset(P->pweight, 0, sizeof(float) * nv);
+    g_patch_stats[ST_OOB_START]++;
   } else {
     P->cnt = 0;
     P->sq = P->sq_init = (float)1e-10;
@@ -489,9 +509,14 @@ static void patch_run(const cam_t *c, const opt_t *o, const float *im_a, const f
       else
         P->p_iter[0] = stdmaxf(P->p_iter[0], 0.0f);
     }
+    if (!isfinite(P->delta_p[0]) || (o->nop == 2 && !isfinite(P->delta_p[1]))) g_patch_stats[ST_NONFINITE_DELTA]++;
     paramtopt(o, P);
     float ex = P->pt_st[0] - P->pt_iter[0], ey = P->pt_st[1] - P->pt_iter[1];
-    if (sqrtf(ex * ex + ey * ey) > o->outlierthresh || out_of_bounds(c, P->pt_iter)) {
+    const float moved = sqrtf(ex * ex + ey * ey);
+    if (moved > o->outlierthresh || out_of_bounds(c, P->pt_iter)) {
+      /* the outlier test short-circuits the bounds test, as the reference's || does */
+      if (moved > o->outlierthresh) g_patch_stats[ST_OUTLIER_RESET]++;
+      else g_patch_stats[ST_OOB_ITER]++;
       P->p_iter[0] = P->p_in[0];
       if (o->nop == 2) P->p_iter[1] = P->p_in[1];
       paramtopt(o, P);

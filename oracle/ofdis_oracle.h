@@ -110,6 +110,14 @@ void ofo_sor_rb_of(float *du, float *dv, float *a11, float *a12, float *a22, con
 void ofo_sor_rb_de(float *du, const float *a11, const float *b1, const float *h, const float *v, int w, int hgt,
                    int iterations, float omega);
 
+/* Branch statistics of the patch optimisation since the last reset (TEST INFRASTRUCTURE; not reference functions).
+ * out[0..7]: hess_regularised (det == 0 for flow, H00 == 0 for depth), llt_failed (t <= 0 in the 2x2 factorisation:
+ * L11 stays H11), llt_nonpos_h00, oob_start, outlier_reset, oob_iter, early_stop (stopped with cnt < max_iter),
+ * nonfinite_delta.  The solves count once per iteration, the others once per patch.  They are plain unsynchronised
+ * increments that no float depends on: read them from single-threaded tests only. */
+void ofo_patch_stats_reset(void);
+void ofo_patch_stats_get(long out[8]);
+
 #ifdef __cplusplus
 }
 #endif

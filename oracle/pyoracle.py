@@ -87,6 +87,9 @@ def lib():
         L.ofo_sor_rb_de.argtypes = [_f32p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_float]
         L.ofo_set_sor_order.argtypes = [C.c_int]
         L.ofo_get_sor_order.restype = C.c_int
+        L.ofo_patch_stats_reset.restype = None
+        L.ofo_patch_stats_get.argtypes = [C.POINTER(C.c_long)]
+        L.ofo_patch_stats_get.restype = None
         for f in ("ofo_params_oppoint", "ofo_build_pyramid", "ofo_build_pyramid_ex", "ofo_oflow", "ofo_upsample_crop", "ofo_run_u8",
                   "ofo_run_u8_init", "ofo_refine_level"):
             getattr(L, f).restype = C.c_int
@@ -109,6 +112,22 @@ class sor_order:
     def __exit__(self, *exc):
         lib().ofo_set_sor_order(self.prev)
         return False
+
+
+PATCH_STATS = ("hess_regularised", "llt_failed", "llt_nonpos_h00", "oob_start", "outlier_reset", "oob_iter",
+               "early_stop", "nonfinite_delta")
+
+
+def patch_stats_reset() -> None:
+    lib().ofo_patch_stats_reset()
+
+
+def patch_stats() -> dict:
+    """Branch counts of the patch optimisation since patch_stats_reset() (ofdis_oracle.h).  Unsynchronised
+    statistics: meaningful only when nothing else drives the oracle meanwhile (single-threaded tests)."""
+    out = (C.c_long * len(PATCH_STATS))()
+    lib().ofo_patch_stats_get(out)
+    return dict(zip(PATCH_STATS, (int(v) for v in out)))
 
 
 def oppoint(op: int, width: int, mode: int = 1, noc: int = 1) -> Params:
