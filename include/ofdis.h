@@ -214,6 +214,10 @@ int ofdis_context_set_stage_capture(ofdis_context *ctx, float *const *dis_flow, 
  *                        CUs the lanes outside the frame load a slot of their wave's in-frame run (fewer fetched
  *                        lines, one v_med3 per load); 3: that load form in every launch; 1: sized to the
  *                        workgroup limit;
+ *   "sor_pack" (0..2, default 1): the sweep-per-wave SOR lays the rows of several frames end to end in one
+ *                        workgroup, so that levels of up to 128 rows fill their 64-lane waves (2 or 3 sweeps with
+ *                        the coefficient ring, where that saves a quarter of the waves or more); 1: in launches
+ *                        with more frames than CUs; 2: in every launch; 0: one frame per workgroup.  Same bits;
  *   "sor_rows2" (0/1, default 1): levels too tall for one row per lane in a 1024-thread workgroup run the
  *                        sweep-per-wave SOR with two rows per lane -- 321..640 rows at 3 sweeps, 513..1024 at
  *                        2 (else the register pipeline);

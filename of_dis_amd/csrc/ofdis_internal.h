@@ -123,6 +123,8 @@ struct TvArgs {
   int sor_point;               // OpenMP build: point SOR on the raw system (solver.c:34-78) for every size
   int sor_cring;               // lean SOR: coefficients loaded once by sweep 0, passed on through LDS (S <= 3);
                                // 2: the ring sized to the level's row groups
+  int sor_pack;                // lean SOR: rows of several frames end to end in one workgroup (sor_pack_frames);
+                               // 1: in launches with more frames than CUs, 2: in every launch
   int sor_rows2;               // lean SOR with two rows per lane for levels of 321..640 rows (else the pipeline)
   int smsys;                   // smoothness + system in one launch (k_tv_smsys)
   int prepd;                   // prep + derivatives in one launch (k_tv_prepd, intensity images; 0: three launches)

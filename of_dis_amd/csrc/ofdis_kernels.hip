@@ -4424,9 +4424,26 @@ __device__ __forceinline__ int sor_row2(int d, int lim, int rmax) {
 // the ring), so R = 2 runs levels of up to 640 rows with S <= 3 in 16 waves (E's 544-row level) where R = 1
 // would need 27.  Every per-row ring / coefficient-ring offset is a compile-time multiple of 64 entries.
 // SEL: load form of the lanes outside the frame (see load()).
-template <int S, int MODE, int SI, int NB, int CRN, int R = 1, bool SEL = false>
+// PK: packed frames (R = 1).  The workgroup serves F consecutive frames of the launch, their rows laid end to end
+// as one column of V = F h virtual rows, v = f h + y; wave (g, s) owns virtual rows 64 g .. 64 g + 63 of sweep s, and
+// the rings hold entry v + 1.  Schedule, ring protocol and arithmetic are the one-frame form's: all frames of a
+// launch share w and h, so the step's diagonal and its skewed row base stay wave-uniform, and what differs per
+// lane is a lane constant -- the row y inside the lane's own frame (borders, hasl / hasr, the SEL clamp) and the
+// frame's plane offset fo, added to the lane's slot.  Two neighbours cross a frame boundary and both are discarded:
+//  * the lane with y = 0 receives row h - 1 of the previous frame as its upper neighbour (DPP, or the ring for lane 0
+//    of a group): MODE 0 uses (tp, tsv) only in Y = tsv * tp, which the selects drop where notop holds (border is
+//    true there: l = X + bb, rg = -0 + Z); the DE form subtracts tsv * tu only where has_top = !notop;
+//  * the lane with y = h - 1 reads row 0 of the next frame as the ring entry below it (bt; sweep 0 loads slot h of
+//    its own plane row as before): MODE 0 uses bt only in Z = vv * bt, dropped where border && !notop holds
+//    (rg = -0 + Y); the DE form subtracts vv * bt.x only where has_bot = !(border && !notop).  (h >= 2: row 0 is
+//    not also row h - 1.)
+// Every discard is a select, never a product with zero, so whatever the other frame holds cannot reach a result.
+// Lanes past the workgroup's last frame (the launch's last workgroup, the tail of the last group) run as lanes
+// outside the frame do: loads clamped into the last frame's plane, stores masked, nothing below them.
+template <int S, int MODE, int SI, int NB, int CRN, int R = 1, bool SEL = false, bool PK = false>
 struct SorLane {
   static constexpr bool FIRST = SI == 0, LAST = SI == S - 1;
+  static_assert(!PK || R == 1, "packed frames run one row per lane");
   static_assert(CRN == 0 || S <= 3, "coefficient ring depth 6 needs S <= 3");
   static constexpr int PD = NB - 1;                                    // prefetch distance (steps)
   static constexpr int U = NB % 3 == 0 ? (NB < 6 ? 6 : NB) : 3 * NB;  // multiple of 3 (ring) and NB
@@ -4466,6 +4483,8 @@ struct SorLane {
   float4 *cr;
   int w, h, y, s, lim, rmax, hplane;
   unsigned yc[R];  // !SEL load slot: row y + 64 r clamped into the frame (lanes past h read row h - 1: in the plane)
+  unsigned fo;     // PK: plane offset of the lane's frame from the workgroup's first frame (yc[0] = fo + y)
+  bool live;       // PK: the lane's frame exists (stores)
   bool border[R], notop[R];
   float omega;
 #ifdef OFDIS_SOR_PROBE
@@ -4491,6 +4510,7 @@ struct SorLane {
       if (SEL) {
         const int lo = min(max(d - w + 1, 0), h - 1), hi = max(min(d, h - 1), 0);
         yr = (unsigned)min(max(y + 64 * r, lo), hi);
+        if (PK) yr += fo;
       }
       if (FIRST || CRN == 0) {
         const float4 *cp = C + (size_t)r0 * CW;
@@ -4607,10 +4627,11 @@ struct SorLane {
       if (CRN == 0) sv_s[r * RO + m0] = vv;
       pvv[r] = vv;
       if (LAST) {
-        if ((unsigned)xp < (unsigned)w && yr < h) {
+        if ((unsigned)xp < (unsigned)w && (PK ? live : yr < h)) {
           const unsigned r0 = (unsigned)sor_row2(d, lim, rmax) * (unsigned)hplane;
-          du[r0 + (unsigned)yr] = nw.x;
-          if (MODE == 0) dv[r0 + (unsigned)yr] = nw.y;
+          const unsigned ys = PK ? fo + (unsigned)yr : (unsigned)yr;
+          du[r0 + ys] = nw.x;
+          if (MODE == 0) dv[r0 + ys] = nw.y;
         }
       }
       pp[r] = nw;
@@ -4688,11 +4709,12 @@ __host__ __device__ __forceinline__ size_t sor_lanes_lds(int S, int h, int crn, 
   return (uv + 15) / 16 * 16 + sor_cring_bytes(crn, cw);
 }
 
-// One frame's SOR call, lean form: 64 * G * S threads, R rows per lane.
-template <int S, int MODE, int NB, int CRN, int R, bool SEL = false>
-__device__ __forceinline__ void sor_lanes_frame(const TvArgs &a, int frame, f2v *ring) {
+// One frame's SOR call, lean form: 64 * G * S threads, R rows per lane.  PK: the F frames from `frame` on (those
+// below a.n), G = ceil(F h / 64) groups of virtual rows.
+template <int S, int MODE, int NB, int CRN, int R, bool SEL = false, bool PK = false>
+__device__ __forceinline__ void sor_lanes_frame(const TvArgs &a, int frame, f2v *ring, int F = 1) {
   constexpr int CW = MODE == 0 ? 2 : 1;
-  const int G = (a.h + 64 * R - 1) / (64 * R);
+  const int G = ((PK ? F * a.h : a.h) + 64 * R - 1) / (64 * R);
   const int NR = G * 64 * R + 2;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int g = wid / S, s = wid - g * S;
@@ -4716,27 +4738,40 @@ __device__ __forceinline__ void sor_lanes_frame(const TvArgs &a, int frame, f2v 
   const long fo = (long)frame * a.sp;
   constexpr int U = SorLane<S, MODE, 0, NB, CRN, R>::U;
   const int T = ((a.w - 1) + (a.h - 1) + 2 * (S - 1) + 1 + U - 1) / U * U;
-  const int y0 = g * 64 * R, ymax = min(y0 + 64 * R - 1, a.h - 1);
+  int y0 = g * 64 * R, ymax = min(y0 + 64 * R - 1, a.h - 1);
+  const int v0 = y0;                   // PK: the wave's first virtual row
+  const int nf = min(F, a.n - frame);  // PK: frames of this workgroup
+  if (PK) {  // the smallest and largest row among the wave's live lanes: a wave that spans a frame boundary holds
+             // row h - 1 of one frame and row 0 of the next; a wave without live lanes runs row 0's steps unused
+    const int v1 = min(v0 + 63, nf * a.h - 1);
+    const int f0 = v0 / a.h, f1 = v1 / a.h;
+    y0 = v1 < v0 ? 0 : f0 == f1 ? v0 - f0 * a.h : 0;
+    ymax = v1 < v0 ? 0 : f0 == f1 ? v1 - f0 * a.h : a.h - 1;
+  }
   auto setup = [&](auto &st) {
     st.C = reinterpret_cast<const float4 *>(a.coef) + fo * (MODE == 0 ? 2 : 1);
     st.du_r = a.du + fo;
     st.dv_r = a.dv + fo;
     st.du = a.du + fo;
     st.dv = a.dv + fo;
-    const int y = y0 + lane;
-    st.ring_s = ring + (s * NR + y + 1) * 3;
-    st.ring_p = ring + ((s > 0 ? s - 1 : 0) * NR + y + 1) * 3;
-    st.sv_s = svr + (s * NR + y + 1) * 3;
-    st.cr = crr + y + 1;
+    const int v = v0 + lane;  // ring entry - 1: the row, PK: the virtual row
+    const int fl = PK ? v / a.h : 0;
+    const int y = v - fl * a.h;
+    st.ring_s = ring + (s * NR + v + 1) * 3;
+    st.ring_p = ring + ((s > 0 ? s - 1 : 0) * NR + v + 1) * 3;
+    st.sv_s = svr + (s * NR + v + 1) * 3;
+    st.cr = crr + v + 1;
     st.w = a.w; st.h = a.h; st.y = y; st.s = s;  // s == SI
+    st.live = fl < nf;
+    st.fo = (unsigned)min(fl, nf - 1) * (unsigned)a.sp;  // sor_pack_frames: F * sp * 32 bytes < 2^31
     st.lim = a.wrap ? a.w : 1 << 30;
     st.rmax = a.wrap ? a.w - 1 : a.w + a.h - 2;
     st.hplane = a.h;
-    st.top_lds = lane == 0 && y0 > 0;
+    st.top_lds = lane == 0 && v0 > 0 && y > 0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int yr = y + 64 * r;
-      st.yc[r] = (unsigned)min(yr, a.h - 1);
+      st.yc[r] = PK ? st.fo + (unsigned)y : (unsigned)min(yr, a.h - 1);
       st.notop[r] = yr == 0;
       st.border[r] = yr == 0 || yr >= a.h - 1;
     }
@@ -4748,16 +4783,16 @@ __device__ __forceinline__ void sor_lanes_frame(const TvArgs &a, int frame, f2v 
     st.run(T, y0, ymax);
   };
   if (s == 0) {
-    SorLane<S, MODE, 0, NB, CRN, R, SEL> st;
+    SorLane<S, MODE, 0, NB, CRN, R, SEL, PK> st;
     setup(st);
   } else if (s == 1) {
-    SorLane<S, MODE, (S > 1 ? 1 : 0), NB, CRN, R, SEL> st;
+    SorLane<S, MODE, (S > 1 ? 1 : 0), NB, CRN, R, SEL, PK> st;
     setup(st);
   } else if (s == 2) {
-    SorLane<S, MODE, (S > 2 ? 2 : 0), NB, CRN, R, SEL> st;
+    SorLane<S, MODE, (S > 2 ? 2 : 0), NB, CRN, R, SEL, PK> st;
     setup(st);
   } else {
-    SorLane<S, MODE, (S > 3 ? 3 : 0), NB, CRN, R, SEL> st;
+    SorLane<S, MODE, (S > 3 ? 3 : 0), NB, CRN, R, SEL, PK> st;
     setup(st);
   }
 }
@@ -4770,6 +4805,14 @@ __global__ __launch_bounds__(MAXT) void k_tv_sor_lanes(TvArgs a) {
   constexpr int crn = !CRING ? 0 : CG > 0 ? 64 * R * CG + 2 : sor_crn(S, MAXT, R);
   static_assert(CG == 0 || CG * 64 * S <= MAXT, "row groups of the workgroup");
   sor_lanes_frame<S, MODE, NB, crn, R, SEL>(a, blockIdx.x, ring_uv);
+}
+// Packed frames: workgroup b runs frames F b .. F b + F - 1 (SorLane, PK); CG as above, of the virtual rows.
+template <int S, int MODE, int NB, int MAXT, int CG, bool SEL>
+__global__ __launch_bounds__(MAXT) void k_tv_sor_lanes_pack(TvArgs a, int F) {
+  extern __shared__ f2v ring_uv[];
+  constexpr int crn = CG > 0 ? 64 * CG + 2 : sor_crn(S, MAXT, 1);
+  static_assert(CG == 0 || CG * 64 * S <= MAXT, "row groups of the workgroup");
+  sor_lanes_frame<S, MODE, NB, crn, 1, SEL, true>(a, blockIdx.x * F, ring_uv, F);
 }
 
 }  // namespace
@@ -4828,8 +4871,61 @@ static bool sor_lanes(const TvArgs &a, hipStream_t s) {
   pick<0, 1>(cring, [&](auto CR) { go(Int<0>{}, CR, sor_lanes_lds(S, a.h, CR ? crn : 0, cw, R)); });
   return launched;
 }
+// Packed frames (option sor_pack): frames per workgroup of an h-row level at S sweeps, 0 = one frame per workgroup.
+// A frame alone takes S ceil(h / 64) waves, and every wave issues the whole step whether its lanes hold rows or
+// not: 68 rows run 64 + 4, 34 and 17 rows fill 53 % and 27 % of their one group.  F frames end to end take
+// S ceil(F h / 64) waves.  F is the most frames that fit kSorPackGroups groups of 64 virtual rows; the form is
+// taken where
+//  * the launch is a throughput launch (more frames than CUs, the rule of the clamped loads; sor_pack 2: always),
+//    so the latency launches keep their kernels launch for launch;
+//  * S <= 3 with the coefficient ring (S = 4 and sor_cring 0 keep the one-frame form), 2 <= h <= 128;
+//  * ceil(F h / 64) S <= 16 waves and the rings fit the LDS (S = 3: the ring sized to the groups, CG);
+//  * it cuts the waves per frame by a quarter or more (64- and 128-row levels have no empty lanes to fill);
+//  * the lane's 32-bit slot index spans the F planes: F sp 32 bytes < 2^31.
+constexpr int kSorPackGroups = 4;
+static int sor_pack_frames(const TvArgs &a, int S) {
+  if (!a.sor_pack || !a.sor_cring || S > 3 || a.h < 2 || a.h > 128) return 0;
+  if (a.sor_pack < 2 && (long)a.n <= device_cus()) return 0;
+  const int F = 64 * kSorPackGroups / a.h, G = (F * a.h + 63) / 64, G1 = (a.h + 63) / 64;
+  if (F < 2 || G * S > 16 || 4 * G > 3 * G1 * F) return 0;
+  if ((long)F * a.sp * 32 >= (1L << 31)) return 0;
+  return F;
+}
+template <int S>
+static bool sor_lanes_pack(const TvArgs &a, hipStream_t s) {
+  if constexpr (S > 3) {
+    return false;
+  } else {
+    const int F = sor_pack_frames(a, S);
+    if (!F) return false;
+    const int G = (F * a.h + 63) / 64, cw = a.nop == 2 ? 2 : 1;
+    const bool sel = a.sor_cring >= 3 || (long)a.n > device_cus();  // as sor_lanes
+    const int wgs = (a.n + F - 1) / F;
+    bool launched = false;
+    auto go = [&](auto MAXT, auto CG) {
+      const int crn = CG > 0 ? 64 * CG + 2 : sor_crn(S, MAXT, 1);
+      const size_t lds = sor_lanes_lds(S, F * a.h, crn, cw, 1);
+      if (lds > kSorLds) return;
+      pick<0, 1>(sel, [&](auto SEL) {
+        pick_mode(a.nop, [&](auto MODE) {
+          k_tv_sor_lanes_pack<S, MODE, 3, MAXT, CG, SEL != 0><<<wgs, 64 * G * S, lds, s>>>(a, F);
+          launched = true;
+        });
+      });
+    };
+    if constexpr (S == 3) {  // 192 G threads
+      if (G <= 2) pick<1, 2>(G, [&](auto CG) { go(Int<512>{}, CG); });
+      else pick<3, 4, 5>(G, [&](auto CG) { go(Int<1024>{}, CG); });
+    } else {  // 128 G threads, the ring of the workgroup limit
+      if (G <= 4) go(Int<512>{}, Int<0>{});
+      else go(Int<1024>{}, Int<0>{});
+    }
+    return launched;
+  }
+}
 template <int S>
 static bool sor_lanes_s(const TvArgs &a, hipStream_t s) {
+  if (sor_lanes_pack<S>(a, s)) return true;
   const int th = 64 * S * ((a.h + 63) / 64);  // at one row per lane
   if (th <= 512) return sor_lanes<S, 512, 1>(a, s);
   if (th <= 1024) return sor_lanes<S, 1024, 1>(a, s);

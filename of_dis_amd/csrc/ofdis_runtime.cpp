@@ -112,6 +112,8 @@ struct ofdis_context {
   int opt_sor_cring = 2;       // sweep-per-wave SOR: coefficient ring in LDS (0: every sweep loads its coefficients;
                                // 2: ring sized to the level's row groups, the clamped in-frame load form in launches
                                // that oversubscribe the chip; 3: that load form in every launch; 1: workgroup limit)
+  int opt_sor_pack = 1;        // sweep-per-wave SOR: several frames' rows packed into one workgroup's waves (0: one
+                               // frame per workgroup; 1: launches with more frames than CUs; 2: every launch)
   int opt_prepd = 2;           // prep + derivatives in one launch: 1 intensity images, 2 colour images too (0: three launches)
   int opt_sor_rows2 = 1;       // sweep-per-wave SOR with two rows per lane for 321..640-row levels (0: pipeline)
   int opt_wave_per_patch = 0;  // 1: one wave per patch instead of eight lanes (A/B)
@@ -527,7 +529,7 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
       tv.sor_generic = c->opt_sor_generic;
       tv.sor_variant = c->opt_sor_pipe;
       tv.sor_cring = c->opt_sor_cring;
-      tv.sor_rows2 = c->opt_sor_rows2;
+      tv.sor_pack = c->opt_sor_pack;      tv.sor_rows2 = c->opt_sor_rows2;
       tv.smsys = c->opt_smsys;
       tv.smsys2d = c->opt_smsys2d == 2 ? c->call_frames < 512 : c->opt_smsys2d;
       tv.smsys_march = c->opt_smsys_march;
@@ -1364,7 +1366,7 @@ int ofdis_context_set_option(ofdis_context *c, const char *key, int value) {
       {"sor_generic", &ofdis_context::opt_sor_generic, 0, 1},
       {"sor_pipe", &ofdis_context::opt_sor_pipe, 0, 1},     {"smsys", &ofdis_context::opt_smsys, 0, 1},
       {"sor_cring", &ofdis_context::opt_sor_cring, 0, 3},   {"smsys2d", &ofdis_context::opt_smsys2d, 0, 2},
-      {"smsys_march", &ofdis_context::opt_smsys_march, 0, 1},
+      {"sor_pack", &ofdis_context::opt_sor_pack, 0, 2},      {"smsys_march", &ofdis_context::opt_smsys_march, 0, 1},
       {"smsys_prefetch", &ofdis_context::opt_smsys_prefetch, 0, 1},
       {"smsys_small", &ofdis_context::opt_smsys_small, 0, 1},
       {"smsys_deriv", &ofdis_context::opt_smsys_deriv, 0, 1},
