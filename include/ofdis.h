@@ -192,6 +192,35 @@ int ofdis_run_bidir_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint
                             int height, const ofdis_params *p, float alpha, float beta, float *flow_fw,
                             float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw);
 
+/* ------------------------------------------------------------------ video sequences
+ *
+ * Not in the reference, which reads two files per process.  frames: device u8 [nframes][height][width][noc], the
+ * consecutive frames of one video.  n = nframes - stride pairs are computed, pair i being (frame i, frame i + stride):
+ * flow_fw == ofdis_run_batch_u8(frames, frames + stride frames, n), bit for bit -- but every frame's pyramid (base
+ * level, 2x2 levels, padded image and gradients) is built once, nframes of them, where the two-array call builds 2n.
+ * All outputs are [n]...: flow_fw (required) float [n][height][width][2].  flow_bw, occ_*, err_* are optional and
+ * have ofdis_run_bidir_u8's meaning and arithmetic for every pair (flow_bw == the plain call on the pair reversed);
+ * with all five NULL, alpha and beta are ignored.  init_flow: optional device float [n][height][width][2], the
+ * initial flow per pair with ofdis_run_batch_u8_init's meaning.
+ * Refusals, before anything is enqueued (the context stays usable): stride < 1 or nframes <= stride, a NULL frames /
+ * flow_fw pointer or a non-positive size -> OFDIS_ERR_INVALID_ARGUMENT; with a backward output, alpha / beta as in
+ * ofdis_fb_check; init_flow together with any of the five backward outputs -> OFDIS_ERR_UNSUPPORTED (the
+ * bidirectional path has no pinned initial backward flow); OFDIS_MODE_DE -> OFDIS_ERR_UNSUPPORTED (a stereo pair is
+ * not a sequence).  A stage capture behaves as in ofdis_run_batch_u8 when no backward output is asked for (pair 0,
+ * one launch) and is refused as in ofdis_run_bidir_u8 otherwise.  verbosity is ignored (no TIME lines).
+ * Chunked calls ("streams" / "chunk", batches beyond ofdis_max_frames_per_launch()): a chunk of m pairs from pair f0
+ * reads frames [f0, f0 + m + stride), so neighbouring chunks rebuild the `stride` frames they share.  Stream,
+ * ordering and workspace rules are those of ofdis_run_batch_u8. */
+int ofdis_run_sequence_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, int stride, const float *init_flow,
+                          int width, int height, const ofdis_params *p, float alpha, float beta, float *flow_fw,
+                          float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw,
+                          void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_sequence_u8_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int stride,
+                               const float *init_flow, int width, int height, const ofdis_params *p, float alpha,
+                               float beta, float *flow_fw, float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw,
+                               float *err_fw, float *err_bw);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,

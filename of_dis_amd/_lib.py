@@ -107,7 +107,9 @@ def lib():
         "ofdis_fb_check": ([vp, vp, vp, i, i, i, f, f, vp, vp, vp, vp, vp], i),
         "ofdis_run_bidir_u8": ([vp, vp, vp, i, i, i, P, f, f, vp, vp, vp, vp, vp, vp, vp], i),
         "ofdis_run_bidir_u8_host": ([vp, vp, vp, i, i, i, P, f, f, vp, vp, vp, vp, vp, vp], i),
-        "ofdis_pyramid_u8_host": ([vp, vp, i, i, P, i, vp, vp, vp], i),
+        "ofdis_run_sequence_u8": ([vp, vp, i, i, vp, i, i, P, f, f, vp, vp, vp, vp, vp, vp, vp], i),
+        "ofdis_run_sequence_u8_host": ([vp, vp, i, i, vp, i, i, P, f, f, vp, vp, vp, vp, vp, vp], i),
+        "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),
         "ofdis_context_set_option": ([vp, C.c_char_p, i], i),
         "ofdis_context_enable_kernel_timing": ([vp, i], i),

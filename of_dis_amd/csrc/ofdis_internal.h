@@ -2,7 +2,8 @@
 //
 // Device data layout (per batch of n frame pairs, all float32 unless noted):
 //   pyramid level s   : [2n][H_s][W_s][noc]  padded by `pad` (W_s = w_s + 2 pad); frames 0..n-1 are
-//                       image a, n..2n-1 image b (same layout as OFClass's inputs, oflow.h:99-106)
+//                       image a, n..2n-1 image b (same layout as OFClass's inputs, oflow.h:99-106).
+//                       A sequence call holds [n + stride] frames instead: pair f is (frame f, frame f + stride)
 //   patch state       : p_iter [n][npatch][nop], pweight [n][npatch][novals]
 //   flow level s      : planar [n][nop][h_s][w_s]  (wx, wy)
 //   TV scratch        : planar [n][plane][h][w] for du, dv, mask, a11, a12, a22, b1, b2, sh, sv,
@@ -23,23 +24,25 @@ struct LevelGeom {
   int level;       // scale index s
 };
 
+// The pyramid kernels build nf frames: frames 0..n-1 come from img_a, n..nf-1 from img_b.  Pairs: nf = 2n.
+// A sequence (ofdis_run_sequence_u8): one array of nf = pairs + stride frames, n = nf, img_b unread.
 struct PyrBaseArgs {
-  const uint8_t *img_a, *img_b;  // [n][H0][W0][noc]
-  int n, W0, H0, noc;
+  const uint8_t *img_a, *img_b;  // [n][H0][W0][noc], [nf - n][H0][W0][noc]
+  int n, nf, W0, H0, noc;
   int padl, padt;                // divisibility padding offsets (floor halves)
   int log2s;                     // level of the output (sc_l)
   int w, h;                      // output level size
-  float *out;                    // unpadded level [2n][h][w][noc]
-  int rgb_sad;                   // colour, 2^l = 4..16: k_pyr_base_rgb (option pyr_rgb)
+  float *out;                    // unpadded level [nf][h][w][noc]
+  int rgb_sad;                  // colour, 2^l = 4..16: k_pyr_base_rgb (option pyr_rgb)
 };
 
 // SELECTCHANNEL 2 (run_dense.cpp:139-148): level 0 = Sobel gradient magnitude of the divisibility-padded
 // intensity frame, sqrt(dx*dx + dy*dy) (exact up to the correctly rounded sqrt: dx, dy are multiples of
 // 1/8 below 2^10, their squares and sum exact in fp32).
 struct PyrGradmagArgs {
-  const uint8_t *img_a, *img_b;  // [n][H0][W0]
-  int n, W0, H0, padl, padt, Wp, Hp;
-  float *out;                    // [2n][Hp][Wp]
+  const uint8_t *img_a, *img_b;  // [n][H0][W0], [nf - n][H0][W0] (as PyrBaseArgs)
+  int n, nf, W0, H0, padl, padt, Wp, Hp;
+  float *out;                    // [nf][Hp][Wp]
 };
 
 struct PyrDownArgs {

@@ -125,14 +125,14 @@ __global__ __launch_bounds__(256) void k_pyr_base(PyrBaseArgs a) {
   }
 }
 
-// Intensity images, 2^L = 4..32: one output pixel per thread over the flattened [2n][h][w] range (full
+// Intensity images, 2^L = 4..32: one output pixel per thread over the flattened [nf][h][w] range (full
 // waves even for narrow levels), the 2^L rows of the block unrolled so all loads are in flight at once,
 // 4 / 8 / 16-byte loads summed with v_sad_u8.  Blocks that need horizontal clamping take the byte loop.
 template <int L>
 __global__ __launch_bounds__(256) void k_pyr_base_gray(PyrBaseArgs a) {
   constexpr int B = 1 << L;
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= 2L * a.n * a.h * a.w) return;
+  if (t >= (long)a.nf * a.h * a.w) return;
   const int x = (int)(t % a.w);
   const long r = t / a.w;
   const int y = (int)(r % a.h), f = (int)(r / a.h);
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void k_pyr_base_gray(PyrBaseArgs a) {
   a.out[t] = (float)sum * scale;
 }
 
-// Colour images, 2^L = 4..16: one output pixel per thread over the flattened [2n][h][w] range, each of its 2^L rows
+// Colour images, 2^L = 4..16: one output pixel per thread over the flattened [nf][h][w] range, each of its 2^L rows
 // read as 3 * 2^L / 4 dwords (4 pixels' B, G, R per 3 dwords) and each channel's bytes summed by v_sad_u8 under a
 // byte mask -- exact integer sums like k_pyr_base's byte loop (the order of an integer sum is free).  Blocks that
 // need horizontal clamping or are not dword-aligned take the byte loop.  Config C: 4.22 -> 1.50 ms per step
@@ -188,7 +188,7 @@ template <int L>
 __global__ __launch_bounds__(256) void k_pyr_base_rgb(PyrBaseArgs a) {
   constexpr int B = 1 << L, ND = 3 * B / 4;  // dwords per block row
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= 2L * a.n * a.h * a.w) return;
+  if (t >= (long)a.nf * a.h * a.w) return;
   const int x = (int)(t % a.w);
   const long r = t / a.w;
   const int y = (int)(r % a.h), f = (int)(r / a.h);
@@ -348,14 +348,14 @@ __global__ __launch_bounds__(256) void k_pyr_pad_grad_v(PyrPadGradArgs a) {
 }  // namespace
 // ---- launch
 void launch_pyr_base(const PyrBaseArgs &a, hipStream_t s) {
-  const unsigned blocks = ceil_div(2L * a.n * a.h * a.w, 256);
+  const unsigned blocks = ceil_div((long)a.nf * a.h * a.w, 256);
   if (a.noc == 1 && pick<2, 3, 4, 5>(a.log2s, [&](auto L) { k_pyr_base_gray<L><<<blocks, 256, 0, s>>>(a); })) return;
   if (a.noc == 3 && a.rgb_sad && pick<2, 3, 4>(a.log2s, [&](auto L) { k_pyr_base_rgb<L><<<blocks, 256, 0, s>>>(a); }))
     return;
-  k_pyr_base<<<dim3(ceil_div(a.w, 256), a.h, 2 * a.n), 256, 0, s>>>(a);
+  k_pyr_base<<<dim3(ceil_div(a.w, 256), a.h, a.nf), 256, 0, s>>>(a);
 }
 void launch_pyr_gradmag(const PyrGradmagArgs &a, hipStream_t s) {
-  k_pyr_gradmag<<<dim3(ceil_div(a.Wp, 256), a.Hp, 2 * a.n), 256, 0, s>>>(a);
+  k_pyr_gradmag<<<dim3(ceil_div(a.Wp, 256), a.Hp, a.nf), 256, 0, s>>>(a);
 }
 void launch_pyr_down(const PyrDownArgs &a, hipStream_t s) {
   k_pyr_down<<<std::min(ceil_div((long)a.n2 * a.h * a.w * a.noc, 256), 1u << 22), 256, 0, s>>>(a);  // grid-stride beyond

@@ -30,6 +30,10 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     "fb_check", "fb_check_err"};
 
 struct Plan {
+  // n pairs over nfr pyramid frames, frame b of pair f lying bdist frames after its frame a: two arrays of n frames
+  // (nfr = 2n, bdist = n), or one sequence of n + stride frames (bdist = stride; ofdis_run_sequence_u8)
+  int nfr = 0, bdist = 0;
+  bool seq = false;
   int n = 0, W0 = 0, H0 = 0, Wp = 0, Hp = 0, padl = 0, padt = 0, padw = 0, padh = 0;
   int nop = 2, noc = 1, pad = 8, sc_f = 0, sc_l = 0;
   std::vector<LevelGeom> lv;                       // index s - sc_l
@@ -41,7 +45,7 @@ struct Plan {
   bool bidir = false;   // ofdis_run_bidir_u8: the backward grid, flow and refinement at every level, sc_l included
   size_t off_up_bw = 0; // bidir without a caller's flow_bw: the full-resolution backward flow [n][H0][W0][2]
   bool gradmag = false; // SELECTCHANNEL 2: float level 0 (gradient magnitude) halved down to sc_l
-  size_t off_gm = 0;    // its scratch: [2n][Hp][Wp] + [2n][Hp/2][Wp/2] (ping-pong)
+  size_t off_gm = 0;    // its scratch: [nfr][Hp][Wp] + [nfr][Hp/2][Wp/2] (ping-pong)
   size_t total = 0;
 };
 
@@ -80,6 +84,7 @@ struct ofdis_context {
     const void *flow_bw = nullptr, *occ_fw = nullptr, *occ_bw = nullptr, *err_fw = nullptr, *err_bw = nullptr;
     float alpha = 0.f, beta = 0.f;  // the bidirectional call's extra outputs and thresholds
     int bidir = 0;
+    int seq = 0, stride = 0;  // ofdis_run_sequence_u8: `a` is one array of n + stride frames, b is NULL
     int n = 0, w = 0, h = 0;
     ofdis_params p{};
   } gkey;
@@ -242,9 +247,14 @@ int steps_of(const ofdis_params *p) {
   return st0 > 1 ? st0 : 1;
 }
 
-Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init = false, bool bidir = false) {
+Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init = false, bool bidir = false,
+               int stride = 0) {
   Plan P;
   P.n = n;
+  P.seq = stride > 0;
+  P.nfr = P.seq ? n + stride : 2 * n;
+  P.bdist = P.seq ? stride : n;
+  const size_t nfr = (size_t)P.nfr;
   P.Wp = Wp;
   P.Hp = Hp;
   P.nop = p->mode == OFDIS_MODE_OF ? 2 : 1;
@@ -271,13 +281,14 @@ Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init 
     fill_level(p, Wp, Hp, pad, s, P.lv[i]);
     const LevelGeom &g = P.lv[i];
     P.off_lvl[i] = off;
-    off = align_up(off + sizeof(float) * 2 * (size_t)n * g.w * g.h * P.noc);
-    P.off_img[i] = off;  // (+64 floats: the windowed patch kernel's 16-byte row loads may read past the last row)
-    off = align_up(off + sizeof(float) * (2 * (size_t)n * g.W * g.H * P.noc + 64));
+    off = align_up(off + sizeof(float) * nfr * g.w * g.h * P.noc);
+    P.off_img[i] = off;  // (+64 floats: the windowed patch kernel's 16-byte row loads may read past the last row
+                         // of the last frame -- frame nfr - 1, the last pair's frame b in either layout)
+    off = align_up(off + sizeof(float) * (nfr * g.W * g.H * P.noc + 64));
     P.off_dx[i] = off;
-    off = align_up(off + sizeof(float) * 2 * (size_t)n * g.W * g.H * P.noc);
+    off = align_up(off + sizeof(float) * nfr * g.W * g.H * P.noc);
     P.off_dy[i] = off;
-    off = align_up(off + sizeof(float) * 2 * (size_t)n * g.W * g.H * P.noc);
+    off = align_up(off + sizeof(float) * nfr * g.W * g.H * P.noc);
     P.off_flow[i] = off;
     off = align_up(off + sizeof(float) * (size_t)n * P.nop * g.w * g.h);
     P.off_flow_bw[i] = off;
@@ -303,7 +314,7 @@ Plan make_plan(const ofdis_params *p, int n, int Wp, int Hp, int pad, bool init 
   P.off_gm = off;
   if (p->gradmag) {
     P.gradmag = true;
-    off = align_up(off + sizeof(float) * 2 * (size_t)n * ((size_t)Wp * Hp + (size_t)(Wp / 2) * (Hp / 2)));
+    off = align_up(off + sizeof(float) * nfr * ((size_t)Wp * Hp + (size_t)(Wp / 2) * (Hp / 2)));
   }
   P.off_init = off;
   if (init) {
@@ -371,6 +382,7 @@ static float sqrt_le_bound(float t) {
 int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, hipStream_t s, const float *init,
                std::vector<StageTimes> *times) {
   const int nop = P.nop, noc = P.noc, n = P.n;
+  const size_t bd = (size_t)P.bdist;  // frame b of pair f: bd frames after frame a in every pyramid array
   const int novals = noc * p->p_samp_s * p->p_samp_s;
   const int steps = steps_of(p);
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -390,7 +402,7 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
     pa.img_a = img;
     pa.dx_a = dxp;
     pa.dy_a = dyp;
-    pa.img_b = img + (size_t)n * fsp;
+    pa.img_b = img + bd * fsp;
     if (sl < p->sc_f) {
       const LevelGeom &gc = P.lv[i + 1];
       pa.prev = (const float *)(ws + P.off_flow[i + 1]);
@@ -431,6 +443,8 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
     pa.aslots = (p->p_samp_s - 1) / steps + 1;
     pa.fdiv = c->opt_patch_fdiv;
     pa.maxres = c->opt_patch_maxres && pa.res_thresh == 0.0f && pa.min_iter >= pa.max_iter;
+    // the buffer resource starts at the launch's img_b and its offsets cover that pointer's n frames, whichever
+    // frame of the array it is (forward: frame bd, backward: frame 0) -- the extent does not depend on bd
     pa.buf32 = c->opt_patch_buf && (size_t)n * fsp * sizeof(float) + 4096 <= 0xffffffffu;
     pa.generic = c->opt_patch_generic;
     pa.g = g;
@@ -451,9 +465,9 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
     const bool bw = P.fb || P.bidir;
     bool absw_bw = false;
     if (bw) {
-      pb.img_a = img + (size_t)n * fsp;
-      pb.dx_a = dxp + (size_t)n * fsp;
-      pb.dy_a = dyp + (size_t)n * fsp;
+      pb.img_a = img + bd * fsp;
+      pb.dx_a = dxp + bd * fsp;
+      pb.dy_a = dyp + bd * fsp;
       pb.img_b = img;
       pb.prev = nullptr;
       if (sl < p->sc_f) pb.prev = (const float *)(ws + P.off_flow_bw[i + 1]);
@@ -488,8 +502,8 @@ int run_levels(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p,
       const size_t pl = (size_t)n * sp;
       float *t0 = (float *)(ws + P.off_tv);
       TvArgs tv{};
-      tv.img_a = dir == 0 ? img : img + (size_t)n * fsp;
-      tv.img_b = dir == 0 ? img + (size_t)n * fsp : img;
+      tv.img_a = dir == 0 ? img : img + bd * fsp;
+      tv.img_b = dir == 0 ? img + bd * fsp : img;
       tv.flow = dir == 0 ? flow : flow_bw;
       tv.du = t0;
       tv.dv = t0 + pl;
@@ -646,15 +660,17 @@ int check_device(int device) {
 }
 
 // Pyramid of the batch (run_dense.cpp:299-312,327-328,131-179) into the workspace.
+// Pairs: frames 0..n-1 from a, n..2n-1 from b.  A sequence plan: its n + stride frames from a alone (b unread).
 int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, const uint8_t *b, hipStream_t s) {
-  const int n2 = 2 * P.n;
+  const int n2 = P.nfr, na = P.seq ? P.nfr : P.n;
   if (P.gradmag) {  // SELECTCHANNEL 2 (run_dense.cpp:139-148): float level 0, then 2x2 means down to sc_l
     float *lvl0 = (float *)(ws + P.off_lvl[0]);
     float *bufA = (float *)(ws + P.off_gm), *bufB = bufA + (size_t)n2 * P.Wp * P.Hp;
     PyrGradmagArgs g{};
     g.img_a = a;
     g.img_b = b;
-    g.n = P.n;
+    g.n = na;
+    g.nf = n2;
     g.W0 = P.W0;
     g.H0 = P.H0;
     g.padl = P.padl;
@@ -680,7 +696,8 @@ int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, con
     PyrBaseArgs pb{};
     pb.img_a = a;
     pb.img_b = b;
-    pb.n = P.n;
+    pb.n = na;
+    pb.nf = n2;
     pb.W0 = P.W0;
     pb.H0 = P.H0;
     pb.noc = P.noc;
@@ -721,10 +738,12 @@ int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, con
 }
 
 // bidir: 0 plain, 1 both directions, 2 both directions and the full-resolution backward flow kept in the workspace
-Plan batch_plan(const ofdis_params *p, int n, int width, int height, bool init = false, int bidir = 0) {
+// stride: 0 two arrays of n frames, k > 0 one sequence of n + k frames
+Plan batch_plan(const ofdis_params *p, int n, int width, int height, bool init = false, int bidir = 0,
+                int stride = 0) {
   const int d = 1 << (p->sc_f + (init ? 1 : 0));  // run_dense.cpp:301-302
   const int padw = (width % d) ? d - width % d : 0, padh = (height % d) ? d - height % d : 0;
-  Plan P = make_plan(p, n, width + padw, height + padh, p->p_samp_s, init, bidir != 0);
+  Plan P = make_plan(p, n, width + padw, height + padh, p->p_samp_s, init, bidir != 0, stride);
   P.off_up_bw = P.total;
   if (bidir == 2) P.total = align_up(P.total + sizeof(float) * (size_t)n * width * height * P.nop);
   P.W0 = width;
@@ -937,7 +956,7 @@ struct CallPlan {
 };
 
 int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int height, bool init, bool capturing,
-            CallPlan &cp, int bidir = 0) {
+            CallPlan &cp, int bidir = 0, int stride = 0) {
   cp.n = n;
   c->call_frames = n;
   c->call_lanes = 1;
@@ -955,18 +974,20 @@ int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int heigh
   if (cp.nchunks > 1 && capturing) return OFDIS_ERR_UNSUPPORTED;
   if (cp.nchunks == 1) {
     cp.kind = CallPlan::kSingle;
-    cp.whole = batch_plan(p, n, width, height, init, bidir);
+    cp.whole = batch_plan(p, n, width, height, init, bidir, stride);
     return ensure_ws(c, cp.whole.total);
   }
   cp.kind = CallPlan::kRoundRobin;
   for (int ch = 0; ch < cp.nchunks; ++ch)
-    cp.parts.push_back(batch_plan(p, std::min(chunk, n - ch * chunk), width, height, init, bidir));
+    cp.parts.push_back(batch_plan(p, std::min(chunk, n - ch * chunk), width, height, init, bidir, stride));
   cp.lanes = std::min(nstreams, cp.nchunks);
   c->call_lanes = cp.lanes;
   return ensure_lanes(c, cp.lanes, cp.parts[0].total);
 }
 
 // Chunks round-robin over the lanes, each chunk's whole pipeline on one lane (fork from s, join into s).
+// A sequence call (img_b NULL): the chunk of m pairs from pair f0 reads frames [f0, f0 + m + stride) of the caller's
+// array, so neighbouring chunks rebuild the `stride` frames they share; the outputs are per pair as ever.
 int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p,
                       const uint8_t *img_a, const uint8_t *img_b, const float *init, float *flow_out,
                       const BidirOut *bd) {
@@ -979,7 +1000,7 @@ int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const
     const size_t f0 = (size_t)ch * cp.chunk;
     auto &L = c->lanes[ch % k];
     const BidirOut part = bd ? bd->at(f0, (size_t)cp.width * cp.height) : BidirOut();
-    int rc = run_chunk(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b + f0 * in_frame,
+    int rc = run_chunk(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b ? img_b + f0 * in_frame : nullptr,
                        init ? init + f0 * out_frame : nullptr, flow_out + f0 * out_frame, bd ? &part : nullptr, L.s);
     if (rc) return rc;
   }
@@ -1031,12 +1052,14 @@ int validate_call(const ofdis_params *p, int width, int height, bool init) {
   return tv_frame_cap(p, width, height) >= 1 ? OFDIS_OK : OFDIS_ERR_INVALID_ARGUMENT;
 }
 
-// The whole-batch device path on stream s (call ordering done by the caller).
+// The whole-batch device path on stream s (call ordering done by the caller).  stride > 0: img_a is a sequence of
+// n + stride frames and pair i is (frame i, frame i + stride); img_b is NULL.
 int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
-              int width, int height, const ofdis_params *p, float *flow_out, const BidirOut *bd = nullptr) {
+              int width, int height, const ofdis_params *p, float *flow_out, const BidirOut *bd = nullptr,
+              int stride = 0) {
   const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
   CallPlan cp;
-  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, bd ? (bd->flow_bw ? 1 : 2) : 0);
+  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, bd ? (bd->flow_bw ? 1 : 2) : 0, stride);
   if (rc) return rc;
   OFDIS_TRACE("run_batch: kind %d, %d chunks of %d, %d lanes", (int)cp.kind, cp.nchunks, cp.chunk, cp.lanes);
   // graph 1: capture single-stream batches; graph 2: also the multi-lane (fork / join) issues
@@ -1050,6 +1073,7 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
   std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
   key.a = img_a; key.b = img_b; key.out = flow_out; key.ws = c->ws; key.init = init;
   key.n = n; key.w = width; key.h = height; key.p = *p;
+  key.seq = stride > 0; key.stride = stride;  // a sequence call on a plain call's buffers records anew
   if (bd) {  // a plain call after a bidirectional one on the same buffers records anew, and the other way round
     key.bidir = 1; key.flow_bw = bd->flow_bw; key.occ_fw = bd->occ_fw; key.occ_bw = bd->occ_bw;
     key.err_fw = bd->err_fw; key.err_bw = bd->err_bw; key.alpha = bd->alpha; key.beta = bd->beta;
@@ -1282,6 +1306,84 @@ int ofdis_run_bidir_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_
       step(hipMemcpyAsync(d + align_up(in), img_b, in, hipMemcpyHostToDevice, c->stream))) {
     rc = ofdis_run_bidir_u8(c, (const uint8_t *)d, (const uint8_t *)(d + align_up(in)), n, width, height, p, alpha,
                             beta, dev_f(0), dev_f(1), dev_u(0), dev_u(1), dev_f(2), dev_f(3), c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      for (int k = 0; k < 4; ++k)
+        if (host_f[k]) step(hipMemcpy(host_f[k], d + off_f[k], bytes_f[k], hipMemcpyDeviceToHost));
+      for (int k = 0; k < 2; ++k)
+        if (host_u[k]) step(hipMemcpy(host_u[k], d + off_u[k], px, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+
+int ofdis_run_sequence_u8(ofdis_context *c, const uint8_t *frames, int nframes, int stride, const float *init,
+                          int width, int height, const ofdis_params *p, float alpha, float beta, float *flow_fw,
+                          float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw,
+                          void *stream) {
+  if (!c || !frames || !flow_fw || width <= 0 || height <= 0 || !p || stride < 1 || nframes <= stride)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  BidirOut o;
+  o.flow_bw = flow_bw;
+  o.occ_fw = occ_fw;
+  o.occ_bw = occ_bw;
+  o.err_fw = err_fw;
+  o.err_bw = err_bw;
+  o.alpha = alpha;
+  o.beta = beta;
+  const bool bidir = flow_bw || o.checks();
+  if (bidir && (!fb_thresholds_ok(alpha, beta) || (long)width * height > 0x7fffffffL)) return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, init != nullptr);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
+  if (init && bidir) return OFDIS_ERR_UNSUPPORTED;              // no pinned initial backward flow
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (bidir && (!c->cap_dis.empty() || !c->cap_tv.empty())) return OFDIS_ERR_UNSUPPORTED;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch(c, s, frames, nullptr, init, nframes - stride, width, height, p, flow_fw, bidir ? &o : nullptr, stride);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_sequence_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int stride, const float *init,
+                               int width, int height, const ofdis_params *p, float alpha, float beta, float *flow_fw,
+                               float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw) {
+  if (!c || !frames || !flow_fw || width <= 0 || height <= 0 || !p || stride < 1 || nframes <= stride)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // (the buffers below are sized for two components)
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)(nframes - stride) * width * height, in = (size_t)nframes * width * height * p->noc;
+  // one device block: the frames, then (each at a multiple of 256 bytes) the initial flow and the outputs asked for
+  float *const host_f[4] = {flow_fw, flow_bw, err_fw, err_bw};
+  uint8_t *const host_u[2] = {occ_fw, occ_bw};
+  const size_t bytes_f[4] = {px * 2 * sizeof(float), px * 2 * sizeof(float), px * sizeof(float), px * sizeof(float)};
+  size_t off_f[4], off_u[2], total = align_up(in);
+  const size_t off_init = total;
+  if (init) total += align_up(bytes_f[0]);
+  for (int k = 0; k < 4; ++k) {
+    off_f[k] = total;
+    if (host_f[k]) total += align_up(bytes_f[k]);
+  }
+  for (int k = 0; k < 2; ++k) {
+    off_u[k] = total;
+    if (host_u[k]) total += align_up(px);
+  }
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, total));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  auto dev_f = [&](int k) { return host_f[k] ? (float *)(d + off_f[k]) : nullptr; };
+  auto dev_u = [&](int k) { return host_u[k] ? (uint8_t *)(d + off_u[k]) : nullptr; };
+  if (step(hipMemcpyAsync(d, frames, in, hipMemcpyHostToDevice, c->stream)) &&
+      (!init || step(hipMemcpyAsync(d + off_init, init, bytes_f[0], hipMemcpyHostToDevice, c->stream)))) {
+    rc = ofdis_run_sequence_u8(c, (const uint8_t *)d, nframes, stride, init ? (const float *)(d + off_init) : nullptr,
+                               width, height, p, alpha, beta, dev_f(0), dev_f(1), dev_u(0), dev_u(1), dev_f(2),
+                               dev_f(3), c->stream);
     if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
       for (int k = 0; k < 4; ++k)
         if (host_f[k]) step(hipMemcpy(host_f[k], d + off_f[k], bytes_f[k], hipMemcpyDeviceToHost));

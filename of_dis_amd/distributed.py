@@ -22,6 +22,19 @@ def shard_range(n_total: int, rank: int, world: int):
     return start, start + base + (1 if rank < rem else 0)
 
 
+def shard_sequence(n_frames: int, stride: int, rank: int, world: int):
+    """A video of `n_frames` frames, pair i = (frame i, frame i + stride), split over the ranks:
+    (frame_start, frame_stop, pair_start, pair_stop).  The n_frames - stride pairs are split as `shard_range` splits
+    them, and the rank's frames are those of its pairs -- `stride` more than its pairs -- so
+    ``run_sequence(frames[frame_start:frame_stop], stride=stride)`` gives pairs [pair_start, pair_stop) and the shards'
+    outputs concatenate to the whole call's.  With more ranks than pairs a rank has pair_start == pair_stop: it
+    has nothing to compute (a sequence call needs at least one pair)."""
+    if stride < 1 or n_frames <= stride:
+        raise ValueError("a sequence needs stride >= 1 and more than `stride` frames")
+    p0, p1 = shard_range(n_frames - stride, rank, world)
+    return p0, p1 + stride, p0, p1
+
+
 def max_over_ranks(value: float, device=None) -> float:
     import torch
     import torch.distributed as dist

@@ -281,6 +281,72 @@ class Context:
         out = tuple(flow + occ + err)
         return tuple(t[0] for t in out) if single else out
 
+    def run_sequence_ptr(self, frames_ptr: int, nframes: int, stride: int, width: int, height: int, p: Params,
+                         fw_ptr: int, init_ptr: int = 0, alpha: float = 0.01, beta: float = 0.5, bw_ptr: int = 0,
+                         occ_fw_ptr: int = 0, occ_bw_ptr: int = 0, err_fw_ptr: int = 0, err_bw_ptr: int = 0,
+                         stream: int = 0) -> None:
+        """``ofdis_run_sequence_u8`` on raw device pointers, asynchronous on `stream`: frames u8
+        [nframes, h, w, noc], pair i = (frame i, frame i + stride), outputs for nframes - stride pairs; every output
+        but the forward flow is optional (0), and so is the initial flow."""
+        check(lib().ofdis_run_sequence_u8(self._h, frames_ptr, nframes, stride, init_ptr or None, width, height,
+                                          C.byref(p), alpha, beta, fw_ptr or None, bw_ptr or None, occ_fw_ptr or None,
+                                          occ_bw_ptr or None, err_fw_ptr or None, err_bw_ptr or None, stream or None),
+              "ofdis_run_sequence_u8")
+
+    def run_sequence(self, frames, p: Params, stride: int = 1, init=None, bidir: bool = False, alpha: float = 0.01,
+                     beta: float = 0.5, want_err: bool = False):
+        """Flow along a video: torch.uint8 CUDA tensor [T, h, w] or [T, h, w, noc] -> the flow of the T - stride pairs
+        (frame i, frame i + stride), bit for bit ``run(frames[:-stride], frames[stride:])`` with every frame's
+        pyramid built once.  Returns the flow [T - stride, h, w, 2]; with ``bidir`` the tuple of ``run_bidir``
+        (flow_fw, flow_bw, occ_fw, occ_bw[, err_fw, err_bw]).  init: optional float32 CUDA tensor
+        [T - stride, h, w, 2] as in ``run`` (not together with ``bidir``).  Optical flow only."""
+        import torch
+        if frames.dim() == 3:
+            frames = frames.unsqueeze(-1)
+        t, h, w, noc = frames.shape
+        if noc != p.noc or frames.dtype != torch.uint8 or not frames.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor with noc channels")
+        n = t - stride
+        if stride < 1 or n < 1:
+            raise ValueError("a sequence needs stride >= 1 and more than `stride` frames")
+        frames = frames.contiguous()
+        if init is not None:
+            if tuple(init.shape) != (n, h, w, 2) or init.dtype != torch.float32 or not init.is_cuda:
+                raise ValueError("init must be a float32 CUDA tensor [T - stride, h, w, 2]")
+            init = init.contiguous()
+        flow = [torch.empty((n, h, w, 2), dtype=torch.float32, device=frames.device) for _ in range(2 if bidir else 1)]
+        occ = [torch.empty((n, h, w), dtype=torch.uint8, device=frames.device) for _ in range(2 if bidir else 0)]
+        err = [torch.empty((n, h, w), dtype=torch.float32, device=frames.device)
+               for _ in range(2 if bidir and want_err else 0)]
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        self.run_sequence_ptr(frames.data_ptr(), t, stride, w, h, p, flow[0].data_ptr(),
+                              init.data_ptr() if init is not None else 0, alpha, beta,
+                              flow[1].data_ptr() if bidir else 0, occ[0].data_ptr() if bidir else 0,
+                              occ[1].data_ptr() if bidir else 0, err[0].data_ptr() if err else 0,
+                              err[1].data_ptr() if err else 0, stream)
+        return tuple(flow + occ + err) if bidir else flow[0]
+
+    def run_sequence_host(self, frames: np.ndarray, p: Params, stride: int = 1, init: Optional[np.ndarray] = None,
+                          bidir: bool = False, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False):
+        """run_sequence on a numpy u8 array [T, h, w] or [T, h, w, noc]; synchronous."""
+        f4 = np.ascontiguousarray(frames[..., None] if frames.ndim == 3 else frames, np.uint8)
+        t, h, w = f4.shape[:3]
+        n = t - stride
+        if stride < 1 or n < 1:
+            raise ValueError("a sequence needs stride >= 1 and more than `stride` frames")
+        i4 = None if init is None else np.ascontiguousarray(init, _f32).reshape(n, h, w, 2)
+        flow = [np.empty((n, h, w, 2), _f32) for _ in range(2 if bidir else 1)]
+        occ = [np.empty((n, h, w), np.uint8) for _ in range(2 if bidir else 0)]
+        err = [np.empty((n, h, w), _f32) for _ in range(2 if bidir and want_err else 0)]
+        check(lib().ofdis_run_sequence_u8_host(self._h, f4.ctypes.data, t, stride,
+                                               None if i4 is None else i4.ctypes.data, w, h, C.byref(p), alpha, beta,
+                                               flow[0].ctypes.data, flow[1].ctypes.data if bidir else None,
+                                               occ[0].ctypes.data if bidir else None,
+                                               occ[1].ctypes.data if bidir else None,
+                                               err[0].ctypes.data if err else None,
+                                               err[1].ctypes.data if err else None), "ofdis_run_sequence_u8_host")
+        return tuple(flow + occ + err) if bidir else flow[0]
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
