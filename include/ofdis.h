@@ -221,6 +221,52 @@ int ofdis_run_sequence_u8_host(ofdis_context *ctx, const uint8_t *frames, int nf
                                float beta, float *flow_fw, float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw,
                                float *err_fw, float *err_bw);
 
+/* ------------------------------------------------------------------ compact output formats
+ *
+ * Not in the reference, whose one output is float32, interleaved, at full resolution (run_dense.cpp:407-415) -- the
+ * largest array a call moves.  A format names the element type, the layout and the grid of the forward flow:
+ *   dtype   F32, or F16: every float32 value converted to IEEE binary16, round to nearest even, overflow to +-inf,
+ *           subnormals kept;
+ *   layout  INTERLEAVED [n][H][W][nop], or PLANAR [n][nop][H][W] (the same values transposed; one layout when nop = 1);
+ *   grid    FULL: the plain call's width x height field.  LEVEL: the finest level's flow as the coarse-to-fine loop
+ *           leaves it (tv_flow[sc_l] of the stage capture; dis_flow[sc_l] with usetvref = 0 -- the values OFClass hands
+ *           to run_dense.cpp:387-401), multiplied by 2^sc_l, so every format is in full-resolution pixels.  No
+ *           upsample runs.  The level grid belongs to the divisibility-padded frame and is not cropped: cell (X, Y)
+ *           covers the original pixels [X * cell - off_x, (X + 1) * cell - off_x) x [Y * cell - off_y, ...).
+ * {F32, INTERLEAVED, FULL}, or a NULL format, is the plain call: the same launches. */
+enum { OFDIS_OUT_F32 = 0, OFDIS_OUT_F16 = 1 };             /* dtype  */
+enum { OFDIS_OUT_INTERLEAVED = 0, OFDIS_OUT_PLANAR = 1 };  /* layout */
+enum { OFDIS_OUT_FULL = 0, OFDIS_OUT_LEVEL = 1 };          /* grid   */
+typedef struct ofdis_out_format { int dtype, layout, grid; } ofdis_out_format;
+
+/* The output grid of one pair in format fmt (NULL = the plain format), host only.  FULL: out_w x out_h = width x
+ * height, offsets 0, cell 1.  LEVEL: out_w = Wp >> sc_l, out_h = Hp >> sc_l, cell = 2^sc_l, off_x = floor(padw / 2),
+ * off_y = floor(padh / 2), where Wp = width + padw and Hp = height + padh are the sizes padded to a multiple of 2^sc_f,
+ * or of 2^(sc_f+1) when with_init (run_dense.cpp:299-312).  bytes_per_pair = out_w * out_h * nop * element size.  Any
+ * output pointer may be NULL.  Invalid parameters, sizes or enum values return OFDIS_ERR_INVALID_ARGUMENT. */
+int ofdis_out_geometry(const ofdis_params *p, int width, int height, int with_init, const ofdis_out_format *fmt,
+                       int *out_w, int *out_h, int *off_x, int *off_y, int *cell, size_t *bytes_per_pair);
+
+/* ofdis_run_batch_u8_init writing flow_out in format fmt: n * bytes_per_pair bytes, nothing beyond them.  Both modes.
+ * init_flow (or NULL) stays float32 [n][height][width][nop]; with it the level grid is the with_init one.  Stage
+ * capture, options, streams, chunks and graphs behave as in the plain call; the _host form ignores verbosity.
+ * Refusals before anything is enqueued: those of the plain call, an unknown enum value, and a frame of 2^31 pixels
+ * or more (OFDIS_ERR_INVALID_ARGUMENT). */
+int ofdis_run_batch_u8_fmt(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, const float *init_flow,
+                           int n, int width, int height, const ofdis_params *p, const ofdis_out_format *fmt,
+                           void *flow_out, void *stream);
+int ofdis_run_batch_u8_fmt_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, const float *init_flow,
+                                int n, int width, int height, const ofdis_params *p, const ofdis_out_format *fmt,
+                                void *flow_out);
+/* ofdis_run_sequence_u8's forward flow in format fmt (the backward flow, masks and errors are defined on float32
+ * fields and stay with ofdis_run_sequence_u8). */
+int ofdis_run_sequence_u8_fmt(ofdis_context *ctx, const uint8_t *frames, int nframes, int stride,
+                              const float *init_flow, int width, int height, const ofdis_params *p,
+                              const ofdis_out_format *fmt, void *flow_fw, void *stream);
+int ofdis_run_sequence_u8_fmt_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int stride,
+                                   const float *init_flow, int width, int height, const ofdis_params *p,
+                                   const ofdis_out_format *fmt, void *flow_fw);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -304,11 +350,12 @@ int ofdis_context_set_stage_capture(ofdis_context *ctx, float *const *dis_flow, 
  *                        summing |w| (the same decision; NaN and tiny terms redo the evaluation with the sum);
  *   "patch_generic" (0/1, default 0): every patch shape on the any-shape kernel (runtime value loops: the
  *                        default for p*p*noc > 448, e.g. RGB p >= 14, gray p >= 22);
- *   "nt_store" (0/1, default 0): write the full-resolution flow with non-temporal stores;
+ *   "nt_store" (0/1, default 0): write the full-resolution flow with non-temporal stores (the plain format);
  *   "up_form" (0..3, default 3): optical-flow upsample: 1 / 2 = each staged source row's horizontal taps once per
  *                        column for blocks of 4 / 8 output rows, 0 = once per output row that reads them (round 4),
  *                        3 = 1 on frames at least 1024 wide for calls on two or more streams or of fewer than
- *                        1024 pairs, else 0 (the faster of the two end to end in each measured regime);
+ *                        1024 pairs, else 0 (the faster of the two end to end in each measured regime); the other
+ *                        output formats have one store form each and ignore it;
  *   "graph" (0/1/2, default 1): replay a batch as one captured HIP graph while its pointers, sizes and
  *                        parameters repeat (re-captured when they change); 1 captures single-stream
  *                        batches, 2 also the multi-stream ones (chunks forked over lanes and joined);
@@ -332,10 +379,13 @@ int ofdis_context_enable_kernel_timing(ofdis_context *ctx, int enable);
 /* Accumulated device time (ms) and launch count for kernel `name` since timing was enabled. */
 int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *total_ms, long *launches);
 /* Comma-separated list of kernel names known to the timer.  The forward-backward check is timed as "fb_check"
- * when it writes masks only and as "fb_check_err" when it also writes an error map. */
+ * when it writes masks only and as "fb_check_err" when it also writes an error map; the upsample as "upsample" when
+ * it writes the plain format alone, else as "upsample_f16", "upsample_planar" or "upsample_planar_f16", and the
+ * level-grid output that replaces it as "level_out". */
 const char *ofdis_kernel_names(void);
 
-/* Per-frame algorithmic byte counts of the §8(d) byte model for this workload. */
+/* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
+ * bytes written ("level_out": the float32 level plane read and a float32 write). */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */

@@ -25,6 +25,11 @@ ERR_IO = 6
 MODE_OF = 1
 MODE_DE = 2
 
+# ofdis_out_format (include/ofdis.h): element type, layout and grid of the forward flow
+OUT_F32, OUT_F16 = 0, 1
+OUT_INTERLEAVED, OUT_PLANAR = 0, 1
+OUT_FULL, OUT_LEVEL = 0, 1
+
 
 class OfdisError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
@@ -65,6 +70,23 @@ class Params(C.Structure):
         return "Params(" + ", ".join(f"{k}={v!r}" for k, v in self.as_dict().items()) + ")"
 
 
+class OutFormat(C.Structure):
+    """ofdis_out_format (include/ofdis.h)."""
+
+    _fields_ = [("dtype", C.c_int), ("layout", C.c_int), ("grid", C.c_int)]
+
+
+def out_format(dtype="float32", layout="nhwc", grid="full") -> OutFormat:
+    """OutFormat from the Python spellings: dtype float32 / float16 (a numpy or torch dtype, or its name), layout
+    "nhwc" (interleaved) / "nchw" (planar), grid "full" / "level".  Anything else raises OfdisError(INVALID_ARGUMENT)."""
+    name = str(getattr(dtype, "__name__", dtype)).replace("torch.", "")
+    try:
+        return OutFormat({"float32": OUT_F32, "float16": OUT_F16, "half": OUT_F16, "float": OUT_F32}[name],
+                         {"nhwc": OUT_INTERLEAVED, "nchw": OUT_PLANAR}[layout], {"full": OUT_FULL, "level": OUT_LEVEL}[grid])
+    except (KeyError, TypeError):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"output format ({dtype!r}, {layout!r}, {grid!r})") from None
+
+
 def build(verbose: bool = False) -> None:
     """Compile libofdis.so (+ CLI binaries) for gfx950 with hipcc, in-tree."""
     jobs = os.environ.get("MAX_JOBS", "4")
@@ -90,6 +112,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     P = C.POINTER(Params)
+    F = C.POINTER(OutFormat)
     sig = {
         "ofdis_abi_version": ([], i),
         "ofdis_status_string": ([i], C.c_char_p),
@@ -109,6 +132,11 @@ def lib():
         "ofdis_run_bidir_u8_host": ([vp, vp, vp, i, i, i, P, f, f, vp, vp, vp, vp, vp, vp], i),
         "ofdis_run_sequence_u8": ([vp, vp, i, i, vp, i, i, P, f, f, vp, vp, vp, vp, vp, vp, vp], i),
         "ofdis_run_sequence_u8_host": ([vp, vp, i, i, vp, i, i, P, f, f, vp, vp, vp, vp, vp, vp], i),
+        "ofdis_out_geometry": ([P, i, i, i, F] + [C.POINTER(i)] * 5 + [C.POINTER(C.c_size_t)], i),
+        "ofdis_run_batch_u8_fmt": ([vp, vp, vp, vp, i, i, i, P, F, vp, vp], i),
+        "ofdis_run_batch_u8_fmt_host": ([vp, vp, vp, vp, i, i, i, P, F, vp], i),
+        "ofdis_run_sequence_u8_fmt": ([vp, vp, i, i, vp, i, i, P, F, vp, vp], i),
+        "ofdis_run_sequence_u8_fmt_host": ([vp, vp, i, i, vp, i, i, P, F, vp], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),
         "ofdis_context_set_option": ([vp, C.c_char_p, i], i),

@@ -121,6 +121,33 @@ int ofdis_params_validate(const ofdis_params *p, int width, int height, int imgp
   return OFDIS_OK;
 }
 
+// The output grid of one pair in a format (include/ofdis.h); the padding rules are run_dense.cpp:299-312.
+int ofdis_out_geometry(const ofdis_params *p, int width, int height, int with_init, const ofdis_out_format *fmt,
+                       int *out_w, int *out_h, int *off_x, int *off_y, int *cell, size_t *bytes_per_pair) {
+  static const ofdis_out_format plain = {OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_FULL};
+  if (!fmt) fmt = &plain;
+  int rc = ofdis_params_validate(p, -1, -1, -1);
+  if (rc) return rc;
+  if (width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
+  if (fmt->dtype != OFDIS_OUT_F32 && fmt->dtype != OFDIS_OUT_F16) return OFDIS_ERR_INVALID_ARGUMENT;
+  if (fmt->layout != OFDIS_OUT_INTERLEAVED && fmt->layout != OFDIS_OUT_PLANAR) return OFDIS_ERR_INVALID_ARGUMENT;
+  if (fmt->grid != OFDIS_OUT_FULL && fmt->grid != OFDIS_OUT_LEVEL) return OFDIS_ERR_INVALID_ARGUMENT;
+  const long d = 1L << (p->sc_f + (with_init ? 1 : 0));
+  const long padw = (width % d) ? d - width % d : 0, padh = (height % d) ? d - height % d : 0;
+  if (width + padw > 0x7fffffffL || height + padh > 0x7fffffffL) return OFDIS_ERR_INVALID_ARGUMENT;
+  const bool level = fmt->grid == OFDIS_OUT_LEVEL;
+  const int ow = level ? (int)((width + padw) >> p->sc_l) : width;
+  const int oh = level ? (int)((height + padh) >> p->sc_l) : height;
+  if (out_w) *out_w = ow;
+  if (out_h) *out_h = oh;
+  if (off_x) *off_x = level ? (int)(padw / 2) : 0;
+  if (off_y) *off_y = level ? (int)(padh / 2) : 0;
+  if (cell) *cell = level ? 1 << p->sc_l : 1;
+  if (bytes_per_pair)
+    *bytes_per_pair = (size_t)ow * oh * (p->mode == OFDIS_MODE_OF ? 2 : 1) * (fmt->dtype == OFDIS_OUT_F16 ? 2 : 4);
+  return OFDIS_OK;
+}
+
 // ------------------------------------------------------------------------------------ files
 
 int ofdis_write_flo(const char *path, const float *flow, int width, int height, int nc) {

@@ -151,6 +151,16 @@ struct UpArgs {
   int n, nop, wl, hl, log2s, W0, H0, offx, offy;
   int nt_store;       // non-temporal output stores (A/B option "nt_store")
   int form;           // nop = 2: 0 k_upsample_rows, 1 k_upsample_h<4>, 2 k_upsample_h<8> (option "up_form")
+  int f16, planar;    // output format (ofdis_out_format): `out` holds binary16 values / is [n][nop][H0][W0].  Either set:
+                      // one store form per nop whatever `form` (k_upsample_h<4>, k_upsample_rows1, k_upsample)
+};
+
+// The finest level's flow x 2^sc_l in an output format, no upsample (ofdis_out_format, OFDIS_OUT_LEVEL).
+struct LevelOutArgs {
+  const float *flow;  // planar [n][nop][hl][wl]
+  void *out;          // float or binary16, [n][hl][wl][nop] or [n][nop][hl][wl]
+  int n, nop, wl, hl, log2s;
+  int f16, planar;
 };
 
 // Initial flow (run_dense.cpp:356-379): full-resolution [n][H0][W0][nop] -> replicate-padded, x sc,
@@ -196,5 +206,6 @@ bool tv_level_rb_ok(const TvArgs &a);  // ofdis_tvrb.hip
 void launch_tv_level_rb(const TvArgs &a, int n_inner, hipStream_t s);
 void launch_tv_final(const TvArgs &a, hipStream_t s);
 void launch_upsample(const UpArgs &a, hipStream_t s);
+void launch_level_out(const LevelOutArgs &a, hipStream_t s);
 
 }  // namespace ofdis

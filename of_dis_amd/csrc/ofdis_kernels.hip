@@ -29,6 +29,7 @@
 //                k_tv_sor_lanes<S, MODE, NB, MAXT, CRING, R, CG, SEL>  exact order, one wave per sweep and row group
 //                k_tv_final<TH>      refine_variational.cpp:209-227,305-323
 //   output       k_upsample, k_upsample_rows, k_upsample_h<R>, k_upsample_rows1  run_dense.cpp:407-415
+//                (<T, PLANAR>: the float16 / planar output formats), k_level_out  (ofdis_out_format)
 //   fb check     k_fb_check<OCC, ERR, PX>  forward-backward consistency masks of two flow fields (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
@@ -5049,6 +5050,24 @@ constexpr int kUpCols = 1024;
 constexpr int kUpRows = 4;
 constexpr int kUpSrcRows = kUpRows / 2 + 3;  // source rows a block can touch (2^l >= 2)
 typedef float v4f __attribute__((ext_vector_type(4)));
+
+// Output formats (ofdis_out_format).  The kernels below compute every output value in float32 exactly as the plain
+// format's store receives it; a format changes only the element type T (float, or _Float16 through out_cvt) and the
+// layout (PLANAR: [n][nop][H][W]) of the final store.  <float, false> is the plain format: the code it had before the
+// formats existed.
+typedef _Float16 v2h __attribute__((ext_vector_type(2)));
+typedef _Float16 v4h __attribute__((ext_vector_type(4)));
+typedef _Float16 v8h __attribute__((ext_vector_type(8)));
+// The one conversion to the output element type.  To binary16: the plain C++ conversion, i.e. v_cvt_f16_f32 in the
+// default rounding mode -- round to nearest even, overflow to +-inf, subnormal results kept -- never a packed
+// round-toward-zero form.
+template <class T>
+__device__ __forceinline__ T out_cvt(float x) {
+  return (T)x;
+}
+template <class T, bool PLANAR>
+constexpr bool kPlainOut = std::is_same<T, float>::value && !PLANAR;
+
 __global__ __launch_bounds__(256) void k_upsample_rows(UpArgs a) {
   __shared__ float src[kUpSrcRows][2][kUpCols / 2 + 8];  // [row][comp][col]
   const int y0 = blockIdx.y * kUpRows, f = blockIdx.z;
@@ -5147,8 +5166,17 @@ __global__ __launch_bounds__(256) void k_upsample_rows(UpArgs a) {
 // horizontal evaluations before), and the staging copy in 16-byte groups with no per-element division:
 // B's upsample issued ~500 VALU per wave, 43 % of the whole pipeline's VALU (profiles/r05/s9).  R output rows
 // per block (4 or 8).  The staged window starts at the 4-aligned column below the first one the block reads.
-template <int R>
+//
+// Formats other than the plain one (T, PLANAR; R = 4 only): lane i of wave wv owns the four consecutive columns
+// xb + 4i .. 4i + 3 (xb = block + 256 wv) instead of two column pairs 128 apart -- a column's taps and value do not
+// depend on the lane that computes it -- so that every store is one contiguous piece per lane and per wave: binary16
+// interleaved 16 bytes per lane (1 KiB per wave instruction), float32 planar 16 bytes per component, binary16 planar
+// 8 bytes per component (512 bytes per wave instruction: whole 128-byte lines).  launch_upsample takes this kernel
+// only when W0 % 4 == 0 and the output is 16-byte aligned, which aligns each of these stores to its own size and
+// leaves no partial group of columns.
+template <int R, class T = float, bool PLANAR = false>
 __global__ __launch_bounds__(256) void k_upsample_h(UpArgs a) {
+  constexpr bool PLAIN = kPlainOut<T, PLANAR>;
   constexpr int NSR = R / 2 + 3;         // source rows a block can touch (2^l >= 2)
   constexpr int SC = kUpCols / 2 + 8;    // staged columns per row (>= the 514 + 3 a block reads at 2^l = 2)
   constexpr int S4 = SC / 4;             // 16-byte groups per staged row
@@ -5190,8 +5218,8 @@ __global__ __launch_bounds__(256) void k_upsample_h(UpArgs a) {
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int xb = blockIdx.x * kUpCols + wv * 256 + 2 * lane;
-  int xs[2] = {xb, xb + 128};
+  const int xb = blockIdx.x * kUpCols + wv * 256 + (PLAIN ? 2 : 4) * lane;
+  int xs[2] = {xb, xb + (PLAIN ? 128 : 2)};
   int cc[4];
   float fxs[4], gxs[4];
   bool lin[4];
@@ -5252,19 +5280,39 @@ __global__ __launch_bounds__(256) void k_upsample_h(UpArgs a) {
     float v[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) v[t] = ha[t] * b0 + hb[t] * b1;
-    float *orow = a.out + ((long)f * a.H0 + y) * a.W0 * 2;
+    if constexpr (PLAIN) {
+      float *orow = a.out + ((long)f * a.H0 + y) * a.W0 * 2;
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int x = xs[hh];
-      if (x + 2 <= a.W0) {
-        const v4f val = v4f{v[4 * hh], v[4 * hh + 1], v[4 * hh + 2], v[4 * hh + 3]};
-        if (a.nt_store)
-          __builtin_nontemporal_store(val, reinterpret_cast<v4f *>(orow + 2 * x));
-        else
-          *reinterpret_cast<v4f *>(orow + 2 * x) = val;
-      } else if (x < a.W0) {
-        orow[2 * x] = v[4 * hh];
-        orow[2 * x + 1] = v[4 * hh + 1];
+      for (int hh = 0; hh < 2; ++hh) {
+        const int x = xs[hh];
+        if (x + 2 <= a.W0) {
+          const v4f val = v4f{v[4 * hh], v[4 * hh + 1], v[4 * hh + 2], v[4 * hh + 3]};
+          if (a.nt_store)
+            __builtin_nontemporal_store(val, reinterpret_cast<v4f *>(orow + 2 * x));
+          else
+            *reinterpret_cast<v4f *>(orow + 2 * x) = val;
+        } else if (x < a.W0) {
+          orow[2 * x] = v[4 * hh];
+          orow[2 * x + 1] = v[4 * hh + 1];
+        }
+      }
+    } else if (xb < a.W0) {  // v[2 q + k]: column xb + q, component k; W0 % 4 == 0: all four columns are inside
+      T *O = reinterpret_cast<T *>(a.out);
+      if constexpr (PLANAR) {
+        const long pl = (long)a.H0 * a.W0;
+        T *o0 = O + ((long)f * 2 * a.H0 + y) * a.W0 + xb;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          if constexpr (std::is_same<T, float>::value)
+            *reinterpret_cast<v4f *>(o0 + k * pl) = v4f{v[k], v[2 + k], v[4 + k], v[6 + k]};
+          else
+            *reinterpret_cast<v4h *>(o0 + k * pl) =
+                v4h{out_cvt<T>(v[k]), out_cvt<T>(v[2 + k]), out_cvt<T>(v[4 + k]), out_cvt<T>(v[6 + k])};
+        }
+      } else {  // binary16 interleaved
+        *reinterpret_cast<v8h *>(O + (((long)f * a.H0 + y) * a.W0 + xb) * 2) =
+            v8h{out_cvt<T>(v[0]), out_cvt<T>(v[1]), out_cvt<T>(v[2]), out_cvt<T>(v[3]),
+                out_cvt<T>(v[4]), out_cvt<T>(v[5]), out_cvt<T>(v[6]), out_cvt<T>(v[7])};
       }
     }
   }
@@ -5272,6 +5320,7 @@ __global__ __launch_bounds__(256) void k_upsample_h(UpArgs a) {
 
 // The same for depth (nop = 1): lane i of wave wv owns the four output columns xb + 4i .. xb + 4i + 3
 // (xb = block + 256 wv): one 16-byte store per row, 1 KiB contiguous per wave-instruction.
+template <class T = float>
 __global__ __launch_bounds__(256) void k_upsample_rows1(UpArgs a) {
   __shared__ float src[kUpSrcRows][kUpCols / 2 + 8];
   const int y0 = blockIdx.y * kUpRows, f = blockIdx.z;
@@ -5336,28 +5385,48 @@ __global__ __launch_bounds__(256) void k_upsample_rows1(UpArgs a) {
       const float h1 = lin[q] ? s10 * (1.f - fxs[q]) + src[j1][c + 1] * fxs[q] : s10;
       v[q] = h0 * b0 + h1 * b1;
     }
-    float *row = a.out + ((long)f * a.H0 + y) * a.W0;
+    T *row = reinterpret_cast<T *>(a.out) + ((long)f * a.H0 + y) * a.W0;
     if (xb + 4 <= a.W0) {
-      *reinterpret_cast<v4f *>(row + xb) = v4f{v[0], v[1], v[2], v[3]};
+      if constexpr (std::is_same<T, float>::value)
+        *reinterpret_cast<v4f *>(row + xb) = v4f{v[0], v[1], v[2], v[3]};
+      else  // binary16: 8 bytes per lane, 512 contiguous bytes per wave instruction
+        *reinterpret_cast<v4h *>(row + xb) = v4h{out_cvt<T>(v[0]), out_cvt<T>(v[1]), out_cvt<T>(v[2]), out_cvt<T>(v[3])};
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        if (xb + q < a.W0) row[xb + q] = v[q];
+        if (xb + q < a.W0) row[xb + q] = out_cvt<T>(v[q]);
     }
   }
 }
 
-// Generic path (any nop, 2^l = 1, unaligned output): one output pixel per thread.
+// Generic path (any nop, 2^l = 1, unaligned output): one output pixel per thread.  Formats: T and PLANAR as above;
+// PAIR (binary16, interleaved, nop = 2, output 4-byte aligned): the pixel's two components in one 4-byte store.  A
+// planar binary16 row of an odd-width frame starts 2-byte aligned on every other row: 2-byte stores.
+template <class T = float, bool PLANAR = false, bool PAIR = false>
 __global__ __launch_bounds__(256) void k_upsample(UpArgs a) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
   if (x >= a.W0) return;
   const long plane = (long)a.wl * a.hl;
   const float *F = a.flow + (long)f * a.nop * plane;
-  float *out = a.out + (((long)f * a.H0 + y) * a.W0 + x) * a.nop;
+  T *O = reinterpret_cast<T *>(a.out);
+  T *out = PLANAR ? O + ((long)f * a.nop * a.H0 + y) * a.W0 + x : O + (((long)f * a.H0 + y) * a.W0 + x) * a.nop;
+  const long ks = PLANAR ? (long)a.H0 * a.W0 : 1;  // component stride
+  auto put = [&](float r0, float r1) {             // r1 unused when nop = 1
+    if constexpr (PAIR) {
+      *reinterpret_cast<v2h *>(out) = v2h{out_cvt<T>(r0), out_cvt<T>(r1)};
+    } else {
+      out[0] = out_cvt<T>(r0);
+      if (a.nop == 2) out[ks] = out_cvt<T>(r1);
+    }
+  };
   if (a.log2s == 0) {
     const long o = (long)(y + a.offy) * a.wl + (x + a.offx);
-    out[0] = F[o];
-    if (a.nop == 2) out[1] = F[plane + o];
+    if constexpr (kPlainOut<T, PLANAR>) {
+      out[0] = F[o];
+      if (a.nop == 2) out[1] = F[plane + o];
+    } else {
+      put(F[o], a.nop == 2 ? F[plane + o] : 0.f);
+    }
     return;
   }
   const float fct = (float)(1 << a.log2s);
@@ -5370,12 +5439,89 @@ __global__ __launch_bounds__(256) void k_upsample(UpArgs a) {
   const long r1 = (long)(sy + 1 >= 0 ? (sy + 1 < a.hl ? sy + 1 : a.hl - 1) : 0) * a.wl;
   const float b0 = 1.f - fy, b1 = fy;
   const XTap xt = xtap(x + a.offx, scale, a.wl);
-  for (int k = 0; k < a.nop; ++k) out[k] = up_px(F + k * plane, r0, r1, xt, fct, b0, b1);
+  if constexpr (kPlainOut<T, PLANAR>) {
+    for (int k = 0; k < a.nop; ++k) out[k] = up_px(F + k * plane, r0, r1, xt, fct, b0, b1);
+  } else {
+    const float v0 = up_px(F, r0, r1, xt, fct, b0, b1);
+    put(v0, a.nop == 2 ? up_px(F + plane, r0, r1, xt, fct, b0, b1) : 0.f);
+  }
+}
+
+// OFDIS_OUT_LEVEL: the finest level's flow x 2^sc_l (exact) in the output format, one level pixel per thread.  65 KB
+// per pair at 1920 x 1080 op-point 2 where the upsample writes 16.6 MB: nothing here is worth tuning.
+template <class T, bool PLANAR, bool PAIR>
+__global__ __launch_bounds__(256) void k_level_out(LevelOutArgs a) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
+  if (x >= a.wl) return;
+  const long plane = (long)a.wl * a.hl, o = (long)y * a.wl + x;
+  const float *F = a.flow + (long)f * a.nop * plane + o;
+  const float fct = (float)(1 << a.log2s);
+  T *O = reinterpret_cast<T *>(a.out);
+  T *out = PLANAR ? O + (long)f * a.nop * plane + o : O + ((long)f * plane + o) * a.nop;
+  const long ks = PLANAR ? plane : 1;
+  const float r0 = F[0] * fct, r1 = a.nop == 2 ? F[plane] * fct : 0.f;
+  if constexpr (PAIR) {
+    *reinterpret_cast<v2h *>(out) = v2h{out_cvt<T>(r0), out_cvt<T>(r1)};
+  } else {
+    out[0] = out_cvt<T>(r0);
+    if (a.nop == 2) out[ks] = out_cvt<T>(r1);
+  }
 }
 
 }  // namespace
 // ---- launch
+namespace {
+// The formats' store forms, one per nop.  The vector forms need what the plain ones need -- W0 % 4 == 0
+// and a 16-byte aligned output, which aligns every row (and plane) start to the lane's store size in each format --
+// else the one-pixel-per-thread kernel stores element by element.
+template <class T, bool PLANAR>
+void launch_upsample_fmt(const UpArgs &a, hipStream_t s) {
+  const bool tiled = a.log2s >= 1 && a.log2s <= 9 && (a.W0 % 4) == 0 && ((uintptr_t)a.out % 16) == 0;
+  if (a.nop == 2 && tiled)
+    k_upsample_h<4, T, PLANAR><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, 4), a.n), 256, 0, s>>>(a);
+  else if (a.nop == 1 && tiled)
+    k_upsample_rows1<T><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, kUpRows), a.n), 256, 0, s>>>(a);
+  else {
+    const dim3 grid(ceil_div(a.W0, 256), a.H0, a.n);
+    if constexpr (!PLANAR && !std::is_same<T, float>::value) {
+      if (a.nop == 2 && ((uintptr_t)a.out % 4) == 0) {
+        k_upsample<T, false, true><<<grid, 256, 0, s>>>(a);
+        return;
+      }
+    }
+    k_upsample<T, PLANAR, false><<<grid, 256, 0, s>>>(a);
+  }
+}
+template <class T, bool PLANAR>
+void launch_level_out_fmt(const LevelOutArgs &a, hipStream_t s) {
+  const dim3 grid(ceil_div(a.wl, 256), a.hl, a.n);
+  if constexpr (!PLANAR && !std::is_same<T, float>::value) {
+    if (a.nop == 2 && ((uintptr_t)a.out % 4) == 0) {
+      k_level_out<T, false, true><<<grid, 256, 0, s>>>(a);
+      return;
+    }
+  }
+  k_level_out<T, PLANAR, false><<<grid, 256, 0, s>>>(a);
+}
+}  // namespace
+
+void launch_level_out(const LevelOutArgs &a, hipStream_t s) {
+  const bool planar = a.planar && a.nop == 2;  // one component: the layouts coincide
+  if (a.f16)
+    planar ? launch_level_out_fmt<_Float16, true>(a, s) : launch_level_out_fmt<_Float16, false>(a, s);
+  else
+    planar ? launch_level_out_fmt<float, true>(a, s) : launch_level_out_fmt<float, false>(a, s);
+}
+
 void launch_upsample(const UpArgs &a, hipStream_t s) {
+  if (a.f16 || (a.planar && a.nop == 2)) {
+    const bool planar = a.planar && a.nop == 2;
+    if (a.f16)
+      planar ? launch_upsample_fmt<_Float16, true>(a, s) : launch_upsample_fmt<_Float16, false>(a, s);
+    else
+      launch_upsample_fmt<float, true>(a, s);
+    return;
+  }
   if (a.nop == 2 && a.log2s >= 1 && a.log2s <= 9 && (a.W0 % 4) == 0 && ((uintptr_t)a.out % 16) == 0) {
     if (a.form == 2)
       k_upsample_h<8><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, 8), a.n), 256, 0, s>>>(a);

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -27,7 +28,16 @@ namespace {
 
 const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "patch",    "aggregate", "tv_prep",
                                     "tv_deriv", "tv_system", "tv_sor",       "tv_final", "upsample",  "tv_level",
-                                    "fb_check", "fb_check_err"};
+                                    "fb_check", "fb_check_err",
+                                    // the upsample writing an output format other than the plain one, and the
+                                    // level-grid output that replaces it ("upsample": the plain format alone)
+                                    "upsample_f16", "upsample_planar", "upsample_planar_f16", "level_out"};
+
+// Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
+struct OutFmt {
+  int f16 = 0, planar = 0, level = 0;
+  bool plain() const { return !f16 && !planar && !level; }
+};
 
 struct Plan {
   // n pairs over nfr pyramid frames, frame b of pair f lying bdist frames after its frame a: two arrays of n frames
@@ -85,6 +95,8 @@ struct ofdis_context {
     float alpha = 0.f, beta = 0.f;  // the bidirectional call's extra outputs and thresholds
     int bidir = 0;
     int seq = 0, stride = 0;  // ofdis_run_sequence_u8: `a` is one array of n + stride frames, b is NULL
+    int out_f16 = 0, out_planar = 0, out_level = 0;  // output format: a formatted call on a plain call's buffers
+                                                     // records anew, and the other way round
     int n = 0, w = 0, h = 0;
     ofdis_params p{};
   } gkey;
@@ -812,11 +824,27 @@ void ofdis_context_destroy(ofdis_context *c) {
 namespace {
 
 // x 2^sc_l + INTER_LINEAR upsample + crop of the finest level's flow in workspace ws (run_dense.cpp:407-415).
-int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, float *flow_out, hipStream_t s,
-                 bool backward = false) {
+// A format other than the plain one (never with `backward`): the formatted store forms, or for the level grid no
+// upsample at all -- the level plane x 2^sc_l in the format.
+int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, void *flow_out, hipStream_t s,
+                 bool backward = false, const OutFmt &fmt = OutFmt()) {
+  if (fmt.level) {
+    LevelOutArgs lo{};
+    lo.flow = (const float *)(ws + P.off_flow[0]);
+    lo.out = flow_out;
+    lo.n = P.n;
+    lo.nop = P.nop;
+    lo.wl = P.lv[0].w;
+    lo.hl = P.lv[0].h;
+    lo.log2s = p->sc_l;
+    lo.f16 = fmt.f16;
+    lo.planar = fmt.planar;
+    timed(c, 17, s, [&] { launch_level_out(lo, s); });
+    return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+  }
   UpArgs up{};
   up.flow = (const float *)(ws + (backward ? P.off_flow_bw[0] : P.off_flow[0]));
-  up.out = flow_out;
+  up.out = (float *)flow_out;
   up.n = P.n;
   up.nop = P.nop;
   up.wl = P.lv[0].w;
@@ -829,7 +857,9 @@ int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *
   up.nt_store = c->opt_nt_store;
   up.form = c->opt_up_form == 3 ? (P.W0 >= 1024 && (c->call_lanes >= 2 || c->call_frames < 1024) ? 1 : 0)
                                  : c->opt_up_form;
-  timed(c, 10, s, [&] { launch_upsample(up, s); });
+  up.f16 = fmt.f16;
+  up.planar = fmt.planar;
+  timed(c, fmt.f16 ? (fmt.planar ? 16 : 14) : fmt.planar ? 15 : 10, s, [&] { launch_upsample(up, s); });
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
@@ -894,17 +924,18 @@ int run_fb_check(ofdis_context *c, const float *fw, const float *bw, int n, int 
 // One chunk of frames through the whole pipeline on stream s with workspace ws.  bd (P.bidir): the backward flow
 // of the same pyramid upsampled too -- into the workspace when the caller wants only the masks -- and the check.
 int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
-              const uint8_t *img_b, const float *init, float *flow_out, const BidirOut *bd, hipStream_t s) {
+              const uint8_t *img_b, const float *init, void *flow_out, const BidirOut *bd, hipStream_t s,
+              const OutFmt &fmt) {
   int rc = run_pyramid(c, ws, P, img_a, img_b, s);
   if (rc) return rc;
   if (init && (rc = run_init(c, ws, P, p, init, s))) return rc;
   rc = run_levels(c, ws, P, p, s, init ? (const float *)(ws + P.off_init) : nullptr, nullptr);
   if (rc) return rc;
-  rc = run_upsample(c, ws, P, p, flow_out, s);
-  if (rc || !bd) return rc;
+  rc = run_upsample(c, ws, P, p, flow_out, s, false, fmt);
+  if (rc || !bd) return rc;  // (bd: the plain format, float32 fields)
   float *flow_bw = bd->flow_bw ? bd->flow_bw : (float *)(ws + P.off_up_bw);
   if ((rc = run_upsample(c, ws, P, p, flow_bw, s, true))) return rc;
-  return bd->checks() ? run_fb_check(c, flow_out, flow_bw, P.n, P.W0, P.H0, *bd, s) : OFDIS_OK;
+  return bd->checks() ? run_fb_check(c, (const float *)flow_out, flow_bw, P.n, P.W0, P.H0, *bd, s) : OFDIS_OK;
 }
 
 // k lanes (stream, done event, workspace of `bytes`).
@@ -951,6 +982,7 @@ struct CallPlan {
   enum Kind { kSingle, kRoundRobin } kind = kSingle;
   int n = 0, width = 0, height = 0, chunk = 0, nchunks = 1, lanes = 0;
   bool init = false;
+  size_t out_pair = 0;      // bytes of one pair's output in the call's format
   Plan whole;               // kSingle
   std::vector<Plan> parts;  // kRoundRobin: one plan per chunk
 };
@@ -989,8 +1021,8 @@ int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int heigh
 // A sequence call (img_b NULL): the chunk of m pairs from pair f0 reads frames [f0, f0 + m + stride) of the caller's
 // array, so neighbouring chunks rebuild the `stride` frames they share; the outputs are per pair as ever.
 int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p,
-                      const uint8_t *img_a, const uint8_t *img_b, const float *init, float *flow_out,
-                      const BidirOut *bd) {
+                      const uint8_t *img_a, const uint8_t *img_b, const float *init, void *flow_out,
+                      const BidirOut *bd, const OutFmt &fmt) {
   const int k = cp.lanes;
   HIP_OK(hipEventRecord(c->entry, s));
   for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
@@ -1001,7 +1033,8 @@ int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const
     auto &L = c->lanes[ch % k];
     const BidirOut part = bd ? bd->at(f0, (size_t)cp.width * cp.height) : BidirOut();
     int rc = run_chunk(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b ? img_b + f0 * in_frame : nullptr,
-                       init ? init + f0 * out_frame : nullptr, flow_out + f0 * out_frame, bd ? &part : nullptr, L.s);
+                       init ? init + f0 * out_frame : nullptr, (char *)flow_out + f0 * cp.out_pair,
+                       bd ? &part : nullptr, L.s, fmt);
     if (rc) return rc;
   }
   for (int i = 0; i < k; ++i) {
@@ -1012,10 +1045,10 @@ int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const
 }
 
 int issue(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *img_a,
-          const uint8_t *img_b, const float *init, float *flow_out, const BidirOut *bd) {
+          const uint8_t *img_b, const float *init, void *flow_out, const BidirOut *bd, const OutFmt &fmt) {
   switch (cp.kind) {
-    case CallPlan::kRoundRobin: return issue_round_robin(c, cp, s, p, img_a, img_b, init, flow_out, bd);
-    default: return run_chunk(c, c->ws, cp.whole, p, img_a, img_b, init, flow_out, bd, s);
+    case CallPlan::kRoundRobin: return issue_round_robin(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt);
+    default: return run_chunk(c, c->ws, cp.whole, p, img_a, img_b, init, flow_out, bd, s, fmt);
   }
 }
 
@@ -1055,16 +1088,21 @@ int validate_call(const ofdis_params *p, int width, int height, bool init) {
 // The whole-batch device path on stream s (call ordering done by the caller).  stride > 0: img_a is a sequence of
 // n + stride frames and pair i is (frame i, frame i + stride); img_b is NULL.
 int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
-              int width, int height, const ofdis_params *p, float *flow_out, const BidirOut *bd = nullptr,
-              int stride = 0) {
+              int width, int height, const ofdis_params *p, void *flow_out, const BidirOut *bd = nullptr,
+              int stride = 0, const OutFmt &fmt = OutFmt()) {
   const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
   CallPlan cp;
   int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, bd ? (bd->flow_bw ? 1 : 2) : 0, stride);
   if (rc) return rc;
+  {  // a chunk of m pairs from pair f0 writes the bytes [f0, f0 + m) * out_pair of flow_out
+    const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
+    const size_t cells = fmt.level ? (size_t)P1.lv[0].w * P1.lv[0].h : (size_t)width * height;
+    cp.out_pair = cells * P1.nop * (fmt.f16 ? 2 : 4);
+  }
   OFDIS_TRACE("run_batch: kind %d, %d chunks of %d, %d lanes", (int)cp.kind, cp.nchunks, cp.chunk, cp.lanes);
   // graph 1: capture single-stream batches; graph 2: also the multi-lane (fork / join) issues
   const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
-  if (!graph || capturing || c->timing) return issue(c, cp, s, p, img_a, img_b, init, flow_out, bd);
+  if (!graph || capturing || c->timing) return issue(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt);
   // ~80 dependent launches per chunk: record them once as a HIP graph (on the context's own stream -- the
   // caller's may be the legacy NULL stream, which cannot capture) and replay it on the caller's stream while
   // the pointers, sizes, parameters and options stay the same (set_option drops the graph).  Multi-lane
@@ -1074,6 +1112,7 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
   key.a = img_a; key.b = img_b; key.out = flow_out; key.ws = c->ws; key.init = init;
   key.n = n; key.w = width; key.h = height; key.p = *p;
   key.seq = stride > 0; key.stride = stride;  // a sequence call on a plain call's buffers records anew
+  key.out_f16 = fmt.f16; key.out_planar = fmt.planar; key.out_level = fmt.level;
   if (bd) {  // a plain call after a bidirectional one on the same buffers records anew, and the other way round
     key.bidir = 1; key.flow_bw = bd->flow_bw; key.occ_fw = bd->occ_fw; key.occ_bw = bd->occ_bw;
     key.err_fw = bd->err_fw; key.err_bw = bd->err_bw; key.alpha = bd->alpha; key.beta = bd->beta;
@@ -1082,7 +1121,7 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
     if ((rc = drop_graph(c))) return rc;
     OFDIS_TRACE("graph: capture (kind %d, %d chunks of %d)", (int)cp.kind, cp.nchunks, cp.chunk);
     HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = issue(c, cp, c->stream, p, img_a, img_b, init, flow_out, bd);
+    rc = issue(c, cp, c->stream, p, img_a, img_b, init, flow_out, bd, fmt);
     OFDIS_TRACE("graph: issued rc %d", rc);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
@@ -1395,6 +1434,130 @@ int ofdis_run_sequence_u8_host(ofdis_context *c, const uint8_t *frames, int nfra
   return rc;
 }
 
+// ------------------------------------------------------------------ output formats (include/ofdis.h)
+
+namespace {
+// fmt (NULL: the plain format) checked and restated; bytes: one pair's output.  With one component the two layouts
+// are one: planar is dropped, so {F32, PLANAR, FULL} of a depth call is the plain call.  The formatted kernels index
+// with 64-bit offsets; frames of 2^31 pixels or more are refused all the same (as ofdis_fb_check does), so that a
+// pixel index within a plane always fits an int.
+int out_format(const ofdis_params *p, int width, int height, bool init, const ofdis_out_format *fmt, OutFmt &of,
+               size_t &bytes) {
+  const int rc = ofdis_out_geometry(p, width, height, init, fmt, nullptr, nullptr, nullptr, nullptr, nullptr, &bytes);
+  if (rc) return rc;
+  of = OutFmt();
+  if (!fmt) return OFDIS_OK;
+  of.f16 = fmt->dtype == OFDIS_OUT_F16;
+  of.planar = fmt->layout == OFDIS_OUT_PLANAR && p->mode == OFDIS_MODE_OF;
+  of.level = fmt->grid == OFDIS_OUT_LEVEL;
+  if (!of.plain() && (long)width * height > 0x7fffffffL) return OFDIS_ERR_INVALID_ARGUMENT;
+  return OFDIS_OK;
+}
+}  // namespace
+
+int ofdis_run_batch_u8_fmt(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
+                           int width, int height, const ofdis_params *p, const ofdis_out_format *fmt, void *flow_out,
+                           void *stream) {
+  if (!c || !img_a || !img_b || !flow_out || n <= 0 || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
+  OutFmt of;
+  size_t bytes = 0;
+  int rc = out_format(p, width, height, init != nullptr, fmt, of, bytes);
+  if (rc) return rc;
+  if (of.plain())  // the existing path and kernel instantiations
+    return ofdis_run_batch_u8_init(c, img_a, img_b, init, n, width, height, p, (float *)flow_out, stream);
+  if ((rc = validate_call(p, width, height, init != nullptr))) return rc;
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch(c, s, img_a, img_b, init, n, width, height, p, flow_out, nullptr, 0, of);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_sequence_u8_fmt(ofdis_context *c, const uint8_t *frames, int nframes, int stride, const float *init,
+                              int width, int height, const ofdis_params *p, const ofdis_out_format *fmt, void *flow_fw,
+                              void *stream) {
+  if (!c || !frames || !flow_fw || width <= 0 || height <= 0 || !p || stride < 1 || nframes <= stride)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  OutFmt of;
+  size_t bytes = 0;
+  int rc = out_format(p, width, height, init != nullptr, fmt, of, bytes);
+  if (rc) return rc;
+  if (of.plain())
+    return ofdis_run_sequence_u8(c, frames, nframes, stride, init, width, height, p, 0.f, 0.f, (float *)flow_fw,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  if ((rc = validate_call(p, width, height, init != nullptr))) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch(c, s, frames, nullptr, init, nframes - stride, width, height, p, flow_fw, nullptr, stride, of);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+namespace {
+// The host forms: frames (two arrays of nfr frames, or one when img_b is NULL) and the initial flow of n pairs up,
+// the device call, n * bytes down (synchronous).
+using FmtCall = std::function<int(const uint8_t *, const uint8_t *, const float *, void *)>;
+int run_fmt_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, size_t nfr, const float *init, size_t n,
+                 int width, int height, const ofdis_params *p, const ofdis_out_format *fmt, void *flow_out,
+                 const FmtCall &call) {
+  OutFmt of;
+  size_t bytes = 0;
+  int rc = out_format(p, width, height, init != nullptr, fmt, of, bytes);
+  if (rc) return rc;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t in = align_up(nfr * width * height * p->noc);
+  const size_t ini = init ? align_up(n * width * height * (p->mode == OFDIS_MODE_OF ? 2 : 1) * sizeof(float)) : 0;
+  const size_t off_b = in, off_init = img_b ? 2 * in : in, off_out = off_init + ini;
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_out + n * bytes));
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  const size_t in_bytes = nfr * width * height * p->noc;
+  if (step(hipMemcpyAsync(d, img_a, in_bytes, hipMemcpyHostToDevice, c->stream)) &&
+      (!img_b || step(hipMemcpyAsync(d + off_b, img_b, in_bytes, hipMemcpyHostToDevice, c->stream))) &&
+      (!init || step(hipMemcpyAsync(d + off_init, init, n * width * height * (p->mode == OFDIS_MODE_OF ? 2 : 1) *
+                                                            sizeof(float), hipMemcpyHostToDevice, c->stream)))) {
+    rc = call((const uint8_t *)d, img_b ? (const uint8_t *)(d + off_b) : nullptr,
+              init ? (const float *)(d + off_init) : nullptr, (void *)(d + off_out));
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream)))
+      step(hipMemcpy(flow_out, d + off_out, n * bytes, hipMemcpyDeviceToHost));
+  }
+  hipFree(d);
+  return rc;
+}
+}  // namespace
+
+int ofdis_run_batch_u8_fmt_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
+                                int width, int height, const ofdis_params *p, const ofdis_out_format *fmt,
+                                void *flow_out) {
+  if (!c || !img_a || !img_b || !flow_out || n <= 0 || width <= 0 || height <= 0 || !p)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  return run_fmt_host(c, img_a, img_b, (size_t)n, init, (size_t)n, width, height, p, fmt, flow_out,
+                      [&](const uint8_t *da, const uint8_t *db, const float *di, void *dout) {
+                        return ofdis_run_batch_u8_fmt(c, da, db, di, n, width, height, p, fmt, dout, c->stream);
+                      });
+}
+
+int ofdis_run_sequence_u8_fmt_host(ofdis_context *c, const uint8_t *frames, int nframes, int stride, const float *init,
+                                   int width, int height, const ofdis_params *p, const ofdis_out_format *fmt,
+                                   void *flow_fw) {
+  if (!c || !frames || !flow_fw || width <= 0 || height <= 0 || !p || stride < 1 || nframes <= stride)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;
+  return run_fmt_host(c, frames, nullptr, (size_t)nframes, init, (size_t)(nframes - stride), width, height, p, fmt,
+                      flow_fw, [&](const uint8_t *df, const uint8_t *, const float *di, void *dout) {
+                        return ofdis_run_sequence_u8_fmt(c, df, nframes, stride, di, width, height, p, fmt, dout,
+                                                         c->stream);
+                      });
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -1561,7 +1724,10 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
     }
   }
   if (k == "pyr_base") b = 2.0 * width * height * noc + 2.0 * 4.0 * P.lv[0].w * P.lv[0].h * noc;
-  if (k == "upsample") b = (double)width * height * nop * 4.0;
+  if (k == "upsample" || k == "upsample_planar") b = (double)width * height * nop * 4.0;  // bytes written
+  if (k == "upsample_f16" || k == "upsample_planar_f16") b = (double)width * height * nop * 2.0;
+  // the level grid: the float32 level plane read, and written (as float32; binary16 writes half of that)
+  if (k == "level_out") b = 2.0 * P.lv[0].w * P.lv[0].h * nop * 4.0;
   // both directions: the pixel's own flow and the gathered one (16 B), the mask byte, the error with "fb_check_err"
   if (k == "fb_check") b = 2.0 * width * height * (16.0 + 1.0);
   if (k == "fb_check_err") b = 2.0 * width * height * (16.0 + 1.0 + 4.0);

@@ -28,7 +28,8 @@ def shard_sequence(n_frames: int, stride: int, rank: int, world: int):
     them, and the rank's frames are those of its pairs -- `stride` more than its pairs -- so
     ``run_sequence(frames[frame_start:frame_stop], stride=stride)`` gives pairs [pair_start, pair_stop) and the shards'
     outputs concatenate to the whole call's.  With more ranks than pairs a rank has pair_start == pair_stop: it
-    has nothing to compute (a sequence call needs at least one pair)."""
+    has nothing to compute (a sequence call needs at least one pair).  The output format keywords of ``run_sequence``
+    (dtype, layout, grid) apply to each shard's call unchanged: every format's leading axis is the pair."""
     if stride < 1 or n_frames <= stride:
         raise ValueError("a sequence needs stride >= 1 and more than `stride` frames")
     p0, p1 = shard_range(n_frames - stride, rank, world)

@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import MODE_DE, MODE_OF, Params, check, lib
+from ._lib import ERR_UNSUPPORTED, MODE_DE, MODE_OF, OfdisError, OutFormat, Params, check, lib, out_format
 
 _f32 = np.float32
 
@@ -168,10 +168,23 @@ class Context:
         check(lib().ofdis_run_batch_u8_init(self._h, a_ptr, b_ptr, init_ptr or None, n, width, height, C.byref(p),
                                             out_ptr, stream or None), "ofdis_run_batch_u8_init")
 
-    def run(self, a, b, p: Params, out=None, init=None):
+    def run_ptr_fmt(self, a_ptr: int, b_ptr: int, n: int, width: int, height: int, p: Params, fmt: OutFormat,
+                    out_ptr: int, stream: int = 0, init_ptr: int = 0) -> None:
+        """``ofdis_run_batch_u8_fmt`` on raw device pointers: run_ptr writing n * bytes_per_pair bytes (out_geometry)
+        in the output format `fmt` (None: the plain format)."""
+        check(lib().ofdis_run_batch_u8_fmt(self._h, a_ptr, b_ptr, init_ptr or None, n, width, height, C.byref(p),
+                                           None if fmt is None else C.byref(fmt), out_ptr or None, stream or None),
+              "ofdis_run_batch_u8_fmt")
+
+    def run(self, a, b, p: Params, out=None, init=None, dtype=None, layout: str = "nhwc", grid: str = "full"):
         """torch.uint8 CUDA tensors [n, h, w] or [n, h, w, noc] -> torch.float32 [n, h, w, nop].
-        init: optional float32 CUDA tensor [n, h, w, nop], the initial flow at full resolution."""
+        init: optional float32 CUDA tensor [n, h, w, nop], the initial flow at full resolution.
+        dtype (torch.float32, the default, or torch.float16), layout ("nhwc" or "nchw") and grid ("full", or "level":
+        the finest level's 2^sc_l-pixel grid, see out_geometry) choose a compact output written by the kernels
+        themselves: [n, H, W, nop] or [n, nop, H, W] of that dtype.  Values are in full-resolution pixels always."""
         import torch
+        if dtype not in (None, torch.float32) or layout != "nhwc" or grid != "full":
+            return self._run_fmt(a, b, p, out, init, out_format(dtype or torch.float32, layout, grid))
         if a.dim() == 3:
             a, b = a.unsqueeze(-1), b.unsqueeze(-1)
         n, h, w, noc = a.shape
@@ -191,13 +204,45 @@ class Context:
                      init.data_ptr() if init is not None else 0)
         return out
 
-    def run_host(self, a: np.ndarray, b: np.ndarray, p: Params, init: Optional[np.ndarray] = None) -> np.ndarray:
+    def _run_fmt(self, a, b, p: Params, out, init, fmt: OutFormat):
+        import torch
+        if a.dim() == 3:
+            a, b = a.unsqueeze(-1), b.unsqueeze(-1)
+        n, h, w, noc = a.shape
+        if noc != p.noc or a.dtype != torch.uint8 or not (a.is_cuda and b.is_cuda):
+            raise ValueError("expected uint8 CUDA tensors with noc channels")
+        a, b = a.contiguous(), b.contiguous()
+        shape, tdt = _out_shape(p, w, h, n, init is not None, fmt), (torch.float16 if fmt.dtype else torch.float32)
+        if out is None:
+            out = torch.empty(shape, dtype=tdt, device=a.device)
+        elif tuple(out.shape) != shape or out.dtype != tdt or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {tdt} CUDA tensor {shape}")
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        if init is not None:
+            if tuple(init.shape) != (n, h, w, p.nop) or init.dtype != torch.float32 or not init.is_cuda:
+                raise ValueError("init must be a float32 CUDA tensor [n, h, w, nop]")
+            init = init.contiguous()
+        self.run_ptr_fmt(a.data_ptr(), b.data_ptr(), n, w, h, p, fmt, out.data_ptr(), stream,
+                         init.data_ptr() if init is not None else 0)
+        return out
+
+    def run_host(self, a: np.ndarray, b: np.ndarray, p: Params, init: Optional[np.ndarray] = None, dtype=np.float32,
+                 layout: str = "nhwc", grid: str = "full") -> np.ndarray:
         """numpy u8 [n,h,w,noc] (or a single [h,w,noc] pair) -> numpy float32 flow; synchronous.
-        init: optional initial flow at full resolution, [n,h,w,nop] (or [h,w,nop] for a single pair)."""
+        init: optional initial flow at full resolution, [n,h,w,nop] (or [h,w,nop] for a single pair).
+        dtype (np.float32 or np.float16), layout and grid: the output format, as in ``run``."""
         single = a.ndim == 3
         a4 = np.ascontiguousarray(a[None] if single else a, np.uint8)
         b4 = np.ascontiguousarray(b[None] if single else b, np.uint8)
         n, h, w = a4.shape[:3]
+        if np.dtype(dtype) != _f32 or layout != "nhwc" or grid != "full":
+            fmt = out_format(np.dtype(dtype), layout, grid)
+            out = np.empty(_out_shape(p, w, h, n, init is not None, fmt), np.float16 if fmt.dtype else _f32)
+            i4 = None if init is None else np.ascontiguousarray(init, _f32).reshape(n, h, w, p.nop)
+            check(lib().ofdis_run_batch_u8_fmt_host(self._h, a4.ctypes.data, b4.ctypes.data,
+                                                    None if i4 is None else i4.ctypes.data, n, w, h, C.byref(p),
+                                                    C.byref(fmt), out.ctypes.data), "ofdis_run_batch_u8_fmt_host")
+            return out[0] if single else out
         out = np.empty((n, h, w, p.nop), _f32)
         i4 = None
         if init is not None:
@@ -294,13 +339,20 @@ class Context:
               "ofdis_run_sequence_u8")
 
     def run_sequence(self, frames, p: Params, stride: int = 1, init=None, bidir: bool = False, alpha: float = 0.01,
-                     beta: float = 0.5, want_err: bool = False):
+                     beta: float = 0.5, want_err: bool = False, dtype=None, layout: str = "nhwc", grid: str = "full"):
         """Flow along a video: torch.uint8 CUDA tensor [T, h, w] or [T, h, w, noc] -> the flow of the T - stride pairs
         (frame i, frame i + stride), bit for bit ``run(frames[:-stride], frames[stride:])`` with every frame's
         pyramid built once.  Returns the flow [T - stride, h, w, 2]; with ``bidir`` the tuple of ``run_bidir``
         (flow_fw, flow_bw, occ_fw, occ_bw[, err_fw, err_bw]).  init: optional float32 CUDA tensor
-        [T - stride, h, w, 2] as in ``run`` (not together with ``bidir``).  Optical flow only."""
+        [T - stride, h, w, 2] as in ``run`` (not together with ``bidir``).  Optical flow only.
+        dtype, layout, grid: the forward flow's output format, as in ``run`` (not together with ``bidir``: the
+        backward flow, masks and errors are float32 fields)."""
         import torch
+        fmt = None
+        if dtype not in (None, torch.float32) or layout != "nhwc" or grid != "full":
+            fmt = out_format(dtype or torch.float32, layout, grid)
+            if bidir:
+                raise OfdisError(ERR_UNSUPPORTED, "run_sequence: bidir with an output format")
         if frames.dim() == 3:
             frames = frames.unsqueeze(-1)
         t, h, w, noc = frames.shape
@@ -314,6 +366,15 @@ class Context:
             if tuple(init.shape) != (n, h, w, 2) or init.dtype != torch.float32 or not init.is_cuda:
                 raise ValueError("init must be a float32 CUDA tensor [T - stride, h, w, 2]")
             init = init.contiguous()
+        if fmt is not None:
+            out = torch.empty(_out_shape(p, w, h, n, init is not None, fmt),
+                              dtype=torch.float16 if fmt.dtype else torch.float32, device=frames.device)
+            check(lib().ofdis_run_sequence_u8_fmt(self._h, frames.data_ptr(), t, stride,
+                                                  init.data_ptr() if init is not None else None, w, h, C.byref(p),
+                                                  C.byref(fmt), out.data_ptr(),
+                                                  torch.cuda.current_stream(frames.device).cuda_stream or None),
+                  "ofdis_run_sequence_u8_fmt")
+            return out
         flow = [torch.empty((n, h, w, 2), dtype=torch.float32, device=frames.device) for _ in range(2 if bidir else 1)]
         occ = [torch.empty((n, h, w), dtype=torch.uint8, device=frames.device) for _ in range(2 if bidir else 0)]
         err = [torch.empty((n, h, w), dtype=torch.float32, device=frames.device)
@@ -327,14 +388,26 @@ class Context:
         return tuple(flow + occ + err) if bidir else flow[0]
 
     def run_sequence_host(self, frames: np.ndarray, p: Params, stride: int = 1, init: Optional[np.ndarray] = None,
-                          bidir: bool = False, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False):
+                          bidir: bool = False, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False,
+                          dtype=np.float32, layout: str = "nhwc", grid: str = "full"):
         """run_sequence on a numpy u8 array [T, h, w] or [T, h, w, noc]; synchronous."""
+        fmt = None
+        if np.dtype(dtype) != _f32 or layout != "nhwc" or grid != "full":
+            fmt = out_format(np.dtype(dtype), layout, grid)
+            if bidir:
+                raise OfdisError(ERR_UNSUPPORTED, "run_sequence_host: bidir with an output format")
         f4 = np.ascontiguousarray(frames[..., None] if frames.ndim == 3 else frames, np.uint8)
         t, h, w = f4.shape[:3]
         n = t - stride
         if stride < 1 or n < 1:
             raise ValueError("a sequence needs stride >= 1 and more than `stride` frames")
         i4 = None if init is None else np.ascontiguousarray(init, _f32).reshape(n, h, w, 2)
+        if fmt is not None:
+            out = np.empty(_out_shape(p, w, h, n, init is not None, fmt), np.float16 if fmt.dtype else _f32)
+            check(lib().ofdis_run_sequence_u8_fmt_host(self._h, f4.ctypes.data, t, stride,
+                                                       None if i4 is None else i4.ctypes.data, w, h, C.byref(p),
+                                                       C.byref(fmt), out.ctypes.data), "ofdis_run_sequence_u8_fmt_host")
+            return out
         flow = [np.empty((n, h, w, 2), _f32) for _ in range(2 if bidir else 1)]
         occ = [np.empty((n, h, w), np.uint8) for _ in range(2 if bidir else 0)]
         err = [np.empty((n, h, w), _f32) for _ in range(2 if bidir and want_err else 0)]
@@ -389,6 +462,26 @@ class Context:
         return ms.value, cnt.value
 
 
+def out_geometry(p: Params, width: int, height: int, with_init: bool = False, dtype="float32", layout: str = "nhwc",
+                 grid: str = "full") -> dict:
+    """``ofdis_out_geometry``: the output grid of one pair in a format -- out_w, out_h, off_x, off_y, cell and
+    bytes_per_pair.  Level cell (X, Y) covers the original pixels [X * cell - off_x, (X + 1) * cell - off_x) x
+    [Y * cell - off_y, (Y + 1) * cell - off_y); the level grid is not cropped."""
+    fmt = out_format(dtype, layout, grid)
+    v = [C.c_int() for _ in range(5)]
+    nb = C.c_size_t()
+    check(lib().ofdis_out_geometry(C.byref(p), width, height, int(bool(with_init)), C.byref(fmt),
+                                   *[C.byref(x) for x in v], C.byref(nb)), "ofdis_out_geometry")
+    return dict(zip(("out_w", "out_h", "off_x", "off_y", "cell"), (x.value for x in v)), bytes_per_pair=nb.value)
+
+
+def _out_shape(p: Params, width: int, height: int, n: int, with_init: bool, fmt: OutFormat):
+    ow, oh = C.c_int(), C.c_int()
+    check(lib().ofdis_out_geometry(C.byref(p), width, height, int(with_init), C.byref(fmt), C.byref(ow), C.byref(oh),
+                                   None, None, None, None), "ofdis_out_geometry")
+    return (n, p.nop, oh.value, ow.value) if fmt.layout else (n, oh.value, ow.value, p.nop)
+
+
 def kernel_names():
     return lib().ofdis_kernel_names().decode().split(",")
 
@@ -408,5 +501,5 @@ def algorithmic_bytes(p: Params, width: int, height: int, kernel: str) -> float:
 
 __all__ = ["OFClass", "Context", "Params", "oppoint", "params_from_strings", "validate", "synth_pair", "synth_shift_pair",
            "write_flo", "write_pfm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
-           "max_frames_per_launch",
+           "max_frames_per_launch", "out_geometry",
            "MODE_OF", "MODE_DE"]
