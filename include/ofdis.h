@@ -267,6 +267,60 @@ int ofdis_run_sequence_u8_fmt_host(ofdis_context *ctx, const uint8_t *frames, in
                                    const float *init_flow, int width, int height, const ofdis_params *p,
                                    const ofdis_out_format *fmt, void *flow_fw);
 
+/* ------------------------------------------------------------------ flow-driven image warping
+ *
+ * Not in the reference, which stops at the flow file.  The first thing a consumer does with a flow is pull frame b
+ * back onto frame a along it (motion compensation, temporal denoising, interpolation, photometric error maps).
+ *
+ * ofdis_warp_u8: backward warp of n u8 frames by n optical-flow fields (device pointers).
+ * img: u8 [n][height][width][noc] (noc 1 or 3); out: u8 or float32 (out_dtype) of the same shape; valid: u8
+ * [n][height][width] or NULL.  flow: the field in any form ofdis_run_batch_u8_fmt can write, described by view.
+ *
+ * Definition, frame size W x H, pixel (x, y), channel c, (u, v) the flow at that pixel as float32 (a binary16 value
+ * converted exactly); all arithmetic float32 in this order, every operation rounded on its own (no fused multiply-add):
+ *   su = scale*u;  sv = scale*v
+ *   px = (float)x + su;  py = (float)y + sv
+ *   inside = px >= 0 && px <= (float)(W-1) && py >= 0 && py <= (float)(H-1)           (false for NaN)
+ *   pxc = fminf(fmaxf(px, 0), (float)(W-1));  pyc likewise                  (NaN -> 0: IEEE maxNum / minNum)
+ *   x0 = (int)floorf(pxc); y0 = (int)floorf(pyc); x1 = min(x0+1, W-1); y1 = min(y0+1, H-1)
+ *   ax = pxc - (float)x0;  ay = pyc - (float)y0
+ *   t.. = (float)img[y.][x.][c]
+ *   top = t00 + ax*(t01 - t00);  bot = t10 + ax*(t11 - t10);  val = top + ay*(bot - top)
+ *   float32 output: val.   u8 output: (uint8_t)rintf(val)                             (round half to even)
+ *   valid = inside ? 1 : 0
+ * The u8 form needs no clamp: the taps are integers in 0..255 and every rounding is monotonic, so val stays in [0, 255].
+ * A pixel whose position leaves the frame samples the replicated border and is flagged valid = 0.
+ *
+ * Flow views.  dtype / layout / grid are ofdis_out_format's enums.  FULL: flow is [n][H][W][2] (INTERLEAVED) or
+ * [n][2][H][W] (PLANAR); the other fields are ignored.  LEVEL: flow is [n][gh][gw][2] or [n][2][gh][gw], the level
+ * grid of ofdis_run_batch_u8_fmt, and gw, gh, cell, off_x, off_y are what ofdis_out_geometry reports for it (out_w,
+ * out_h, cell, off_x, off_y).  (u, v) at pixel (x, y) is then the value the plain call's upsample computes from those
+ * cells -- cv::resize INTER_LINEAR's taps of column x + off_x and row y + off_y, h = s0*(1-fx) + s1*fx per source
+ * row, then h0*(1-fy) + h1*fy; the cell at (x + off_x, y + off_y) itself when cell = 1 -- so a float32 level view gives
+ * the picture of the full-resolution float32 field bit for bit, and that field is never written or read.
+ *
+ * Refused before anything is enqueued (OFDIS_ERR_INVALID_ARGUMENT, the context stays usable): NULL img / flow / view /
+ * out, n < 1, non-positive sizes, noc not 1 or 3, unknown enum values, a level view whose cell is not a power of two in
+ * 1..512 or whose grid does not cover the frame (gw*cell < width + off_x, gh*cell < height + off_y, a negative
+ * offset), scale not finite, width * height >= 2^31.  Stream, ordering and workspace rules are those of ofdis_fb_check. */
+enum { OFDIS_IMG_U8 = 0, OFDIS_IMG_F32 = 1 }; /* out_dtype */
+typedef struct ofdis_flow_view { int dtype, layout, grid, gw, gh, cell, off_x, off_y; } ofdis_flow_view;
+int ofdis_warp_u8(ofdis_context *ctx, const uint8_t *img, const void *flow, const ofdis_flow_view *view, int n,
+                  int width, int height, int noc, float scale, int out_dtype, void *out, uint8_t *valid, void *stream);
+
+/* The flow a -> b of each pair, then img_b warped by it: at scale = 1, frame b pulled back onto frame a.  By definition
+ * out / valid == ofdis_warp_u8(img_b, ofdis_run_batch_u8(img_a, img_b)), bit for bit -- but the flow leaves the
+ * coarse-to-fine loop as the float32 level grid, n * bytes_per_pair bytes in a buffer the context owns, and the warp
+ * expands it on the fly: no full-resolution flow is allocated or written and no upsample runs.  valid may be NULL.
+ * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED.  No initial flow.  verbosity is ignored (no TIME
+ * lines).  A stage capture behaves as in ofdis_run_batch_u8_fmt.  Argument errors as for ofdis_run_batch_u8 and
+ * ofdis_warp_u8; stream, ordering, chunking, graph and workspace rules are those of ofdis_run_batch_u8. */
+int ofdis_run_warp_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                      const ofdis_params *p, float scale, int out_dtype, void *out, uint8_t *valid, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_warp_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
+                           int height, const ofdis_params *p, float scale, int out_dtype, void *out, uint8_t *valid);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -381,11 +435,15 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
 /* Comma-separated list of kernel names known to the timer.  The forward-backward check is timed as "fb_check"
  * when it writes masks only and as "fb_check_err" when it also writes an error map; the upsample as "upsample" when
  * it writes the plain format alone, else as "upsample_f16", "upsample_planar" or "upsample_planar_f16", and the
- * level-grid output that replaces it as "level_out". */
+ * level-grid output that replaces it as "level_out"; the warp as "warp" with a full-resolution flow view and as
+ * "warp_level" with a level-grid view. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
- * bytes written ("level_out": the float32 level plane read and a float32 write). */
+ * bytes written ("level_out": the float32 level plane read and a float32 write).  "warp" / "warp_level": p->noc bytes
+ * of image read per pixel, the flow view (8 bytes per pixel; the level grid's gw * gh * 2 * 4 bytes per frame), noc
+ * bytes of u8 output and the mask byte -- the float32 views and the u8 output with its mask, as ofdis_run_warp_u8
+ * issues them. */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */
@@ -398,6 +456,8 @@ int ofdis_write_pfm(const char *path, const float *depth, int width, int height)
 int ofdis_read_flo(const char *path, float *flow, int *width, int *height, int nc);
 /* Binary PGM (P5, noc = 1) / PPM (P6, noc = 3, returned in BGR order like cv::imread). */
 int ofdis_read_pnm(const char *path, uint8_t *pixels, int *width, int *height, int *noc, size_t capacity);
+/* Binary PGM (P5, noc = 1) / PPM (P6, noc = 3: pixels in BGR order, written as RGB) -- the inverse of ofdis_read_pnm. */
+int ofdis_write_pnm(const char *path, const uint8_t *pixels, int width, int height, int noc);
 /* cv::imread(path, want_noc == 1 ? CV_LOAD_IMAGE_GRAYSCALE : CV_LOAD_IMAGE_COLOR) (run_dense.cpp:202-206)
  * for PNG (zlib inflate; gray / RGB / palette / alpha, 1-16 bit, Adam7; libpng's transform chain as
  * OpenCV configures it, incl. png_set_rgb_to_gray(0.299, 0.587)) and Netpbm P1-P6 (colour -> gray with

@@ -29,6 +29,8 @@ MODE_DE = 2
 OUT_F32, OUT_F16 = 0, 1
 OUT_INTERLEAVED, OUT_PLANAR = 0, 1
 OUT_FULL, OUT_LEVEL = 0, 1
+# out_dtype of the warp entry points
+IMG_U8, IMG_F32 = 0, 1
 
 
 class OfdisError(RuntimeError):
@@ -76,6 +78,14 @@ class OutFormat(C.Structure):
     _fields_ = [("dtype", C.c_int), ("layout", C.c_int), ("grid", C.c_int)]
 
 
+class FlowView(C.Structure):
+    """ofdis_flow_view (include/ofdis.h): how a warp reads its flow -- an OutFormat plus, for the level grid, the
+    geometry ofdis_out_geometry reports."""
+
+    _fields_ = [("dtype", C.c_int), ("layout", C.c_int), ("grid", C.c_int), ("gw", C.c_int), ("gh", C.c_int),
+                ("cell", C.c_int), ("off_x", C.c_int), ("off_y", C.c_int)]
+
+
 def out_format(dtype="float32", layout="nhwc", grid="full") -> OutFormat:
     """OutFormat from the Python spellings: dtype float32 / float16 (a numpy or torch dtype, or its name), layout
     "nhwc" (interleaved) / "nchw" (planar), grid "full" / "level".  Anything else raises OfdisError(INVALID_ARGUMENT)."""
@@ -113,6 +123,7 @@ def lib():
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     P = C.POINTER(Params)
     F = C.POINTER(OutFormat)
+    V = C.POINTER(FlowView)
     sig = {
         "ofdis_abi_version": ([], i),
         "ofdis_status_string": ([i], C.c_char_p),
@@ -137,6 +148,10 @@ def lib():
         "ofdis_run_batch_u8_fmt_host": ([vp, vp, vp, vp, i, i, i, P, F, vp], i),
         "ofdis_run_sequence_u8_fmt": ([vp, vp, i, i, vp, i, i, P, F, vp, vp], i),
         "ofdis_run_sequence_u8_fmt_host": ([vp, vp, i, i, vp, i, i, P, F, vp], i),
+        "ofdis_warp_u8": ([vp, vp, vp, V, i, i, i, i, f, i, vp, vp, vp], i),
+        "ofdis_run_warp_u8": ([vp, vp, vp, i, i, i, P, f, i, vp, vp, vp], i),
+        "ofdis_run_warp_u8_host": ([vp, vp, vp, i, i, i, P, f, i, vp, vp], i),
+        "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),
         "ofdis_context_set_option": ([vp, C.c_char_p, i], i),

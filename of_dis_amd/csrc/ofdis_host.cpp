@@ -251,6 +251,29 @@ int ofdis_read_pnm(const char *path, uint8_t *pixels, int *width, int *height, i
   return OFDIS_OK;
 }
 
+int ofdis_write_pnm(const char *path, const uint8_t *pixels, int width, int height, int noc) {
+  if (!path || !pixels || width <= 0 || height <= 0 || (noc != 1 && noc != 3)) return OFDIS_ERR_INVALID_ARGUMENT;
+  FILE *f = std::fopen(path, "wb");
+  if (!f) return OFDIS_ERR_IO;
+  bool ok = std::fprintf(f, "P%d\n%d %d\n255\n", noc == 1 ? 5 : 6, width, height) > 0;
+  const size_t rowb = (size_t)width * noc;
+  std::vector<uint8_t> row(rowb);
+  for (int y = 0; y < height && ok; ++y) {
+    const uint8_t *src = pixels + (size_t)y * rowb;
+    if (noc == 3) {  // BGR in memory, RGB in the file
+      for (size_t i = 0; i < rowb; i += 3) {
+        row[i] = src[i + 2];
+        row[i + 1] = src[i + 1];
+        row[i + 2] = src[i];
+      }
+      src = row.data();
+    }
+    ok = std::fwrite(src, 1, rowb, f) == rowb;
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? OFDIS_OK : OFDIS_ERR_IO;
+}
+
 // ------------------------------------------------------------------------------------ synthetic pairs
 
 static inline uint64_t splitmix64(uint64_t &s) {

@@ -181,6 +181,20 @@ struct FbArgs {
   float alpha, beta;
 };
 
+// Backward warp of u8 frames along a flow view (include/ofdis.h: ofdis_warp_u8).
+struct WarpArgs {
+  const uint8_t *img;  // [n][H][W][noc]
+  const void *flow;    // full grid: [n][H][W][2] or [n][2][H][W]; level grid: [n][gh][gw][2] or [n][2][gh][gw]
+  void *out;           // u8 or float [n][H][W][noc]
+  uint8_t *valid;      // [n][H][W] 1 / 0, or NULL
+  int n, W, H, noc;    // W * H < 2^31
+  float scale;
+  int out_f32;             // `out` holds float32 values
+  int f16, planar, level;  // the flow view (ofdis_out_format's dtype, layout, grid)
+  int gw, gh, log2c, offx, offy;  // level grid: its size, log2 of the cell, the frame's offset in it (ofdis_out_geometry)
+};
+
+void launch_warp(const WarpArgs &a, hipStream_t s);
 void launch_fb_check(const FbArgs &a, hipStream_t s);
 void launch_init_area(const InitArgs &a, hipStream_t s);
 void warm_kernels_module(hipStream_t s);  // one empty launch per kernel translation unit: loads its code object

@@ -31,6 +31,8 @@
 //   output       k_upsample, k_upsample_rows, k_upsample_h<R>, k_upsample_rows1  run_dense.cpp:407-415
 //                (<T, PLANAR>: the float16 / planar output formats), k_level_out  (ofdis_out_format)
 //   fb check     k_fb_check<OCC, ERR, PX>  forward-backward consistency masks of two flow fields (no reference code)
+//   warp         k_warp<OT, NOC, FT, PLANAR, PX>, k_warp_level<OT, NOC, PX>  backward warp of u8 frames along a flow
+//                field / along the level grid expanded on the fly (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -5038,6 +5040,30 @@ __device__ __forceinline__ float up_px(const float *P, long r0, long r1, const X
   return h0 * b0 + h1 * b1;
 }
 
+// up_px on values that already hold S * 2^l (staged rows, the level grid of ofdis_out_format): R0 / R1 are the two
+// source rows, xt.sx an index into them.
+__device__ __forceinline__ float up_px_s(const float *R0, const float *R1, const XTap &xt, float b0, float b1) {
+  const float s0 = R0[xt.sx], s1 = R1[xt.sx];
+  const float h0 = xt.lin ? s0 * (1.f - xt.fx) + R0[xt.sx + 1] * xt.fx : s0;
+  const float h1 = xt.lin ? s1 * (1.f - xt.fx) + R1[xt.sx + 1] * xt.fx : s1;
+  return h0 * b0 + h1 * b1;
+}
+
+// Vertical source rows / weight of output row dy (resizeGeneric_Invoker: sy, fy; the rows clamped, the weight not).
+struct YTap {
+  int r0, r1;
+  float fy;
+};
+__device__ __forceinline__ YTap ytap(int dy, double scale, int hl) {
+  YTap r;
+  float fy = (float)((dy + 0.5) * scale - 0.5);
+  const int sy = (int)floorf(fy);
+  r.fy = fy - (float)sy;
+  r.r0 = sy >= 0 ? (sy < hl ? sy : hl - 1) : 0;
+  r.r1 = sy + 1 >= 0 ? (sy + 1 < hl ? sy + 1 : hl - 1) : 0;
+  return r;
+}
+
 // Upsample for 2^l >= 2, nop = 2: one block = 1024 output columns x kUpRows output rows, 4 columns (two
 // 16-byte stores per row) per thread.  The source rows the block needs are staged in LDS once,
 // already multiplied by 2^l.  The OpenCV tap positions fx = (dx + .5) / 2^l - .5 are dyadic rationals, so
@@ -5431,13 +5457,9 @@ __global__ __launch_bounds__(256) void k_upsample(UpArgs a) {
   }
   const float fct = (float)(1 << a.log2s);
   const double scale = 1.0 / (double)(1 << a.log2s);
-  const int dy = y + a.offy;
-  float fy = (float)((dy + 0.5) * scale - 0.5);
-  const int sy = (int)floorf(fy);
-  fy -= (float)sy;
-  const long r0 = (long)(sy >= 0 ? (sy < a.hl ? sy : a.hl - 1) : 0) * a.wl;
-  const long r1 = (long)(sy + 1 >= 0 ? (sy + 1 < a.hl ? sy + 1 : a.hl - 1) : 0) * a.wl;
-  const float b0 = 1.f - fy, b1 = fy;
+  const YTap yt = ytap(y + a.offy, scale, a.hl);
+  const long r0 = (long)yt.r0 * a.wl, r1 = (long)yt.r1 * a.wl;
+  const float b0 = 1.f - yt.fy, b1 = yt.fy;
   const XTap xt = xtap(x + a.offx, scale, a.wl);
   if constexpr (kPlainOut<T, PLANAR>) {
     for (int k = 0; k < a.nop; ++k) out[k] = up_px(F + k * plane, r0, r1, xt, fct, b0, b1);
@@ -5638,6 +5660,279 @@ void launch_fb_check(const FbArgs &a0, hipStream_t s) {
     if (occ && err) go(Int<1>{}, Int<1>{});
     else if (occ) go(Int<1>{}, Int<0>{});
     else go(Int<0>{}, Int<1>{});
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ warp
+// The backward warp of include/ofdis.h (ofdis_warp_u8): every pixel of a u8 frame is read at (x + scale u, y + scale v)
+// with bilinear taps and a replicated border.  Like the consistency check, the definition fixes every operation and
+// its order (float32, no contraction), so the picture is a pure function of the image and the flow values.
+//   k_warp<OT, NOC, FT, PLANAR, PX>  the flow is a full-resolution field (float32 / binary16, interleaved / planar)
+//   k_warp_level<OT, NOC, PX>        the flow is the level grid of ofdis_out_format: the kernel expands the cells with
+//                                    the upsample's own taps (xtap, ytap, up_px_s) from rows staged in LDS, so the
+//                                    pixel's (u, v) carries the bits k_upsample would have written
+namespace {
+
+// One pixel: the NOC interpolated values; returns valid (1: the position lies inside the frame).
+template <int NOC>
+__device__ __forceinline__ unsigned warp_pixel(const uint8_t *__restrict__ I, int W, int H, int x, int y, float u,
+                                               float v, float scale, float *val) {
+  const float su = scale * u, sv = scale * v;
+  const float px = (float)x + su, py = (float)y + sv;
+  const float wm = (float)(W - 1), hm = (float)(H - 1);
+  const bool inside = px >= 0.f && px <= wm && py >= 0.f && py <= hm;  // false for NaN
+  // no branch around the gather (as fb_pixel): a position outside the frame reads the replicated border.
+  // fmaxf / fminf are IEEE maxNum / minNum: NaN -> 0
+  const float pxc = fminf(fmaxf(px, 0.f), wm), pyc = fminf(fmaxf(py, 0.f), hm);
+  // the integer min is a no-op below 2^24 columns / rows, where (float)(W - 1) is exact; beyond, it keeps the taps
+  // inside the frame when (float)(W - 1) rounds up
+  const int x0 = min((int)floorf(pxc), W - 1), y0 = min((int)floorf(pyc), H - 1);
+  const int y1 = y0 + 1 < H ? y0 + 1 : H - 1;  // (x1 = min(x0 + 1, W - 1): the second byte of the pair below)
+  const float ax = pxc - (float)x0, ay = pyc - (float)y0;
+  // pixel indices stay below 2^31 (W * H < 2^31): one 32-bit multiply per pixel, the second row a row stride further
+  const unsigned o0 = (unsigned)y0 * (unsigned)W, o1 = o0 + (y1 != y0 ? (unsigned)W : 0u);
+  float t00[NOC], t01[NOC], t10[NOC], t11[NOC];
+  if (W >= 2) {
+    // the two taps of a row are neighbours in memory: the 2 NOC bytes from column xl = min(x0, W - 2) hold both (in the
+    // last column, where x1 = x0, the second pixel of the pair twice) -- one 2-byte load per row for intensity images,
+    // 4 + 2 bytes for colour, instead of a byte load per tap and channel; the gather is bound by load instructions
+    const int xl = x0 < W - 1 ? x0 : W - 2;
+    const bool last = x0 != xl;
+    const uint8_t *q0 = I + (size_t)(o0 + (unsigned)xl) * NOC, *q1 = I + (size_t)(o1 + (unsigned)xl) * NOC;
+    unsigned b0[2 * NOC], b1[2 * NOC];
+    if constexpr (NOC == 1) {
+      uint16_t h0, h1;  // all loads issued before the arithmetic
+      __builtin_memcpy(&h0, q0, 2);
+      __builtin_memcpy(&h1, q1, 2);
+      b0[0] = h0 & 0xffu, b0[1] = h0 >> 8;
+      b1[0] = h1 & 0xffu, b1[1] = h1 >> 8;
+    } else {
+      uint32_t w0, w1;
+      uint16_t h0, h1;
+      __builtin_memcpy(&w0, q0, 4);
+      __builtin_memcpy(&h0, q0 + 4, 2);
+      __builtin_memcpy(&w1, q1, 4);
+      __builtin_memcpy(&h1, q1 + 4, 2);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) b0[k] = (w0 >> (8 * k)) & 0xffu, b1[k] = (w1 >> (8 * k)) & 0xffu;
+      b0[4] = h0 & 0xffu, b0[5] = h0 >> 8;
+      b1[4] = h1 & 0xffu, b1[5] = h1 >> 8;
+    }
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) {
+      t01[c] = (float)b0[NOC + c];
+      t11[c] = (float)b1[NOC + c];
+      t00[c] = last ? t01[c] : (float)b0[c];
+      t10[c] = last ? t11[c] : (float)b1[c];
+    }
+  } else {  // one column: x0 = x1 = 0
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) {
+      t00[c] = t01[c] = (float)I[(size_t)o0 * NOC + c];
+      t10[c] = t11[c] = (float)I[(size_t)o1 * NOC + c];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NOC; ++c) {
+    const float top = t00[c] + ax * (t01[c] - t00[c]), bot = t10[c] + ax * (t11[c] - t10[c]);
+    val[c] = top + ay * (bot - top);
+  }
+  return inside ? 1u : 0u;
+}
+
+// The PX pixels (x .. x + PX - 1, y) of frame f from their flows: gather, interpolate, store.  PX = 4: four u8 values
+// as one dword, four float32 values as one 16-byte store (NOC = 3: three of them), the four valid bytes as one dword.
+template <class OT, int NOC, int PX>
+__device__ __forceinline__ void warp_emit(const WarpArgs &a, int f, int x, int y, const float *u, const float *v) {
+  const long plane = (long)a.W * a.H, o = (long)f * plane + (long)y * a.W + x;
+  const uint8_t *I = a.img + (long)f * plane * NOC;
+  float val[PX * NOC];
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < PX; ++i) m |= warp_pixel<NOC>(I, a.W, a.H, x + i, y, u[i], v[i], a.scale, val + i * NOC) << (8 * i);
+  OT *out = reinterpret_cast<OT *>(a.out) + o * NOC;
+  if constexpr (std::is_same<OT, float>::value) {
+    if constexpr (PX == 4) {
+#pragma unroll
+      for (int j = 0; j < NOC; ++j)
+        *reinterpret_cast<float4_v *>(out + 4 * j) = float4_v{val[4 * j], val[4 * j + 1], val[4 * j + 2], val[4 * j + 3]};
+    } else {
+#pragma unroll
+      for (int c = 0; c < NOC; ++c) out[c] = val[c];
+    }
+  } else {  // u8: round half to even; the taps lie in 0..255 and rounding is monotonic, so no clamp
+    unsigned b[PX * NOC];
+#pragma unroll
+    for (int k = 0; k < PX * NOC; ++k) b[k] = (unsigned)(int)rintf(val[k]);
+    if constexpr (PX == 4) {
+#pragma unroll
+      for (int j = 0; j < NOC; ++j)
+        *reinterpret_cast<unsigned *>(out + 4 * j) = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
+    } else {
+#pragma unroll
+      for (int c = 0; c < NOC; ++c) out[c] = (uint8_t)b[c];
+    }
+  }
+  if (a.valid) {
+    if constexpr (PX == 4)
+      *reinterpret_cast<unsigned *>(a.valid + o) = m;
+    else
+      a.valid[o] = (uint8_t)m;
+  }
+}
+
+// A thread's own flow from a full-resolution field F (one frame; o = y W + x, plane = W H), binary16 converted
+// exactly.  PX = 4: 16-byte loads (binary16 planar: 8 bytes per component).
+template <class FT, bool PLANAR, int PX>
+__device__ __forceinline__ void warp_own_flow(const FT *F, long o, long plane, float *u, float *v) {
+  constexpr bool kF32 = std::is_same<FT, float>::value;
+  if constexpr (PX == 1) {
+    u[0] = (float)(PLANAR ? F[o] : F[2 * o]);
+    v[0] = (float)(PLANAR ? F[plane + o] : F[2 * o + 1]);
+  } else if constexpr (PLANAR) {
+    using V = std::conditional_t<kF32, float4_v, v4h>;
+    const V p = *reinterpret_cast<const V *>(F + o), q = *reinterpret_cast<const V *>(F + plane + o);
+    u[0] = (float)p.x, u[1] = (float)p.y, u[2] = (float)p.z, u[3] = (float)p.w;
+    v[0] = (float)q.x, v[1] = (float)q.y, v[2] = (float)q.z, v[3] = (float)q.w;
+  } else if constexpr (kF32) {
+    const float4_v lo = *reinterpret_cast<const float4_v *>(F + 2 * o), hi = *reinterpret_cast<const float4_v *>(F + 2 * o + 4);
+    u[0] = lo.x, v[0] = lo.y, u[1] = lo.z, v[1] = lo.w;
+    u[2] = hi.x, v[2] = hi.y, u[3] = hi.z, v[3] = hi.w;
+  } else {
+    const v8h p = *reinterpret_cast<const v8h *>(F + 2 * o);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) u[i] = (float)p[2 * i], v[i] = (float)p[2 * i + 1];
+  }
+}
+
+// PX = 4: four consecutive pixels of a row per thread (W % 4 == 0 and aligned pointers: launch_warp).  PX = 1: any
+// width and alignment.
+template <class OT, int NOC, class FT, bool PLANAR, int PX>
+__global__ __launch_bounds__(256) void k_warp(WarpArgs a) {
+  const int f = blockIdx.z;
+  const unsigned wq = (unsigned)a.W / PX;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= wq * (unsigned)a.H) return;
+  const int y = (int)(q / wq), x = (int)(q - (unsigned)y * wq) * PX;
+  const long plane = (long)a.W * a.H;
+  float u[PX], v[PX];
+  warp_own_flow<FT, PLANAR, PX>(reinterpret_cast<const FT *>(a.flow) + (long)f * 2 * plane, (long)y * a.W + x, plane, u, v);
+  warp_emit<OT, NOC, PX>(a, f, x, y, u, v);
+}
+
+// The level-grid form: one block = 256 PX columns x kWarpRows rows, PX consecutive columns per thread.  cell >= 2: the
+// rows of cells the block's output rows touch (at most kWarpRows / cell + 2) and its window of columns are staged in
+// LDS once as float32 -- the view's element type and layout end there -- and every pixel's (u, v) is the upsample's
+// expression on them: xtap on column x + off_x, ytap on row y + off_y, up_px_s.  cell == 1: the cell at
+// (x + off_x, y + off_y), the log2s == 0 branch of k_upsample, read directly.
+constexpr int kWarpRows = 4;
+constexpr int kWarpSrcRows = kWarpRows / 2 + 3;
+constexpr int kWarpSrcCols = 1024 / 2 + 4;  // ceil(256 PX / cell) + 2 columns, PX = 4, cell = 2; one spare
+
+template <class OT, int NOC, int PX>
+__global__ __launch_bounds__(256) void k_warp_level(WarpArgs a) {
+  __shared__ float src[kWarpSrcRows][2][kWarpSrcCols];  // [row][comp][col]
+  constexpr int kCols = 256 * PX;
+  // blockIdx.x = row block * column blocks + column block: neighbours in x share their rows of cells
+  const unsigned ncb = ((unsigned)a.W + kCols - 1) / kCols;
+  const int y0 = (int)(blockIdx.x / ncb) * kWarpRows, f = blockIdx.z;
+  const long xb = (long)(blockIdx.x % ncb) * kCols;
+  const long xl = xb + threadIdx.x * PX;  // (a block's last columns may pass W, and 2^31 with it)
+  const int x = (int)(xl < a.W ? xl : a.W);
+  const long gplane = (long)a.gw * a.gh;
+  auto cell = [&](long i, int k) {  // component k of cell i of frame f
+    const long e = a.planar ? ((long)f * 2 + k) * gplane + i : ((long)f * gplane + i) * 2 + k;
+    return a.f16 ? (float)reinterpret_cast<const _Float16 *>(a.flow)[e] : reinterpret_cast<const float *>(a.flow)[e];
+  };
+  float u[PX], v[PX];
+  if (a.log2c == 0) {
+    if (x >= a.W) return;
+    for (int r = 0; r < kWarpRows; ++r) {
+      const int y = y0 + r;
+      if (y >= a.H) break;
+#pragma unroll
+      for (int i = 0; i < PX; ++i) {
+        const long o = (long)(y + a.offy) * a.gw + (x + i + a.offx);
+        u[i] = cell(o, 0);
+        v[i] = cell(o, 1);
+      }
+      warp_emit<OT, NOC, PX>(a, f, x, y, u, v);
+    }
+    return;
+  }
+  const double scale = 1.0 / (double)(1 << a.log2c);
+  const int ylast = min(y0 + kWarpRows, a.H) - 1;
+  const int r_first = ytap(y0 + a.offy, scale, a.gh).r0;
+  const int nr = min(ytap(ylast + a.offy, scale, a.gh).r1 - r_first + 1, kWarpSrcRows);
+  // first source column of the block: floor of xtap's position of output column xb + off_x, (2 dx + 1 - cell) / (2 cell)
+  const long c_raw = (2 * (xb + a.offx) + 1 - (1 << a.log2c)) >> (a.log2c + 1);
+  const int c_lo = (int)(c_raw > 0 ? c_raw : 0);
+  const int ncol = min((kCols >> a.log2c) + 3, kWarpSrcCols);
+  for (int k = threadIdx.x; k < nr * 2 * ncol; k += 256) {
+    const int col = k % ncol, rc = k / ncol;  // rc = row * 2 + comp
+    const int sc = min(c_lo + col, a.gw - 1);
+    src[rc >> 1][rc & 1][col] = cell((long)(r_first + (rc >> 1)) * a.gw + sc, rc & 1);
+  }
+  __syncthreads();
+  if (x >= a.W) return;
+  XTap xt[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    xt[i] = xtap(x + i + a.offx, scale, a.gw);
+    xt[i].sx = min(max(xt[i].sx - c_lo, 0), kWarpSrcCols - 2);  // (inside the staged window by construction)
+  }
+  for (int r = 0; r < kWarpRows; ++r) {
+    const int y = y0 + r;
+    if (y >= a.H) break;
+    const YTap yt = ytap(y + a.offy, scale, a.gh);
+    const int j0 = min(max(yt.r0 - r_first, 0), nr - 1), j1 = min(max(yt.r1 - r_first, 0), nr - 1);
+    const float b0 = 1.f - yt.fy, b1 = yt.fy;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      u[i] = up_px_s(src[j0][0], src[j1][0], xt[i], b0, b1);
+      v[i] = up_px_s(src[j0][1], src[j1][1], xt[i], b0, b1);
+    }
+    warp_emit<OT, NOC, PX>(a, f, x, y, u, v);
+  }
+}
+
+}  // namespace
+// ---- launch
+// Frames go in grid z, 65535 per launch.  The vector forms need W % 4 == 0, the flow 16-byte aligned (which aligns
+// every row, plane and frame of it to the thread's loads in each format; the level form reads cells one by one), the
+// output aligned to its store (4 bytes u8, 16 float32) and the mask to 4.
+void launch_warp(const WarpArgs &a0, hipStream_t s) {
+  const bool vec = a0.W % 4 == 0 && (a0.level || (uintptr_t)a0.flow % 16 == 0) &&
+                   (uintptr_t)a0.out % (a0.out_f32 ? 16 : 4) == 0 && (uintptr_t)a0.valid % 4 == 0;
+  const long frame = (long)a0.W * a0.H;
+  const long flow_frame = (a0.level ? (long)a0.gw * a0.gh : frame) * 2 * (a0.f16 ? 2 : 4);  // bytes
+  const int kSlice = 65535;  // grid z
+  for (int f0 = 0; f0 < a0.n; f0 += kSlice) {
+    WarpArgs a = a0;
+    a.n = std::min(kSlice, a0.n - f0);
+    a.img += f0 * frame * a0.noc;
+    a.flow = (const char *)a0.flow + f0 * flow_frame;
+    a.out = (char *)a0.out + f0 * frame * a0.noc * (a0.out_f32 ? 4 : 1);
+    if (a.valid) a.valid += f0 * frame;
+    auto go = [&](auto OT, auto NOC, auto PX) {
+      using O = std::conditional_t<OT != 0, float, uint8_t>;
+      if (a.level) {
+        const dim3 grid(ceil_div(a.H, kWarpRows) * ceil_div(a.W, 256 * PX), 1, a.n);
+        k_warp_level<O, NOC, PX><<<grid, 256, 0, s>>>(a);
+        return;
+      }
+      const dim3 grid(ceil_div(frame / PX, 256), 1, a.n);
+      if (a.f16 && a.planar) k_warp<O, NOC, _Float16, true, PX><<<grid, 256, 0, s>>>(a);
+      else if (a.f16) k_warp<O, NOC, _Float16, false, PX><<<grid, 256, 0, s>>>(a);
+      else if (a.planar) k_warp<O, NOC, float, true, PX><<<grid, 256, 0, s>>>(a);
+      else k_warp<O, NOC, float, false, PX><<<grid, 256, 0, s>>>(a);
+    };
+    pick_noc(a.noc, [&](auto NOC) {
+      pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {
+        if (vec) go(OT, NOC, Int<4>{});
+        else go(OT, NOC, Int<1>{});
+      });
+    });
   }
 }
 

@@ -31,7 +31,9 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     "fb_check", "fb_check_err",
                                     // the upsample writing an output format other than the plain one, and the
                                     // level-grid output that replaces it ("upsample": the plain format alone)
-                                    "upsample_f16", "upsample_planar", "upsample_planar_f16", "level_out"};
+                                    "upsample_f16", "upsample_planar", "upsample_planar_f16", "level_out",
+                                    // the warp with a full-resolution flow view / with a level-grid view
+                                    "warp", "warp_level"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -75,6 +77,9 @@ struct ofdis_context {
   hipStream_t stream = nullptr;
   char *ws = nullptr;
   size_t ws_cap = 0;
+  // ofdis_run_warp_u8: the call's flow as the float32 level grid, [n] x bytes_per_pair (ofdis_out_geometry)
+  char *warp_buf = nullptr;
+  size_t warp_cap = 0;
   // stage capture (frame 0), indexed by scale
   std::vector<float *> cap_dis, cap_tv;
   // kernel timing
@@ -97,6 +102,10 @@ struct ofdis_context {
     int seq = 0, stride = 0;  // ofdis_run_sequence_u8: `a` is one array of n + stride frames, b is NULL
     int out_f16 = 0, out_planar = 0, out_level = 0;  // output format: a formatted call on a plain call's buffers
                                                      // records anew, and the other way round
+    // ofdis_run_warp_u8: the picture, its mask and the level-grid buffer the flow passes through
+    const void *warp_out = nullptr, *warp_valid = nullptr, *warp_buf = nullptr;
+    float warp_scale = 0.f;
+    int warp = 0, warp_f32 = 0;
     int n = 0, w = 0, h = 0;
     ofdis_params p{};
   } gkey;
@@ -358,6 +367,21 @@ int ensure_ws(ofdis_context *c, size_t bytes) {
   }
   HIP_OK(hipMalloc(&c->ws, bytes));
   c->ws_cap = bytes;
+  return OFDIS_OK;
+}
+
+int ensure_warp_buf(ofdis_context *c, size_t bytes) {
+  if (bytes <= c->warp_cap) return OFDIS_OK;
+  if (c->warp_buf) {
+    int rc = drop_graph(c);
+    if (rc) return rc;
+    HIP_OK(hipDeviceSynchronize());  // callers may have queued work on their own streams
+    HIP_OK(hipFree(c->warp_buf));
+    c->warp_buf = nullptr;
+    c->warp_cap = 0;
+  }
+  HIP_OK(hipMalloc(&c->warp_buf, bytes));
+  c->warp_cap = bytes;
   return OFDIS_OK;
 }
 
@@ -808,6 +832,7 @@ void ofdis_context_destroy(ofdis_context *c) {
   drain_timing(c);
   for (auto e : c->pool) hipEventDestroy(e);
   if (c->ws) hipFree(c->ws);
+  if (c->warp_buf) hipFree(c->warp_buf);
   for (auto &L : c->lanes) {
     if (L.s) hipStreamSynchronize(L.s);
     if (L.ws) hipFree(L.ws);
@@ -921,17 +946,63 @@ int run_fb_check(ofdis_context *c, const float *fw, const float *bw, int n, int 
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
+// The picture of a warp (ofdis_warp_u8, ofdis_run_warp_u8); at() is a chunk's share.
+struct WarpOut {
+  void *out = nullptr;
+  uint8_t *valid = nullptr;
+  float scale = 1.f;
+  int f32 = 0;
+  WarpOut at(size_t f0, size_t px, int noc) const {
+    WarpOut o = *this;
+    o.out = (char *)out + f0 * px * noc * (f32 ? 4 : 1);
+    if (valid) o.valid += f0 * px;
+    return o;
+  }
+};
+
+// n frames warped along a flow view (timer "warp_level" for a level-grid view, else "warp").
+int run_warp(ofdis_context *c, const uint8_t *img, const void *flow, const ofdis_flow_view &v, int n, int width,
+             int height, int noc, const WarpOut &o, hipStream_t s) {
+  WarpArgs wa{};
+  wa.img = img;
+  wa.flow = flow;
+  wa.out = o.out;
+  wa.valid = o.valid;
+  wa.n = n;
+  wa.W = width;
+  wa.H = height;
+  wa.noc = noc;
+  wa.scale = o.scale;
+  wa.out_f32 = o.f32;
+  wa.f16 = v.dtype == OFDIS_OUT_F16;
+  wa.planar = v.layout == OFDIS_OUT_PLANAR;
+  wa.level = v.grid == OFDIS_OUT_LEVEL;
+  if (wa.level) {
+    wa.gw = v.gw;
+    wa.gh = v.gh;
+    wa.offx = v.off_x;
+    wa.offy = v.off_y;
+    while ((1 << wa.log2c) < v.cell) ++wa.log2c;
+  }
+  timed(c, wa.level ? 19 : 18, s, [&] { launch_warp(wa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
 // One chunk of frames through the whole pipeline on stream s with workspace ws.  bd (P.bidir): the backward flow
 // of the same pyramid upsampled too -- into the workspace when the caller wants only the masks -- and the check.
 int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
               const uint8_t *img_b, const float *init, void *flow_out, const BidirOut *bd, hipStream_t s,
-              const OutFmt &fmt) {
+              const OutFmt &fmt, const WarpOut *wo = nullptr) {
   int rc = run_pyramid(c, ws, P, img_a, img_b, s);
   if (rc) return rc;
   if (init && (rc = run_init(c, ws, P, p, init, s))) return rc;
   rc = run_levels(c, ws, P, p, s, init ? (const float *)(ws + P.off_init) : nullptr, nullptr);
   if (rc) return rc;
   rc = run_upsample(c, ws, P, p, flow_out, s, false, fmt);
+  if (!rc && wo) {  // ofdis_run_warp_u8: flow_out is the chunk's float32 level grid (fmt), img_b warped by it
+    ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
+    return run_warp(c, img_b, flow_out, v, P.n, P.W0, P.H0, P.noc, *wo, s);
+  }
   if (rc || !bd) return rc;  // (bd: the plain format, float32 fields)
   float *flow_bw = bd->flow_bw ? bd->flow_bw : (float *)(ws + P.off_up_bw);
   if ((rc = run_upsample(c, ws, P, p, flow_bw, s, true))) return rc;
@@ -1022,7 +1093,7 @@ int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int heigh
 // array, so neighbouring chunks rebuild the `stride` frames they share; the outputs are per pair as ever.
 int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p,
                       const uint8_t *img_a, const uint8_t *img_b, const float *init, void *flow_out,
-                      const BidirOut *bd, const OutFmt &fmt) {
+                      const BidirOut *bd, const OutFmt &fmt, const WarpOut *wo) {
   const int k = cp.lanes;
   HIP_OK(hipEventRecord(c->entry, s));
   for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
@@ -1032,9 +1103,10 @@ int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const
     const size_t f0 = (size_t)ch * cp.chunk;
     auto &L = c->lanes[ch % k];
     const BidirOut part = bd ? bd->at(f0, (size_t)cp.width * cp.height) : BidirOut();
+    const WarpOut wpart = wo ? wo->at(f0, (size_t)cp.width * cp.height, p->noc) : WarpOut();
     int rc = run_chunk(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b ? img_b + f0 * in_frame : nullptr,
                        init ? init + f0 * out_frame : nullptr, (char *)flow_out + f0 * cp.out_pair,
-                       bd ? &part : nullptr, L.s, fmt);
+                       bd ? &part : nullptr, L.s, fmt, wo ? &wpart : nullptr);
     if (rc) return rc;
   }
   for (int i = 0; i < k; ++i) {
@@ -1045,10 +1117,11 @@ int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const
 }
 
 int issue(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *img_a,
-          const uint8_t *img_b, const float *init, void *flow_out, const BidirOut *bd, const OutFmt &fmt) {
+          const uint8_t *img_b, const float *init, void *flow_out, const BidirOut *bd, const OutFmt &fmt,
+          const WarpOut *wo) {
   switch (cp.kind) {
-    case CallPlan::kRoundRobin: return issue_round_robin(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt);
-    default: return run_chunk(c, c->ws, cp.whole, p, img_a, img_b, init, flow_out, bd, s, fmt);
+    case CallPlan::kRoundRobin: return issue_round_robin(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt, wo);
+    default: return run_chunk(c, c->ws, cp.whole, p, img_a, img_b, init, flow_out, bd, s, fmt, wo);
   }
 }
 
@@ -1089,7 +1162,7 @@ int validate_call(const ofdis_params *p, int width, int height, bool init) {
 // n + stride frames and pair i is (frame i, frame i + stride); img_b is NULL.
 int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
               int width, int height, const ofdis_params *p, void *flow_out, const BidirOut *bd = nullptr,
-              int stride = 0, const OutFmt &fmt = OutFmt()) {
+              int stride = 0, const OutFmt &fmt = OutFmt(), const WarpOut *wo = nullptr) {
   const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
   CallPlan cp;
   int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, bd ? (bd->flow_bw ? 1 : 2) : 0, stride);
@@ -1099,10 +1172,14 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
     const size_t cells = fmt.level ? (size_t)P1.lv[0].w * P1.lv[0].h : (size_t)width * height;
     cp.out_pair = cells * P1.nop * (fmt.f16 ? 2 : 4);
   }
+  if (wo) {  // ofdis_run_warp_u8 (flow_out NULL, fmt the float32 level grid): the flow goes through the context's buffer
+    if ((rc = ensure_warp_buf(c, (size_t)n * cp.out_pair))) return rc;
+    flow_out = c->warp_buf;
+  }
   OFDIS_TRACE("run_batch: kind %d, %d chunks of %d, %d lanes", (int)cp.kind, cp.nchunks, cp.chunk, cp.lanes);
   // graph 1: capture single-stream batches; graph 2: also the multi-lane (fork / join) issues
   const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
-  if (!graph || capturing || c->timing) return issue(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt);
+  if (!graph || capturing || c->timing) return issue(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt, wo);
   // ~80 dependent launches per chunk: record them once as a HIP graph (on the context's own stream -- the
   // caller's may be the legacy NULL stream, which cannot capture) and replay it on the caller's stream while
   // the pointers, sizes, parameters and options stay the same (set_option drops the graph).  Multi-lane
@@ -1117,11 +1194,15 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
     key.bidir = 1; key.flow_bw = bd->flow_bw; key.occ_fw = bd->occ_fw; key.occ_bw = bd->occ_bw;
     key.err_fw = bd->err_fw; key.err_bw = bd->err_bw; key.alpha = bd->alpha; key.beta = bd->beta;
   }
+  if (wo) {  // (key.out is then the level-grid buffer)
+    key.warp = 1; key.warp_out = wo->out; key.warp_valid = wo->valid; key.warp_buf = c->warp_buf;
+    key.warp_scale = wo->scale; key.warp_f32 = wo->f32;
+  }
   if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0) {
     if ((rc = drop_graph(c))) return rc;
     OFDIS_TRACE("graph: capture (kind %d, %d chunks of %d)", (int)cp.kind, cp.nchunks, cp.chunk);
     HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = issue(c, cp, c->stream, p, img_a, img_b, init, flow_out, bd, fmt);
+    rc = issue(c, cp, c->stream, p, img_a, img_b, init, flow_out, bd, fmt, wo);
     OFDIS_TRACE("graph: issued rc %d", rc);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
@@ -1558,6 +1639,94 @@ int ofdis_run_sequence_u8_fmt_host(ofdis_context *c, const uint8_t *frames, int 
                       });
 }
 
+// ------------------------------------------------------------------ warping (include/ofdis.h)
+
+namespace {
+bool img_dtype_ok(int d) { return d == OFDIS_IMG_U8 || d == OFDIS_IMG_F32; }
+}  // namespace
+
+int ofdis_warp_u8(ofdis_context *c, const uint8_t *img, const void *flow, const ofdis_flow_view *v, int n, int width,
+                  int height, int noc, float scale, int out_dtype, void *out, uint8_t *valid, void *stream) {
+  if (!c || !img || !flow || !v || !out || n <= 0 || width <= 0 || height <= 0 || (noc != 1 && noc != 3) ||
+      !std::isfinite(scale) || !img_dtype_ok(out_dtype) || (long)width * height > 0x7fffffffL)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->grid == OFDIS_OUT_LEVEL) {
+    if (v->cell < 1 || v->cell > 512 || (v->cell & (v->cell - 1)) || v->gw <= 0 || v->gh <= 0 || v->off_x < 0 ||
+        v->off_y < 0 || (long)v->gw * v->cell < (long)width + v->off_x || (long)v->gh * v->cell < (long)height + v->off_y)
+      return OFDIS_ERR_INVALID_ARGUMENT;
+  }
+  WarpOut o;
+  o.out = out;
+  o.valid = valid;
+  o.scale = scale;
+  o.f32 = out_dtype == OFDIS_IMG_F32;
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
+  if (rc) return rc;
+  rc = run_warp(c, img, flow, *v, n, width, height, noc, o, s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_warp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                      const ofdis_params *p, float scale, int out_dtype, void *out, uint8_t *valid, void *stream) {
+  if (!c || !img_a || !img_b || !out || n <= 0 || width <= 0 || height <= 0 || !p || !std::isfinite(scale) ||
+      !img_dtype_ok(out_dtype) || (long)width * height > 0x7fffffffL)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a disparity is not a flow view
+  WarpOut o;
+  o.out = out;
+  o.valid = valid;
+  o.scale = scale;
+  o.f32 = out_dtype == OFDIS_IMG_F32;
+  OutFmt of;
+  of.level = 1;  // float32, interleaved
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch(c, s, img_a, img_b, nullptr, n, width, height, p, nullptr, nullptr, 0, of, &o);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_warp_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                           const ofdis_params *p, float scale, int out_dtype, void *out, uint8_t *valid) {
+  if (!c || !img_a || !img_b || !out || n <= 0 || width <= 0 || height <= 0 || !p || !img_dtype_ok(out_dtype) ||
+      (p->noc != 1 && p->noc != 3))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)n * width * height, in = px * p->noc, outb = in * (out_dtype == OFDIS_IMG_F32 ? 4 : 1);
+  // one device block: the two images, the picture, the mask (each at a multiple of 256 bytes)
+  const size_t off_b = align_up(in), off_out = 2 * align_up(in), off_valid = off_out + align_up(outb);
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_valid + (valid ? px : 0)));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  if (step(hipMemcpyAsync(d, img_a, in, hipMemcpyHostToDevice, c->stream)) &&
+      step(hipMemcpyAsync(d + off_b, img_b, in, hipMemcpyHostToDevice, c->stream))) {
+    rc = ofdis_run_warp_u8(c, (const uint8_t *)d, (const uint8_t *)(d + off_b), n, width, height, p, scale, out_dtype,
+                           d + off_out, valid ? (uint8_t *)(d + off_valid) : nullptr, c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      step(hipMemcpy(out, d + off_out, outb, hipMemcpyDeviceToHost));
+      if (valid) step(hipMemcpy(valid, d + off_valid, px, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -1731,6 +1900,10 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   // both directions: the pixel's own flow and the gathered one (16 B), the mask byte, the error with "fb_check_err"
   if (k == "fb_check") b = 2.0 * width * height * (16.0 + 1.0);
   if (k == "fb_check_err") b = 2.0 * width * height * (16.0 + 1.0 + 4.0);
+  // the warp as ofdis_run_warp_u8 issues it: image taps and u8 picture (noc each) and the mask byte per pixel, and the
+  // float32 flow view -- 8 bytes per pixel, or the level grid once per frame
+  if (k == "warp") b = (double)width * height * (2.0 * noc + 1.0 + 8.0);
+  if (k == "warp_level") b = (double)width * height * (2.0 * noc + 1.0) + (double)P.lv[0].w * P.lv[0].h * 2 * 4.0;
   *bytes = b;
   return OFDIS_OK;
 }

@@ -14,7 +14,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import ERR_UNSUPPORTED, MODE_DE, MODE_OF, OfdisError, OutFormat, Params, check, lib, out_format
+from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, IMG_F32, IMG_U8, MODE_DE, MODE_OF, FlowView, OfdisError,
+                   OutFormat, Params, check, lib, out_format)
 
 _f32 = np.float32
 
@@ -420,6 +421,102 @@ class Context:
                                                err[1].ctypes.data if err else None), "ofdis_run_sequence_u8_host")
         return tuple(flow + occ + err) if bidir else flow[0]
 
+    def warp_ptr(self, img_ptr: int, flow_ptr: int, view: FlowView, n: int, width: int, height: int, noc: int,
+                 scale: float, out_dtype: int, out_ptr: int, valid_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_warp_u8`` on raw device pointers (valid_ptr 0: no mask); out_dtype IMG_U8 / IMG_F32."""
+        check(lib().ofdis_warp_u8(self._h, img_ptr or None, flow_ptr or None, C.byref(view), n, width, height, noc,
+                                  scale, out_dtype, out_ptr or None, valid_ptr or None, stream or None),
+              "ofdis_warp_u8")
+
+    def warp(self, img, flow, scale: float = 1.0, out_dtype=None, layout: str = "nhwc", grid: str = "full",
+             p: Optional[Params] = None, want_valid: bool = False):
+        """Backward warp of u8 frames along a flow: torch.uint8 CUDA tensor [n, h, w] or [n, h, w, 3] read at
+        (x + scale u, y + scale v) with bilinear taps and a replicated border (the definition is in ofdis.h) ->
+        the picture in the image's shape, torch.uint8 (the default) or torch.float32; with want_valid the tuple
+        (picture, valid uint8 [n, h, w], 0 where the position left the frame).
+        flow: any output of ``run`` -- float32 or float16 (read from the tensor), layout "nhwc" / "nchw", grid "full"
+        ([n, h, w, 2] / [n, 2, h, w]) or "level" (the level grid of ``run(..., grid="level")``; needs the same `p`, and
+        gives the picture of the full-resolution flow bit for bit without that flow ever existing)."""
+        import torch
+        gray = img.dim() == 3
+        im = img.unsqueeze(-1) if gray else img
+        if im.dim() != 4 or im.shape[-1] not in (1, 3) or im.dtype != torch.uint8 or not (im.is_cuda and flow.is_cuda):
+            raise ValueError("expected a uint8 CUDA tensor [n, h, w] or [n, h, w, 3] and a CUDA flow tensor")
+        n, h, w, noc = im.shape
+        fmt = out_format(flow.dtype, layout, grid)
+        view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        if grid == "level":
+            if p is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'warp: grid="level" needs the parameters the flow was computed with')
+            g = out_geometry(p, w, h, False, flow.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        want = (n, 2, view.gh, view.gw) if fmt.layout else (n, view.gh, view.gw, 2)
+        if tuple(flow.shape) != want:
+            raise ValueError(f"flow has shape {tuple(flow.shape)}, expected {want}")
+        if out_dtype not in (None, torch.uint8, torch.float32):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"warp: out_dtype {out_dtype!r}")
+        f32 = out_dtype == torch.float32
+        im, flow = im.contiguous(), flow.contiguous()
+        out = torch.empty(img.shape, dtype=torch.float32 if f32 else torch.uint8, device=im.device)
+        valid = torch.empty((n, h, w), dtype=torch.uint8, device=im.device) if want_valid else None
+        self.warp_ptr(im.data_ptr(), flow.data_ptr(), view, n, w, h, noc, float(scale), IMG_F32 if f32 else IMG_U8,
+                      out.data_ptr(), valid.data_ptr() if want_valid else 0,
+                      torch.cuda.current_stream(im.device).cuda_stream)
+        return (out, valid) if want_valid else out
+
+    def run_warp_ptr(self, a_ptr: int, b_ptr: int, n: int, width: int, height: int, p: Params, scale: float,
+                     out_dtype: int, out_ptr: int, valid_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_run_warp_u8`` on raw device pointers, asynchronous on `stream` (valid_ptr 0: no mask)."""
+        check(lib().ofdis_run_warp_u8(self._h, a_ptr or None, b_ptr or None, n, width, height, C.byref(p), scale,
+                                      out_dtype, out_ptr or None, valid_ptr or None, stream or None),
+              "ofdis_run_warp_u8")
+
+    def run_warp(self, a, b, p: Params, scale: float = 1.0, out_dtype=None, want_valid: bool = False):
+        """Motion compensation in one call: the flow a -> b of each pair, then b warped by it -- at scale 1, frame b
+        pulled back onto frame a.  torch.uint8 CUDA tensors [n, h, w] or [n, h, w, 3] -> the picture in that shape
+        (torch.uint8, or torch.float32), with want_valid the tuple (picture, valid).  Bit for bit
+        ``warp(b, run(a, b, p), scale)``, but the flow stays on its level grid: no full-resolution flow is written."""
+        import torch
+        a4, b4 = (a.unsqueeze(-1), b.unsqueeze(-1)) if a.dim() == 3 else (a, b)
+        if (a4.dim() != 4 or a4.shape[-1] != p.noc or a4.dtype != torch.uint8 or a.shape != b.shape
+                or b.dtype != torch.uint8 or not (a.is_cuda and b.is_cuda)):
+            raise ValueError("expected two uint8 CUDA tensors of one shape with noc channels")
+        if out_dtype not in (None, torch.uint8, torch.float32):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_warp: out_dtype {out_dtype!r}")
+        f32 = out_dtype == torch.float32
+        n, h, w, _ = a4.shape
+        a4, b4 = a4.contiguous(), b4.contiguous()
+        out = torch.empty(a.shape, dtype=torch.float32 if f32 else torch.uint8, device=a.device)
+        valid = torch.empty((n, h, w), dtype=torch.uint8, device=a.device) if want_valid else None
+        self.run_warp_ptr(a4.data_ptr(), b4.data_ptr(), n, w, h, p, float(scale), IMG_F32 if f32 else IMG_U8,
+                          out.data_ptr(), valid.data_ptr() if want_valid else 0,
+                          torch.cuda.current_stream(a.device).cuda_stream)
+        return (out, valid) if want_valid else out
+
+    def run_warp_host(self, a: np.ndarray, b: np.ndarray, p: Params, scale: float = 1.0, out_dtype=np.uint8,
+                      want_valid: bool = False):
+        """run_warp on numpy u8 arrays; synchronous.  Colour: [n, h, w, 3] or a single pair [h, w, 3]; gray:
+        [n, h, w, 1], [n, h, w], or a single pair [h, w, 1] (as synth_pair returns it) or [h, w].  The picture has the
+        input's shape; valid is [n, h, w] ([h, w] for a single pair)."""
+        if np.dtype(out_dtype) not in (np.dtype(np.uint8), np.dtype(_f32)):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_warp_host: out_dtype {out_dtype!r}")
+        a = np.ascontiguousarray(a, np.uint8)
+        b = np.ascontiguousarray(b, np.uint8)
+        if a.shape != b.shape or a.ndim < 2 or a.ndim > 4:
+            raise ValueError("expected two uint8 arrays of one shape")
+        channels = a.ndim == 4 or (a.ndim == 3 and a.shape[-1] == p.noc and (p.noc == 3 or a.shape[-1] == 1))
+        if channels and a.shape[-1] != p.noc:
+            raise ValueError("expected noc channels")
+        h, w = a.shape[-3:-1] if channels else a.shape[-2:]
+        single = a.ndim == (3 if channels else 2)
+        n = 1 if single else a.shape[0]
+        out = np.empty(a.shape, out_dtype)
+        valid = np.empty((h, w) if single else (n, h, w), np.uint8) if want_valid else None
+        check(lib().ofdis_run_warp_u8_host(self._h, a.ctypes.data, b.ctypes.data, n, w, h, C.byref(p), float(scale),
+                                           IMG_F32 if np.dtype(out_dtype) == _f32 else IMG_U8, out.ctypes.data,
+                                           valid.ctypes.data if want_valid else None), "ofdis_run_warp_u8_host")
+        return (out, valid) if want_valid else out
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
@@ -482,6 +579,13 @@ def _out_shape(p: Params, width: int, height: int, n: int, with_init: bool, fmt:
     return (n, p.nop, oh.value, ow.value) if fmt.layout else (n, oh.value, ow.value, p.nop)
 
 
+def write_pnm(path: str, pixels: np.ndarray) -> None:
+    """Binary PGM (u8 [h, w] or [h, w, 1]) / PPM (u8 [h, w, 3] in BGR order, written as RGB)."""
+    pixels = np.ascontiguousarray(pixels, np.uint8)
+    noc = 1 if pixels.ndim == 2 else pixels.shape[2]
+    check(lib().ofdis_write_pnm(path.encode(), pixels.ctypes.data, pixels.shape[1], pixels.shape[0], noc), "write_pnm")
+
+
 def kernel_names():
     return lib().ofdis_kernel_names().decode().split(",")
 
@@ -500,6 +604,6 @@ def algorithmic_bytes(p: Params, width: int, height: int, kernel: str) -> float:
 
 
 __all__ = ["OFClass", "Context", "Params", "oppoint", "params_from_strings", "validate", "synth_pair", "synth_shift_pair",
-           "write_flo", "write_pfm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
+           "write_flo", "write_pfm", "write_pnm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
            "max_frames_per_launch", "out_geometry",
            "MODE_OF", "MODE_DE"]
