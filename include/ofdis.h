@@ -192,6 +192,64 @@ int ofdis_run_bidir_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint
                             int height, const ofdis_params *p, float alpha, float beta, float *flow_fw,
                             float *flow_bw, uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw);
 
+/* ------------------------------------------------------------------ stereo: both views and left-right masks
+ *
+ * Not in the reference, whose depth mode gives the left view's disparity and nothing that says where it can be
+ * trusted.  The left-right consistency check is the forward-backward check of a rectified pair: follow each pixel
+ * along its disparity into the other view, read that view's disparity there and ask whether the two cancel.
+ *
+ * ofdis_lr_check: the check on two full-resolution disparity fields (device pointers).
+ * disp_l, disp_r: float [n][height][width]; occ_*: u8 [n][height][width]; err_*: float [n][height][width].
+ * disp_l[y][x] = d: left pixel x matches right pixel x + d (d <= 0 from the plain depth call); disp_r[y][x] = d: right
+ * pixel x matches left pixel x + d (d >= 0).  The check does not assume the signs.  Any of the four outputs may be
+ * NULL (all NULL: OFDIS_OK, nothing enqueued).  Mask codes: 0 consistent, 1 inconsistent (occluded or wrong), 2 the
+ * disparity leaves the frame (err = +inf there).
+ *
+ * Definition, view l (r: D and O exchanged), pixel (x, y), D = the view's own field, O = the other field of the same
+ * frame; all arithmetic float32 in this order, every operation rounded on its own (no fused multiply-add):
+ *   u = D[y][x];  px = (float)x + u
+ *   inside = px >= 0 && px <= (float)(W-1)                                            (false for NaN)
+ *   if !inside: occ = 2, err = +inf
+ *   x0 = (int)floorf(px);  x1 = min(x0+1, W-1);  ax = px - (float)x0
+ *   b = O[y][x0] + ax*(O[y][x1] - O[y][x0])
+ *   d = u + b;  err = d*d;  mag = u*u + b*b;  thr = alpha*mag + beta
+ *   occ = (err <= thr) ? 0 : 1                                                        (NaN err -> 1)
+ *   a NaN err is stored as the canonical quiet NaN 0x7fc00000
+ * This is ofdis_fb_check on the two-component fields (d, 0), bit for bit, whenever both fields are finite (the v terms
+ * are exact zeros there and the vertical tap has weight 0).  Thresholds, NULL rules, refusals, stream and ordering
+ * rules are those of ofdis_fb_check.
+ */
+int ofdis_lr_check(ofdis_context *ctx, const float *disp_l, const float *disp_r, int n, int width, int height,
+                   float alpha, float beta, uint8_t *occ_l, uint8_t *occ_r, float *err_l, float *err_r, void *stream);
+
+/* Both views' disparities of n rectified pairs and the check, from one call.  img_l / img_r: device u8
+ * [n][height][width][noc].  Definition, with mir(I)[y][x] = I[y][width-1-x]:
+ *   disp_l == ofdis_run_batch_u8(img_l, img_r) in OFDIS_MODE_DE, bit for bit;
+ *   M = ofdis_run_batch_u8(mir(img_r), mir(img_l)): the mirrored right image is the left camera of a valid rectified
+ *   pair, so the plain depth call applies to it unchanged (the mirrored pair is padded for divisibility after
+ *   mirroring, exactly as that call pads it: with an odd padding the two views' padded frames differ);
+ *   disp_r[y][x] = M[y][width-1-x] with its sign bit flipped (+0 becomes -0, a NaN keeps its payload);
+ *   the masks and errors are ofdis_lr_check(disp_l, disp_r).
+ * (The reference's own backward field -- usefbcon's right-camera grid, patch.cpp:186-190 with camlr == 1, clamped to
+ * >= 0 and then to <= 0 by the refinement -- is not a right-view disparity; it stays an internal of the plain call.)
+ * At less than the cost of the two calls: both views of a chunk run as one batch of 2n flow pairs through the same
+ * launches, the mirrored frames' pyramid base is read from img_l / img_r through a mirrored column index (no mirrored
+ * copy of the images), and the upsample stores the mirrored half at column width-1-x with the sign flipped (no pass
+ * over the float fields).
+ * disp_l is required; disp_r and the occ / err outputs may be NULL (masks without disp_r: the right field stays in the
+ * workspace; all five NULL: the plain call).  Depth only: OFDIS_MODE_OF returns OFDIS_ERR_UNSUPPORTED, and so does a
+ * call while a stage capture is set.  No initial flow.  verbosity is ignored (no TIME lines).  Float32 outputs only.
+ * Argument errors as for ofdis_run_bidir_u8; stream, ordering, chunking, graph and workspace rules are those of
+ * ofdis_run_batch_u8, with chunk sizes counting stereo pairs: a stereo pair is two flow pairs and four pyramid frames,
+ * so a launch takes at most ofdis_max_frames_per_launch() / 2 of them. */
+int ofdis_run_stereo_u8(ofdis_context *ctx, const uint8_t *img_l, const uint8_t *img_r, int n, int width, int height,
+                        const ofdis_params *p, float alpha, float beta, float *disp_l, float *disp_r,
+                        uint8_t *occ_l, uint8_t *occ_r, float *err_l, float *err_r, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_stereo_u8_host(ofdis_context *ctx, const uint8_t *img_l, const uint8_t *img_r, int n, int width,
+                             int height, const ofdis_params *p, float alpha, float beta, float *disp_l, float *disp_r,
+                             uint8_t *occ_l, uint8_t *occ_r, float *err_l, float *err_r);
+
 /* ------------------------------------------------------------------ video sequences
  *
  * Not in the reference, which reads two files per process.  frames: device u8 [nframes][height][width][noc], the
@@ -436,14 +494,15 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * when it writes masks only and as "fb_check_err" when it also writes an error map; the upsample as "upsample" when
  * it writes the plain format alone, else as "upsample_f16", "upsample_planar" or "upsample_planar_f16", and the
  * level-grid output that replaces it as "level_out"; the warp as "warp" with a full-resolution flow view and as
- * "warp_level" with a level-grid view. */
+ * "warp_level" with a level-grid view; the left-right check as "lr_check" / "lr_check_err" like the forward-backward one. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
  * bytes written ("level_out": the float32 level plane read and a float32 write).  "warp" / "warp_level": p->noc bytes
  * of image read per pixel, the flow view (8 bytes per pixel; the level grid's gw * gh * 2 * 4 bytes per frame), noc
  * bytes of u8 output and the mask byte -- the float32 views and the u8 output with its mask, as ofdis_run_warp_u8
- * issues them. */
+ * issues them.  "lr_check" / "lr_check_err": both views, the pixel's own disparity and the gathered one (8 bytes), the
+ * mask byte, and the 4-byte error with "lr_check_err" -- 2 * W * H * (8 + 1 [+ 4]). */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */

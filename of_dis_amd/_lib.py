@@ -141,6 +141,9 @@ def lib():
         "ofdis_fb_check": ([vp, vp, vp, i, i, i, f, f, vp, vp, vp, vp, vp], i),
         "ofdis_run_bidir_u8": ([vp, vp, vp, i, i, i, P, f, f, vp, vp, vp, vp, vp, vp, vp], i),
         "ofdis_run_bidir_u8_host": ([vp, vp, vp, i, i, i, P, f, f, vp, vp, vp, vp, vp, vp], i),
+        "ofdis_lr_check": ([vp, vp, vp, i, i, i, f, f, vp, vp, vp, vp, vp], i),
+        "ofdis_run_stereo_u8": ([vp, vp, vp, i, i, i, P, f, f, vp, vp, vp, vp, vp, vp, vp], i),
+        "ofdis_run_stereo_u8_host": ([vp, vp, vp, i, i, i, P, f, f, vp, vp, vp, vp, vp, vp], i),
         "ofdis_run_sequence_u8": ([vp, vp, i, i, vp, i, i, P, f, f, vp, vp, vp, vp, vp, vp, vp], i),
         "ofdis_run_sequence_u8_host": ([vp, vp, i, i, vp, i, i, P, f, f, vp, vp, vp, vp, vp, vp], i),
         "ofdis_out_geometry": ([P, i, i, i, F] + [C.POINTER(i)] * 5 + [C.POINTER(C.c_size_t)], i),

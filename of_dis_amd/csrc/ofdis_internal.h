@@ -34,6 +34,9 @@ struct PyrBaseArgs {
   int w, h;                      // output level size
   float *out;                    // unpadded level [nf][h][w][noc]
   int rgb_sad;                  // colour, 2^l = 4..16: k_pyr_base_rgb (option pyr_rgb)
+  int stereo;                    // ofdis_run_stereo_u8: n stereo pairs (img_a left, img_b right), nf = 4n frames --
+                                 // left, mirrored right, right, mirrored left, n of each; the mirrored frames are read
+                                 // from img_b / img_a through a mirrored column index
 };
 
 // SELECTCHANNEL 2 (run_dense.cpp:139-148): level 0 = Sobel gradient magnitude of the divisibility-padded
@@ -43,6 +46,7 @@ struct PyrGradmagArgs {
   const uint8_t *img_a, *img_b;  // [n][H0][W0], [nf - n][H0][W0] (as PyrBaseArgs)
   int n, nf, W0, H0, padl, padt, Wp, Hp;
   float *out;                    // [nf][Hp][Wp]
+  int stereo;                    // as PyrBaseArgs::stereo
 };
 
 struct PyrDownArgs {
@@ -153,6 +157,9 @@ struct UpArgs {
   int form;           // nop = 2: 0 k_upsample_rows, 1 k_upsample_h<4>, 2 k_upsample_h<8> (option "up_form")
   int f16, planar;    // output format (ofdis_out_format): `out` holds binary16 values / is [n][nop][H0][W0].  Either set:
                       // one store form per nop whatever `form` (k_upsample_h<4>, k_upsample_rows1, k_upsample)
+  float *out_r;       // ofdis_run_stereo_u8 (nop = 1, the plain format), else NULL: frames 0 .. n_l - 1 go to `out`; frame
+  int n_l;            // n_l + i is the mirrored view of pair i and goes to out_r[i], its column x stored at W0 - 1 - x
+                      // with the sign bit flipped -- the right view's disparity in the right view's coordinates
 };
 
 // The finest level's flow x 2^sc_l in an output format, no upsample (ofdis_out_format, OFDIS_OUT_LEVEL).
@@ -181,6 +188,15 @@ struct FbArgs {
   float alpha, beta;
 };
 
+// Left-right consistency of two full-resolution disparity fields (include/ofdis.h: ofdis_lr_check).
+struct LrArgs {
+  const float *dl, *dr;    // [n][H][W]
+  uint8_t *occ_l, *occ_r;  // [n][H][W] mask codes 0 / 1 / 2, or NULL
+  float *err_l, *err_r;    // [n][H][W] squared round-trip error, or NULL
+  int n, W, H;             // W * H < 2^31
+  float alpha, beta;
+};
+
 // Backward warp of u8 frames along a flow view (include/ofdis.h: ofdis_warp_u8).
 struct WarpArgs {
   const uint8_t *img;  // [n][H][W][noc]
@@ -196,6 +212,7 @@ struct WarpArgs {
 
 void launch_warp(const WarpArgs &a, hipStream_t s);
 void launch_fb_check(const FbArgs &a, hipStream_t s);
+void launch_lr_check(const LrArgs &a, hipStream_t s);
 void launch_init_area(const InitArgs &a, hipStream_t s);
 void warm_kernels_module(hipStream_t s);  // one empty launch per kernel translation unit: loads its code object
 void warm_tvrb_module(hipStream_t s);

@@ -89,23 +89,43 @@ __device__ __forceinline__ uint3 xcd_block() {
 
 // ------------------------------------------------------------------------------------------------ pyramid
 
+// ST (ofdis_run_stereo_u8): a.n stereo pairs, nf = 4 a.n frames -- left, mirrored right, right, mirrored left (n of
+// each).  A mirrored frame is mir(I)[y][x] = I[y][W0 - 1 - x], read through the column map, never stored: the replicate
+// clamp and padl apply in mirrored coordinates, then the column is mapped.  The base level is an integer box sum, so
+// the order in which a block's columns are read is free: the block of mirrored columns [x0, x0 + B) is the block of
+// original columns [W0 - x0 - B, W0 - x0), and the aligned fast paths apply to that.  ST = false is the code as it was.
+template <bool ST>
+__device__ __forceinline__ const uint8_t *pyr_src(const PyrBaseArgs &a, int f, long fs, bool &mir) {
+  if constexpr (ST) {
+    const int q = f / a.n, i = f - q * a.n;
+    mir = (q & 1) != 0;
+    return (q == 0 || q == 3 ? a.img_a : a.img_b) + (long)i * fs;
+  } else {
+    mir = false;
+    return f < a.n ? a.img_a + (long)f * fs : a.img_b + (long)(f - a.n) * fs;
+  }
+}
+
+template <bool ST = false>
 __global__ __launch_bounds__(256) void k_pyr_base(PyrBaseArgs a) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
   if (x >= a.w) return;
   const long idx = ((long)f * a.h + y) * a.w + x;
   const long fs = (long)a.H0 * a.W0 * a.noc;
-  const uint8_t *src = f < a.n ? a.img_a + (long)f * fs : a.img_b + (long)(f - a.n) * fs;
+  bool mir;
+  const uint8_t *src = pyr_src<ST>(a, f, fs, mir);
   const int B = 1 << a.log2s;
   // 2^l x 2^l box mean of the replicate-padded u8 image.  The sum is an integer < 2^24 and the scale
   // is a power of two, so this equals the reference's repeated ((a+b)+(c+d))*0.25 exactly (l <= 8).
   const float scale = 1.0f / (float)(1 << (2 * a.log2s));
   const int x0 = x * B - a.padl;
+  const int xs = ST && mir ? a.W0 - x0 - B : x0;  // the block's first column in the stored image
   // fast path: intensity image, block row fully inside and 16-byte aligned -> uint4 loads + v_sad_u8
-  if (a.noc == 1 && B >= 16 && x0 >= 0 && x0 + B <= a.W0 && ((((uintptr_t)src) + x0) & 15) == 0 && (a.W0 & 15) == 0) {
+  if (a.noc == 1 && B >= 16 && x0 >= 0 && x0 + B <= a.W0 && ((((uintptr_t)src) + xs) & 15) == 0 && (a.W0 & 15) == 0) {
     unsigned sum = 0;
     for (int by = 0; by < B; ++by) {
       const int yy = clampi(y * B + by - a.padt, 0, a.H0 - 1);
-      const uint4 *row = reinterpret_cast<const uint4 *>(src + (long)yy * a.W0 + x0);
+      const uint4 *row = reinterpret_cast<const uint4 *>(src + (long)yy * a.W0 + xs);
       for (int q = 0; q < B / 16; ++q) {
         const uint4 v = row[q];
         sum = __builtin_amdgcn_sad_u8(v.x, 0u, sum);
@@ -122,7 +142,10 @@ __global__ __launch_bounds__(256) void k_pyr_base(PyrBaseArgs a) {
     for (int by = 0; by < B; ++by) {
       const int yy = clampi(y * B + by - a.padt, 0, a.H0 - 1);
       const uint8_t *row = src + (long)yy * a.W0 * a.noc + c;
-      for (int bx = 0; bx < B; ++bx) sum += row[clampi(x0 + bx, 0, a.W0 - 1) * a.noc];
+      for (int bx = 0; bx < B; ++bx) {
+        const int xc = clampi(x0 + bx, 0, a.W0 - 1);
+        sum += row[(ST && mir ? a.W0 - 1 - xc : xc) * a.noc];
+      }
     }
     a.out[idx * a.noc + c] = (float)sum * scale;
   }
@@ -131,7 +154,7 @@ __global__ __launch_bounds__(256) void k_pyr_base(PyrBaseArgs a) {
 // Intensity images, 2^L = 4..32: one output pixel per thread over the flattened [nf][h][w] range (full
 // waves even for narrow levels), the 2^L rows of the block unrolled so all loads are in flight at once,
 // 4 / 8 / 16-byte loads summed with v_sad_u8.  Blocks that need horizontal clamping take the byte loop.
-template <int L>
+template <int L, bool ST = false>
 __global__ __launch_bounds__(256) void k_pyr_base_gray(PyrBaseArgs a) {
   constexpr int B = 1 << L;
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -140,17 +163,19 @@ __global__ __launch_bounds__(256) void k_pyr_base_gray(PyrBaseArgs a) {
   const long r = t / a.w;
   const int y = (int)(r % a.h), f = (int)(r / a.h);
   const long fs = (long)a.H0 * a.W0;
-  const uint8_t *src = f < a.n ? a.img_a + (long)f * fs : a.img_b + (long)(f - a.n) * fs;
+  bool mir;
+  const uint8_t *src = pyr_src<ST>(a, f, fs, mir);
   const float scale = 1.0f / (float)(1 << (2 * L));
   const int x0 = x * B - a.padl;
+  const int xs = ST && mir ? a.W0 - x0 - B : x0;  // the block's first column in the stored image (pyr_src)
   constexpr int VB = B >= 16 ? 16 : B;  // bytes per load
   unsigned sum = 0;
-  if (x0 >= 0 && x0 + B <= a.W0 && ((((uintptr_t)src) + x0) % VB) == 0 && (a.W0 % VB) == 0) {
+  if (x0 >= 0 && x0 + B <= a.W0 && ((((uintptr_t)src) + xs) % VB) == 0 && (a.W0 % VB) == 0) {
     unsigned acc[B];
 #pragma unroll
     for (int by = 0; by < B; ++by) {
       const int yy = clampi(y * B + by - a.padt, 0, a.H0 - 1);
-      const uint8_t *row = src + (long)yy * a.W0 + x0;
+      const uint8_t *row = src + (long)yy * a.W0 + xs;
       unsigned s2 = 0;
       if (VB == 16) {
 #pragma unroll
@@ -176,7 +201,10 @@ __global__ __launch_bounds__(256) void k_pyr_base_gray(PyrBaseArgs a) {
     for (int by = 0; by < B; ++by) {
       const int yy = clampi(y * B + by - a.padt, 0, a.H0 - 1);
       const uint8_t *row = src + (long)yy * a.W0;
-      for (int bx = 0; bx < B; ++bx) sum += row[clampi(x0 + bx, 0, a.W0 - 1)];
+      for (int bx = 0; bx < B; ++bx) {
+        const int xc = clampi(x0 + bx, 0, a.W0 - 1);
+        sum += row[ST && mir ? a.W0 - 1 - xc : xc];
+      }
     }
   }
   a.out[t] = (float)sum * scale;
@@ -187,7 +215,7 @@ __global__ __launch_bounds__(256) void k_pyr_base_gray(PyrBaseArgs a) {
 // byte mask -- exact integer sums like k_pyr_base's byte loop (the order of an integer sum is free).  Blocks that
 // need horizontal clamping or are not dword-aligned take the byte loop.  Config C: 4.22 -> 1.50 ms per step
 // (profiles/r06/s37).
-template <int L>
+template <int L, bool ST = false>
 __global__ __launch_bounds__(256) void k_pyr_base_rgb(PyrBaseArgs a) {
   constexpr int B = 1 << L, ND = 3 * B / 4;  // dwords per block row
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -196,11 +224,13 @@ __global__ __launch_bounds__(256) void k_pyr_base_rgb(PyrBaseArgs a) {
   const long r = t / a.w;
   const int y = (int)(r % a.h), f = (int)(r / a.h);
   const long fs = (long)a.H0 * a.W0 * 3;
-  const uint8_t *src = f < a.n ? a.img_a + (long)f * fs : a.img_b + (long)(f - a.n) * fs;
+  bool mir;
+  const uint8_t *src = pyr_src<ST>(a, f, fs, mir);
   const float scale = 1.0f / (float)(1 << (2 * L));
   const int x0 = x * B - a.padl;
+  const int xs = ST && mir ? a.W0 - x0 - B : x0;  // the block's first column in the stored image (pyr_src)
   unsigned sum[3] = {0u, 0u, 0u};
-  if (x0 >= 0 && x0 + B <= a.W0 && (((uintptr_t)src + 3 * (long)x0) & 3) == 0 && ((3 * a.W0) & 3) == 0) {
+  if (x0 >= 0 && x0 + B <= a.W0 && (((uintptr_t)src + 3 * (long)xs) & 3) == 0 && ((3 * a.W0) & 3) == 0) {
     // byte k of a 12-byte group (pixels 4i .. 4i + 3) belongs to channel k % 3: its dword k / 4, byte k % 4
     constexpr unsigned M[3][3] = {{0xFF0000FFu, 0x00FF0000u, 0x0000FF00u},
                                   {0x0000FF00u, 0xFF0000FFu, 0x00FF0000u},
@@ -209,7 +239,7 @@ __global__ __launch_bounds__(256) void k_pyr_base_rgb(PyrBaseArgs a) {
 #pragma unroll
     for (int by = 0; by < B; ++by) {
       const int yy = clampi(y * B + by - a.padt, 0, a.H0 - 1);
-      const unsigned *row = reinterpret_cast<const unsigned *>(src + ((long)yy * a.W0 + x0) * 3);
+      const unsigned *row = reinterpret_cast<const unsigned *>(src + ((long)yy * a.W0 + xs) * 3);
 #pragma unroll
       for (int k = 0; k < ND; ++k) v[by][k] = row[k];
     }
@@ -224,7 +254,10 @@ __global__ __launch_bounds__(256) void k_pyr_base_rgb(PyrBaseArgs a) {
       for (int by = 0; by < B; ++by) {
         const int yy = clampi(y * B + by - a.padt, 0, a.H0 - 1);
         const uint8_t *row = src + (long)yy * a.W0 * 3 + c;
-        for (int bx = 0; bx < B; ++bx) sum[c] += row[clampi(x0 + bx, 0, a.W0 - 1) * 3];
+        for (int bx = 0; bx < B; ++bx) {
+          const int xc = clampi(x0 + bx, 0, a.W0 - 1);
+          sum[c] += row[(ST && mir ? a.W0 - 1 - xc : xc) * 3];
+        }
       }
   }
 #pragma unroll
@@ -257,15 +290,26 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 
 // Gradient-magnitude base level (oracle: ofo_build_pyramid_ex): Sobel ksize 3 x 1/8 with reflect-101 at the
 // padded frame's border, on the replicate-padded u8 frame; same expression trees as k_pyr_pad_grad.
+// ST: the four-frame stereo layout of pyr_src, the mirrored frames read through the column map.
+template <bool ST = false>
 __global__ __launch_bounds__(256) void k_pyr_gradmag(PyrGradmagArgs a) {
   const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y, f = blockIdx.z;
   if (X >= a.Wp) return;
   const long fs = (long)a.H0 * a.W0;
-  const uint8_t *src = f < a.n ? a.img_a + (long)f * fs : a.img_b + (long)(f - a.n) * fs;
+  bool mir = false;
+  const uint8_t *src;
+  if constexpr (ST) {
+    const int q = f / a.n, i = f - q * a.n;
+    mir = (q & 1) != 0;
+    src = (q == 0 || q == 3 ? a.img_a : a.img_b) + (long)i * fs;
+  } else {
+    src = f < a.n ? a.img_a + (long)f * fs : a.img_b + (long)(f - a.n) * fs;
+  }
   const int xm = reflect101(X - 1, a.Wp), xp = reflect101(X + 1, a.Wp);
   const int ym = reflect101(Y - 1, a.Hp), yp = reflect101(Y + 1, a.Hp);
   auto px = [&](int xx, int yy) {  // replicate divisibility padding (run_dense.cpp:307-311)
-    return (float)src[(long)clampi(yy - a.padt, 0, a.H0 - 1) * a.W0 + clampi(xx - a.padl, 0, a.W0 - 1)];
+    const int xc = clampi(xx - a.padl, 0, a.W0 - 1);
+    return (float)src[(long)clampi(yy - a.padt, 0, a.H0 - 1) * a.W0 + (ST && mir ? a.W0 - 1 - xc : xc)];
   };
   const float tm = px(xp, ym) - px(xm, ym);
   const float t0 = px(xp, Y) - px(xm, Y);
@@ -352,13 +396,21 @@ __global__ __launch_bounds__(256) void k_pyr_pad_grad_v(PyrPadGradArgs a) {
 // ---- launch
 void launch_pyr_base(const PyrBaseArgs &a, hipStream_t s) {
   const unsigned blocks = ceil_div((long)a.nf * a.h * a.w, 256);
+  if (a.stereo) {  // the same forms and geometry on the four-frame layout
+    if (a.noc == 1 && pick<2, 3, 4, 5>(a.log2s, [&](auto L) { k_pyr_base_gray<L, true><<<blocks, 256, 0, s>>>(a); })) return;
+    if (a.noc == 3 && a.rgb_sad && pick<2, 3, 4>(a.log2s, [&](auto L) { k_pyr_base_rgb<L, true><<<blocks, 256, 0, s>>>(a); }))
+      return;
+    k_pyr_base<true><<<dim3(ceil_div(a.w, 256), a.h, a.nf), 256, 0, s>>>(a);
+    return;
+  }
   if (a.noc == 1 && pick<2, 3, 4, 5>(a.log2s, [&](auto L) { k_pyr_base_gray<L><<<blocks, 256, 0, s>>>(a); })) return;
   if (a.noc == 3 && a.rgb_sad && pick<2, 3, 4>(a.log2s, [&](auto L) { k_pyr_base_rgb<L><<<blocks, 256, 0, s>>>(a); }))
     return;
   k_pyr_base<<<dim3(ceil_div(a.w, 256), a.h, a.nf), 256, 0, s>>>(a);
 }
 void launch_pyr_gradmag(const PyrGradmagArgs &a, hipStream_t s) {
-  k_pyr_gradmag<<<dim3(ceil_div(a.Wp, 256), a.Hp, a.nf), 256, 0, s>>>(a);
+  if (a.stereo) k_pyr_gradmag<true><<<dim3(ceil_div(a.Wp, 256), a.Hp, a.nf), 256, 0, s>>>(a);
+  else k_pyr_gradmag<<<dim3(ceil_div(a.Wp, 256), a.Hp, a.nf), 256, 0, s>>>(a);
 }
 void launch_pyr_down(const PyrDownArgs &a, hipStream_t s) {
   k_pyr_down<<<std::min(ceil_div((long)a.n2 * a.h * a.w * a.noc, 256), 1u << 22), 256, 0, s>>>(a);  // grid-stride beyond
@@ -5346,8 +5398,16 @@ __global__ __launch_bounds__(256) void k_upsample_h(UpArgs a) {
 
 // The same for depth (nop = 1): lane i of wave wv owns the four output columns xb + 4i .. xb + 4i + 3
 // (xb = block + 256 wv): one 16-byte store per row, 1 KiB contiguous per wave-instruction.
-template <class T = float>
+// ST (ofdis_run_stereo_u8, float32): frame n_l + i is the mirrored view of pair i.  Its values are computed as ever, in
+// mirrored coordinates; the store goes to out_r[i] at column W0 - 1 - x with the sign bit flipped (a lane's four values
+// reversed in one 16-byte store: W0 % 4 == 0 keeps it aligned), so the right view's disparity is written once, in the
+// right view's coordinates, and no pass over the float field follows.  ST = false is the code as it was.
+__device__ __forceinline__ float flip_sign(float v) {
+  return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) ^ 0x80000000u);  // a NaN keeps its payload
+}
+template <class T = float, bool ST = false>
 __global__ __launch_bounds__(256) void k_upsample_rows1(UpArgs a) {
+  static_assert(!ST || std::is_same<T, float>::value, "the stereo store form is float32");
   __shared__ float src[kUpSrcRows][kUpCols / 2 + 8];
   const int y0 = blockIdx.y * kUpRows, f = blockIdx.z;
   const int dx0 = blockIdx.x * kUpCols + a.offx;
@@ -5411,6 +5471,20 @@ __global__ __launch_bounds__(256) void k_upsample_rows1(UpArgs a) {
       const float h1 = lin[q] ? s10 * (1.f - fxs[q]) + src[j1][c + 1] * fxs[q] : s10;
       v[q] = h0 * b0 + h1 * b1;
     }
+    if constexpr (ST) {
+      if (f >= a.n_l) {
+        float *rr = a.out_r + ((long)(f - a.n_l) * a.H0 + y) * a.W0;
+        if (xb + 4 <= a.W0) {
+          *reinterpret_cast<v4f *>(rr + (a.W0 - 4 - xb)) =
+              v4f{flip_sign(v[3]), flip_sign(v[2]), flip_sign(v[1]), flip_sign(v[0])};
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (xb + q < a.W0) rr[a.W0 - 1 - xb - q] = flip_sign(v[q]);
+        }
+        continue;
+      }
+    }
     T *row = reinterpret_cast<T *>(a.out) + ((long)f * a.H0 + y) * a.W0;
     if (xb + 4 <= a.W0) {
       if constexpr (std::is_same<T, float>::value)
@@ -5428,12 +5502,28 @@ __global__ __launch_bounds__(256) void k_upsample_rows1(UpArgs a) {
 // Generic path (any nop, 2^l = 1, unaligned output): one output pixel per thread.  Formats: T and PLANAR as above;
 // PAIR (binary16, interleaved, nop = 2, output 4-byte aligned): the pixel's two components in one 4-byte store.  A
 // planar binary16 row of an odd-width frame starts 2-byte aligned on every other row: 2-byte stores.
-template <class T = float, bool PLANAR = false, bool PAIR = false>
+// ST (nop = 1, the plain format): the mirrored frames' store of k_upsample_rows1<float, true>, one pixel per thread.
+template <class T = float, bool PLANAR = false, bool PAIR = false, bool ST = false>
 __global__ __launch_bounds__(256) void k_upsample(UpArgs a) {
+  static_assert(!ST || kPlainOut<T, PLANAR>, "the stereo store form is the plain format");
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
   if (x >= a.W0) return;
   const long plane = (long)a.wl * a.hl;
   const float *F = a.flow + (long)f * a.nop * plane;
+  if constexpr (ST) {  // nop = 1
+    if (f >= a.n_l) {
+      float *o = a.out_r + ((long)(f - a.n_l) * a.H0 + y) * a.W0 + (a.W0 - 1 - x);
+      if (a.log2s == 0) {
+        *o = flip_sign(F[(long)(y + a.offy) * a.wl + (x + a.offx)]);
+        return;
+      }
+      const double scale = 1.0 / (double)(1 << a.log2s);
+      const YTap yt = ytap(y + a.offy, scale, a.hl);
+      *o = flip_sign(up_px(F, (long)yt.r0 * a.wl, (long)yt.r1 * a.wl, xtap(x + a.offx, scale, a.wl),
+                           (float)(1 << a.log2s), 1.f - yt.fy, yt.fy));
+      return;
+    }
+  }
   T *O = reinterpret_cast<T *>(a.out);
   T *out = PLANAR ? O + ((long)f * a.nop * a.H0 + y) * a.W0 + x : O + (((long)f * a.H0 + y) * a.W0 + x) * a.nop;
   const long ks = PLANAR ? (long)a.H0 * a.W0 : 1;  // component stride
@@ -5536,6 +5626,13 @@ void launch_level_out(const LevelOutArgs &a, hipStream_t s) {
 }
 
 void launch_upsample(const UpArgs &a, hipStream_t s) {
+  if (a.out_r) {  // ofdis_run_stereo_u8: nop = 1, the plain format; the depth forms and their geometry
+    if (a.log2s >= 1 && a.log2s <= 9 && (a.W0 % 4) == 0 && (((uintptr_t)a.out | (uintptr_t)a.out_r) % 16) == 0)
+      k_upsample_rows1<float, true><<<dim3(ceil_div(a.W0, kUpCols), ceil_div(a.H0, kUpRows), a.n), 256, 0, s>>>(a);
+    else
+      k_upsample<float, false, false, true><<<dim3(ceil_div(a.W0, 256), a.H0, a.n), 256, 0, s>>>(a);
+    return;
+  }
   if (a.f16 || (a.planar && a.nop == 2)) {
     const bool planar = a.planar && a.nop == 2;
     if (a.f16)
@@ -5656,6 +5753,99 @@ void launch_fb_check(const FbArgs &a0, hipStream_t s) {
         k_fb_check<O != 0, E != 0, 4><<<grid, 256, 0, s>>>(a);
       else
         k_fb_check<O != 0, E != 0, 1><<<grid, 256, 0, s>>>(a);
+    };
+    if (occ && err) go(Int<1>{}, Int<1>{});
+    else if (occ) go(Int<1>{}, Int<0>{});
+    else go(Int<0>{}, Int<1>{});
+  }
+}
+
+// ------------------------------------------------------------------------------ left-right check
+// The stereo counterpart (include/ofdis.h: ofdis_lr_check): one-component fields, a horizontal gather of two taps.
+// Both views in one launch, blockIdx.z = 2 * frame + view: view 0 walks the left disparity and gathers the right one
+// at x + D(x), view 1 the other way round.  Bit for bit k_fb_check on the fields (d, 0) while both are finite.
+namespace {
+
+// One pixel: u = its own disparity, O = the other field's row y.  Returns the mask code, err by reference.
+__device__ __forceinline__ unsigned lr_pixel(const float *__restrict__ O, int W, int x, float u, float alpha,
+                                             float beta, float &err) {
+  const float px = (float)x + u;
+  const bool inside = px >= 0.f && px <= (float)(W - 1);  // false for NaN
+  // no branch around the gather (as fb_pixel): a pixel that leaves the frame reads the taps of column 0
+  const float pxs = inside ? px : 0.f;
+  // in [0, W - 1]; the integer min is a no-op below 2^24 columns, where (float)(W - 1) is exact (as warp_pixel)
+  const int x0 = min((int)floorf(pxs), W - 1);
+  const int x1 = x0 + 1 < W ? x0 + 1 : W - 1;
+  const float ax = pxs - (float)x0;
+  const float b0 = O[x0], b1 = O[x1];
+  const float b = b0 + ax * (b1 - b0);
+  const float d = u + b;
+  const float e = d * d;
+  const float mag = u * u + b * b;
+  const float thr = alpha * mag + beta;
+  err = inside ? (e != e ? __builtin_nanf("") : e) : __builtin_inff();  // the canonical quiet NaN (fb_pixel)
+  return inside ? (e <= thr ? 0u : 1u) : 2u;  // NaN err -> 1
+}
+
+// PX = 4: four consecutive pixels of a row per thread -- its own disparities as one 16-byte load, the four mask bytes
+// as one dword, the errors as one 16-byte store (W % 4 == 0 and aligned pointers: launch_lr_check).  PX = 1: any width
+// and alignment.  OCC / ERR as in k_fb_check.
+template <bool OCC, bool ERR, int PX>
+__global__ __launch_bounds__(256) void k_lr_check(LrArgs a) {
+  const int view = blockIdx.z & 1, f = blockIdx.z >> 1;
+  uint8_t *occ = OCC ? (view ? a.occ_r : a.occ_l) : nullptr;
+  float *errp = ERR ? (view ? a.err_r : a.err_l) : nullptr;
+  if (!occ && !errp) return;
+  const unsigned wq = (unsigned)a.W / PX;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= wq * (unsigned)a.H) return;
+  const int y = (int)(q / wq), x = (int)(q - (unsigned)y * wq) * PX;
+  const long ro = (long)f * a.H * a.W + (long)y * a.W, o = ro + x;
+  const float *D = (view ? a.dr : a.dl) + o;
+  const float *O = (view ? a.dl : a.dr) + ro;
+  float u[PX], e[PX];
+  if constexpr (PX == 4) {
+    const float4_v v = *reinterpret_cast<const float4_v *>(D);
+    u[0] = v.x, u[1] = v.y, u[2] = v.z, u[3] = v.w;
+  } else {
+    u[0] = D[0];
+  }
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < PX; ++i) m |= lr_pixel(O, a.W, x + i, u[i], a.alpha, a.beta, e[i]) << (8 * i);
+  if constexpr (PX == 4) {
+    if (occ) *reinterpret_cast<unsigned *>(occ + o) = m;
+    if (errp) *reinterpret_cast<float4_v *>(errp + o) = float4_v{e[0], e[1], e[2], e[3]};
+  } else {
+    if (occ) occ[o] = (uint8_t)m;
+    if (errp) errp[o] = e[0];
+  }
+}
+
+}  // namespace
+// ---- launch
+void launch_lr_check(const LrArgs &a0, hipStream_t s) {
+  const bool occ = a0.occ_l || a0.occ_r, err = a0.err_l || a0.err_r;
+  if (!occ && !err) return;
+  const bool vec = a0.W % 4 == 0 && ((uintptr_t)a0.dl | (uintptr_t)a0.dr | (uintptr_t)a0.err_l | (uintptr_t)a0.err_r) % 16 == 0 &&
+                   ((uintptr_t)a0.occ_l | (uintptr_t)a0.occ_r) % 4 == 0;
+  const long frame = (long)a0.W * a0.H;
+  const int kSlice = 32767;  // 2 * frames <= 65535 (grid z)
+  for (int f0 = 0; f0 < a0.n; f0 += kSlice) {
+    LrArgs a = a0;
+    a.n = std::min(kSlice, a0.n - f0);
+    a.dl += f0 * frame;
+    a.dr += f0 * frame;
+    if (a.occ_l) a.occ_l += f0 * frame;
+    if (a.occ_r) a.occ_r += f0 * frame;
+    if (a.err_l) a.err_l += f0 * frame;
+    if (a.err_r) a.err_r += f0 * frame;
+    const dim3 grid(ceil_div(frame / (vec ? 4 : 1), 256), 1, 2 * a.n);
+    auto go = [&](auto O, auto E) {
+      if (vec)
+        k_lr_check<O != 0, E != 0, 4><<<grid, 256, 0, s>>>(a);
+      else
+        k_lr_check<O != 0, E != 0, 1><<<grid, 256, 0, s>>>(a);
     };
     if (occ && err) go(Int<1>{}, Int<1>{});
     else if (occ) go(Int<1>{}, Int<0>{});

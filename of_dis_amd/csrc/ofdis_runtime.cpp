@@ -33,7 +33,9 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     // level-grid output that replaces it ("upsample": the plain format alone)
                                     "upsample_f16", "upsample_planar", "upsample_planar_f16", "level_out",
                                     // the warp with a full-resolution flow view / with a level-grid view
-                                    "warp", "warp_level"};
+                                    "warp", "warp_level",
+                                    // the left-right check writing masks only / also an error map
+                                    "lr_check", "lr_check_err"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -46,6 +48,9 @@ struct Plan {
   // (nfr = 2n, bdist = n), or one sequence of n + stride frames (bdist = stride; ofdis_run_sequence_u8)
   int nfr = 0, bdist = 0;
   bool seq = false;
+  // ofdis_run_stereo_u8: n = 2m flow pairs of m stereo pairs -- pair i is (left i, right i), pair m + i is (mirrored
+  // right i, mirrored left i) -- over nfr = 4m frames laid out left, mirrored right, right, mirrored left (bdist = 2m)
+  bool stereo = false;
   int n = 0, W0 = 0, H0 = 0, Wp = 0, Hp = 0, padl = 0, padt = 0, padw = 0, padh = 0;
   int nop = 2, noc = 1, pad = 8, sc_f = 0, sc_l = 0;
   std::vector<LevelGeom> lv;                       // index s - sc_l
@@ -55,7 +60,8 @@ struct Plan {
   bool init = false;    // an initial flow is given: divisibility 2^(sc_f+1) (run_dense.cpp:302)
   bool fb = false;      // usefbcon: backward grid, flow and refinement
   bool bidir = false;   // ofdis_run_bidir_u8: the backward grid, flow and refinement at every level, sc_l included
-  size_t off_up_bw = 0; // bidir without a caller's flow_bw: the full-resolution backward flow [n][H0][W0][2]
+  size_t off_up_bw = 0; // bidir without a caller's flow_bw: the full-resolution backward flow [n][H0][W0][2];
+                        // stereo without a caller's disp_r: the right view's disparity [n / 2][H0][W0]
   bool gradmag = false; // SELECTCHANNEL 2: float level 0 (gradient magnitude) halved down to sc_l
   size_t off_gm = 0;    // its scratch: [nfr][Hp][Wp] + [nfr][Hp/2][Wp/2] (ping-pong)
   size_t total = 0;
@@ -99,6 +105,7 @@ struct ofdis_context {
     const void *flow_bw = nullptr, *occ_fw = nullptr, *occ_bw = nullptr, *err_fw = nullptr, *err_bw = nullptr;
     float alpha = 0.f, beta = 0.f;  // the bidirectional call's extra outputs and thresholds
     int bidir = 0;
+    int stereo = 0;           // ofdis_run_stereo_u8: a / b the left / right images, flow_bw .. beta its outputs
     int seq = 0, stride = 0;  // ofdis_run_sequence_u8: `a` is one array of n + stride frames, b is NULL
     int out_f16 = 0, out_planar = 0, out_level = 0;  // output format: a formatted call on a plain call's buffers
                                                      // records anew, and the other way round
@@ -698,7 +705,7 @@ int check_device(int device) {
 // Pyramid of the batch (run_dense.cpp:299-312,327-328,131-179) into the workspace.
 // Pairs: frames 0..n-1 from a, n..2n-1 from b.  A sequence plan: its n + stride frames from a alone (b unread).
 int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, const uint8_t *b, hipStream_t s) {
-  const int n2 = P.nfr, na = P.seq ? P.nfr : P.n;
+  const int n2 = P.nfr, na = P.seq ? P.nfr : P.stereo ? P.n / 2 : P.n;  // (stereo: the caller's pairs)
   if (P.gradmag) {  // SELECTCHANNEL 2 (run_dense.cpp:139-148): float level 0, then 2x2 means down to sc_l
     float *lvl0 = (float *)(ws + P.off_lvl[0]);
     float *bufA = (float *)(ws + P.off_gm), *bufB = bufA + (size_t)n2 * P.Wp * P.Hp;
@@ -713,6 +720,7 @@ int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, con
     g.padt = P.padt;
     g.Wp = P.Wp;
     g.Hp = P.Hp;
+    g.stereo = P.stereo;
     g.out = P.sc_l == 0 ? lvl0 : bufA;
     timed(c, 0, s, [&] { launch_pyr_gradmag(g, s); });
     const float *src = bufA;
@@ -744,6 +752,7 @@ int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, con
     pb.h = P.lv[0].h;
     pb.out = (float *)(ws + P.off_lvl[0]);
     pb.rgb_sad = c->opt_pyr_rgb;
+    pb.stereo = P.stereo;
     timed(c, 0, s, [&] { launch_pyr_base(pb, s); });
   }
   for (size_t i = 1; i < P.lv.size(); ++i) {
@@ -775,13 +784,15 @@ int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, con
 
 // bidir: 0 plain, 1 both directions, 2 both directions and the full-resolution backward flow kept in the workspace
 // stride: 0 two arrays of n frames, k > 0 one sequence of n + k frames
+// stereo: 0 no, 1 n stereo pairs as 2n flow pairs, 2 the same and the right view's disparity kept in the workspace
 Plan batch_plan(const ofdis_params *p, int n, int width, int height, bool init = false, int bidir = 0,
-                int stride = 0) {
+                int stride = 0, int stereo = 0) {
   const int d = 1 << (p->sc_f + (init ? 1 : 0));  // run_dense.cpp:301-302
   const int padw = (width % d) ? d - width % d : 0, padh = (height % d) ? d - height % d : 0;
-  Plan P = make_plan(p, n, width + padw, height + padh, p->p_samp_s, init, bidir != 0, stride);
+  Plan P = make_plan(p, stereo ? 2 * n : n, width + padw, height + padh, p->p_samp_s, init, bidir != 0, stride);
+  P.stereo = stereo != 0;
   P.off_up_bw = P.total;
-  if (bidir == 2) P.total = align_up(P.total + sizeof(float) * (size_t)n * width * height * P.nop);
+  if (bidir == 2 || stereo == 2) P.total = align_up(P.total + sizeof(float) * (size_t)n * width * height * P.nop);
   P.W0 = width;
   P.H0 = height;
   P.padw = padw;
@@ -851,8 +862,9 @@ namespace {
 // x 2^sc_l + INTER_LINEAR upsample + crop of the finest level's flow in workspace ws (run_dense.cpp:407-415).
 // A format other than the plain one (never with `backward`): the formatted store forms, or for the level grid no
 // upsample at all -- the level plane x 2^sc_l in the format.
+// disp_r (a stereo plan): the mirrored pairs' half of the batch goes there, mirrored back and negated by the store.
 int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, void *flow_out, hipStream_t s,
-                 bool backward = false, const OutFmt &fmt = OutFmt()) {
+                 bool backward = false, const OutFmt &fmt = OutFmt(), float *disp_r = nullptr) {
   if (fmt.level) {
     LevelOutArgs lo{};
     lo.flow = (const float *)(ws + P.off_flow[0]);
@@ -884,6 +896,8 @@ int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *
                                  : c->opt_up_form;
   up.f16 = fmt.f16;
   up.planar = fmt.planar;
+  up.out_r = disp_r;
+  up.n_l = disp_r ? P.n / 2 : P.n;
   timed(c, fmt.f16 ? (fmt.planar ? 16 : 14) : fmt.planar ? 15 : 10, s, [&] { launch_upsample(up, s); });
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
@@ -915,10 +929,13 @@ struct BidirOut {
   uint8_t *occ_fw = nullptr, *occ_bw = nullptr;
   float *err_fw = nullptr, *err_bw = nullptr;
   float alpha = 0.f, beta = 0.f;
+  // ofdis_run_stereo_u8: the same five outputs for the right view (flow_bw = disp_r, one component; occ_fw / err_fw
+  // the left view's), the check ofdis_lr_check
+  bool stereo = false;
   bool checks() const { return occ_fw || occ_bw || err_fw || err_bw; }
   BidirOut at(size_t f0, size_t px) const {
     BidirOut o = *this;
-    if (flow_bw) o.flow_bw += f0 * px * 2;
+    if (flow_bw) o.flow_bw += f0 * px * (stereo ? 1 : 2);
     if (occ_fw) o.occ_fw += f0 * px;
     if (occ_bw) o.occ_bw += f0 * px;
     if (err_fw) o.err_fw += f0 * px;
@@ -943,6 +960,25 @@ int run_fb_check(ofdis_context *c, const float *fw, const float *bw, int n, int 
   fa.alpha = o.alpha;
   fa.beta = o.beta;
   timed(c, o.err_fw || o.err_bw ? 13 : 12, s, [&] { launch_fb_check(fa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// The left-right check of n frames (timer "lr_check_err" when an error map is written, else "lr_check").
+int run_lr_check(ofdis_context *c, const float *dl, const float *dr, int n, int width, int height, const BidirOut &o,
+                 hipStream_t s) {
+  LrArgs la{};
+  la.dl = dl;
+  la.dr = dr;
+  la.occ_l = o.occ_fw;
+  la.occ_r = o.occ_bw;
+  la.err_l = o.err_fw;
+  la.err_r = o.err_bw;
+  la.n = n;
+  la.W = width;
+  la.H = height;
+  la.alpha = o.alpha;
+  la.beta = o.beta;
+  timed(c, o.err_fw || o.err_bw ? 21 : 20, s, [&] { launch_lr_check(la, s); });
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
@@ -998,6 +1034,11 @@ int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, 
   if (init && (rc = run_init(c, ws, P, p, init, s))) return rc;
   rc = run_levels(c, ws, P, p, s, init ? (const float *)(ws + P.off_init) : nullptr, nullptr);
   if (rc) return rc;
+  if (P.stereo) {  // both views' fields from the one batch (bd, the plain format), then the check
+    float *disp_r = bd->flow_bw ? bd->flow_bw : (float *)(ws + P.off_up_bw);
+    if ((rc = run_upsample(c, ws, P, p, flow_out, s, false, fmt, disp_r))) return rc;
+    return bd->checks() ? run_lr_check(c, (const float *)flow_out, disp_r, P.n / 2, P.W0, P.H0, *bd, s) : OFDIS_OK;
+  }
   rc = run_upsample(c, ws, P, p, flow_out, s, false, fmt);
   if (!rc && wo) {  // ofdis_run_warp_u8: flow_out is the chunk's float32 level grid (fmt), img_b warped by it
     ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
@@ -1059,30 +1100,31 @@ struct CallPlan {
 };
 
 int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int height, bool init, bool capturing,
-            CallPlan &cp, int bidir = 0, int stride = 0) {
+            CallPlan &cp, int bidir = 0, int stride = 0, int stereo = 0) {
   cp.n = n;
-  c->call_frames = n;
+  c->call_frames = stereo ? 2 * n : n;  // (a stereo pair is two flow pairs)
   c->call_lanes = 1;
   cp.width = width;
   cp.height = height;
   cp.init = init;
   // a stage capture (frame 0's per-scale flow) runs the batch as one launch on one stream, whatever the
   // stream / chunk options; it is refused only for batches beyond the launch-size cap
-  const int nstreams = capturing ? 1 : stream_count(c, n);
+  const int nstreams = capturing ? 1 : stream_count(c, c->call_frames);
   int chunk = capturing ? n : c->opt_chunk > 0 ? std::min(c->opt_chunk, n) : (n + nstreams - 1) / nstreams;
-  chunk = std::min(chunk, tv_frame_cap(p, width, height));
+  // chunks count stereo pairs: two flow pairs of the launch-size cap each, four frames of the pyramid kernels' grid z
+  chunk = std::min(chunk, stereo ? std::min(tv_frame_cap(p, width, height) / 2, 16383) : tv_frame_cap(p, width, height));
   if (chunk < 1) return OFDIS_ERR_INVALID_ARGUMENT;
   cp.chunk = chunk;
   cp.nchunks = (n + chunk - 1) / chunk;
   if (cp.nchunks > 1 && capturing) return OFDIS_ERR_UNSUPPORTED;
   if (cp.nchunks == 1) {
     cp.kind = CallPlan::kSingle;
-    cp.whole = batch_plan(p, n, width, height, init, bidir, stride);
+    cp.whole = batch_plan(p, n, width, height, init, bidir, stride, stereo);
     return ensure_ws(c, cp.whole.total);
   }
   cp.kind = CallPlan::kRoundRobin;
   for (int ch = 0; ch < cp.nchunks; ++ch)
-    cp.parts.push_back(batch_plan(p, std::min(chunk, n - ch * chunk), width, height, init, bidir, stride));
+    cp.parts.push_back(batch_plan(p, std::min(chunk, n - ch * chunk), width, height, init, bidir, stride, stereo));
   cp.lanes = std::min(nstreams, cp.nchunks);
   c->call_lanes = cp.lanes;
   return ensure_lanes(c, cp.lanes, cp.parts[0].total);
@@ -1165,7 +1207,9 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
               int stride = 0, const OutFmt &fmt = OutFmt(), const WarpOut *wo = nullptr) {
   const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
   CallPlan cp;
-  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, bd ? (bd->flow_bw ? 1 : 2) : 0, stride);
+  const int keep = bd ? (bd->flow_bw ? 1 : 2) : 0;  // 2: the second field stays in the workspace
+  const bool stereo = bd && bd->stereo;
+  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, stereo ? 0 : keep, stride, stereo ? keep : 0);
   if (rc) return rc;
   {  // a chunk of m pairs from pair f0 writes the bytes [f0, f0 + m) * out_pair of flow_out
     const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
@@ -1191,7 +1235,7 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
   key.seq = stride > 0; key.stride = stride;  // a sequence call on a plain call's buffers records anew
   key.out_f16 = fmt.f16; key.out_planar = fmt.planar; key.out_level = fmt.level;
   if (bd) {  // a plain call after a bidirectional one on the same buffers records anew, and the other way round
-    key.bidir = 1; key.flow_bw = bd->flow_bw; key.occ_fw = bd->occ_fw; key.occ_bw = bd->occ_bw;
+    key.bidir = !bd->stereo; key.stereo = bd->stereo; key.flow_bw = bd->flow_bw; key.occ_fw = bd->occ_fw; key.occ_bw = bd->occ_bw;
     key.err_fw = bd->err_fw; key.err_bw = bd->err_bw; key.alpha = bd->alpha; key.beta = bd->beta;
   }
   if (wo) {  // (key.out is then the level-grid buffer)
@@ -1393,17 +1437,18 @@ int ofdis_run_bidir_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *im
   return rc ? rc : rc2;
 }
 
-int ofdis_run_bidir_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
-                            const ofdis_params *p, float alpha, float beta, float *flow_fw, float *flow_bw,
-                            uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw) {
-  if (!c || !img_a || !img_b || !flow_fw || n <= 0 || width <= 0 || height <= 0 || !p)
-    return OFDIS_ERR_INVALID_ARGUMENT;
+extern "C++" {  // (a template)
+namespace {
+// Host form of a call on two images that returns two fields of `comp` components, two masks and two error maps, any
+// but the first field optional (ofdis_run_bidir_u8: comp = 2, ofdis_run_stereo_u8: comp = 1).  One device block: the two
+// images, then (each at a multiple of 256 bytes) the outputs the caller asked for; call(img_a, img_b, f, u) issues
+// the device form on the context's stream with the device pointers (NULL where the host pointer is).  Synchronous.
+template <class Call>
+int two_field_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, size_t px, int noc, int comp,
+                   float *const (&host_f)[4], uint8_t *const (&host_u)[2], Call &&call) {
   HIP_OK(hipSetDevice(c->device));
-  const size_t px = (size_t)n * width * height, in = px * p->noc;
-  // one device block: the two images, then (each at a multiple of 256 bytes) the outputs the caller asked for
-  float *const host_f[4] = {flow_fw, flow_bw, err_fw, err_bw};
-  uint8_t *const host_u[2] = {occ_fw, occ_bw};
-  const size_t bytes_f[4] = {px * 2 * sizeof(float), px * 2 * sizeof(float), px * sizeof(float), px * sizeof(float)};
+  const size_t in = px * noc;
+  const size_t bytes_f[4] = {px * comp * sizeof(float), px * comp * sizeof(float), px * sizeof(float), px * sizeof(float)};
   size_t off_f[4], off_u[2], total = align_up(in) * 2;
   for (int k = 0; k < 4; ++k) {
     off_f[k] = total;
@@ -1420,12 +1465,13 @@ int ofdis_run_bidir_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_
     if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
     return rc == OFDIS_OK;
   };
-  auto dev_f = [&](int k) { return host_f[k] ? (float *)(d + off_f[k]) : nullptr; };
-  auto dev_u = [&](int k) { return host_u[k] ? (uint8_t *)(d + off_u[k]) : nullptr; };
+  float *dev_f[4];
+  uint8_t *dev_u[2];
+  for (int k = 0; k < 4; ++k) dev_f[k] = host_f[k] ? (float *)(d + off_f[k]) : nullptr;
+  for (int k = 0; k < 2; ++k) dev_u[k] = host_u[k] ? (uint8_t *)(d + off_u[k]) : nullptr;
   if (step(hipMemcpyAsync(d, img_a, in, hipMemcpyHostToDevice, c->stream)) &&
       step(hipMemcpyAsync(d + align_up(in), img_b, in, hipMemcpyHostToDevice, c->stream))) {
-    rc = ofdis_run_bidir_u8(c, (const uint8_t *)d, (const uint8_t *)(d + align_up(in)), n, width, height, p, alpha,
-                            beta, dev_f(0), dev_f(1), dev_u(0), dev_u(1), dev_f(2), dev_f(3), c->stream);
+    rc = call((const uint8_t *)d, (const uint8_t *)(d + align_up(in)), dev_f, dev_u);
     if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
       for (int k = 0; k < 4; ++k)
         if (host_f[k]) step(hipMemcpy(host_f[k], d + off_f[k], bytes_f[k], hipMemcpyDeviceToHost));
@@ -1435,6 +1481,89 @@ int ofdis_run_bidir_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_
   }
   hipFree(d);
   return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int ofdis_run_bidir_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                            const ofdis_params *p, float alpha, float beta, float *flow_fw, float *flow_bw,
+                            uint8_t *occ_fw, uint8_t *occ_bw, float *err_fw, float *err_bw) {
+  if (!c || !img_a || !img_b || !flow_fw || n <= 0 || width <= 0 || height <= 0 || !p)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  float *const host_f[4] = {flow_fw, flow_bw, err_fw, err_bw};
+  uint8_t *const host_u[2] = {occ_fw, occ_bw};
+  return two_field_host(c, img_a, img_b, (size_t)n * width * height, p->noc, 2, host_f, host_u,
+                        [&](const uint8_t *a, const uint8_t *b, float *const *f, uint8_t *const *u) {
+                          return ofdis_run_bidir_u8(c, a, b, n, width, height, p, alpha, beta, f[0], f[1], u[0], u[1],
+                                                    f[2], f[3], c->stream);
+                        });
+}
+
+int ofdis_lr_check(ofdis_context *c, const float *disp_l, const float *disp_r, int n, int width, int height,
+                   float alpha, float beta, uint8_t *occ_l, uint8_t *occ_r, float *err_l, float *err_r, void *stream) {
+  if (!c || !disp_l || !disp_r || n <= 0 || width <= 0 || height <= 0 || !fb_thresholds_ok(alpha, beta) ||
+      (long)width * height > 0x7fffffffL)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  BidirOut o;
+  o.stereo = true;
+  o.occ_fw = occ_l;
+  o.occ_bw = occ_r;
+  o.err_fw = err_l;
+  o.err_bw = err_r;
+  o.alpha = alpha;
+  o.beta = beta;
+  if (!o.checks()) return OFDIS_OK;
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
+  if (rc) return rc;
+  rc = run_lr_check(c, disp_l, disp_r, n, width, height, o, s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_stereo_u8(ofdis_context *c, const uint8_t *img_l, const uint8_t *img_r, int n, int width, int height,
+                        const ofdis_params *p, float alpha, float beta, float *disp_l, float *disp_r, uint8_t *occ_l,
+                        uint8_t *occ_r, float *err_l, float *err_r, void *stream) {
+  if (!c || !img_l || !img_r || !disp_l || n <= 0 || width <= 0 || height <= 0 || !p ||
+      !fb_thresholds_ok(alpha, beta) || (long)width * height > 0x7fffffffL)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_DE) return OFDIS_ERR_UNSUPPORTED;  // two views of one scene: a stereo pair
+  BidirOut o;
+  o.stereo = true;
+  o.flow_bw = disp_r;
+  o.occ_fw = occ_l;
+  o.occ_bw = occ_r;
+  o.err_fw = err_l;
+  o.err_bw = err_r;
+  o.alpha = alpha;
+  o.beta = beta;
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  // nothing but the left view's disparity asked for: the plain call
+  rc = run_batch(c, s, img_l, img_r, nullptr, n, width, height, p, disp_l, disp_r || o.checks() ? &o : nullptr);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_stereo_u8_host(ofdis_context *c, const uint8_t *img_l, const uint8_t *img_r, int n, int width, int height,
+                             const ofdis_params *p, float alpha, float beta, float *disp_l, float *disp_r,
+                             uint8_t *occ_l, uint8_t *occ_r, float *err_l, float *err_r) {
+  if (!c || !img_l || !img_r || !disp_l || n <= 0 || width <= 0 || height <= 0 || !p)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  float *const host_f[4] = {disp_l, disp_r, err_l, err_r};
+  uint8_t *const host_u[2] = {occ_l, occ_r};
+  return two_field_host(c, img_l, img_r, (size_t)n * width * height, p->noc, 1, host_f, host_u,
+                        [&](const uint8_t *l, const uint8_t *r, float *const *f, uint8_t *const *u) {
+                          return ofdis_run_stereo_u8(c, l, r, n, width, height, p, alpha, beta, f[0], f[1], u[0], u[1],
+                                                     f[2], f[3], c->stream);
+                        });
 }
 
 int ofdis_run_sequence_u8(ofdis_context *c, const uint8_t *frames, int nframes, int stride, const float *init,
@@ -1900,6 +2029,9 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   // both directions: the pixel's own flow and the gathered one (16 B), the mask byte, the error with "fb_check_err"
   if (k == "fb_check") b = 2.0 * width * height * (16.0 + 1.0);
   if (k == "fb_check_err") b = 2.0 * width * height * (16.0 + 1.0 + 4.0);
+  // both views: the pixel's own disparity and the gathered one (8 B), the mask byte, the error with "lr_check_err"
+  if (k == "lr_check") b = 2.0 * width * height * (8.0 + 1.0);
+  if (k == "lr_check_err") b = 2.0 * width * height * (8.0 + 1.0 + 4.0);
   // the warp as ofdis_run_warp_u8 issues it: image taps and u8 picture (noc each) and the mask byte per pixel, and the
   // float32 flow view -- 8 bytes per pixel, or the level grid once per frame
   if (k == "warp") b = (double)width * height * (2.0 * noc + 1.0 + 8.0);

@@ -327,6 +327,82 @@ class Context:
         out = tuple(flow + occ + err)
         return tuple(t[0] for t in out) if single else out
 
+    def lr_check_ptr(self, l_ptr: int, r_ptr: int, n: int, width: int, height: int, alpha: float, beta: float,
+                     occ_l_ptr: int = 0, occ_r_ptr: int = 0, err_l_ptr: int = 0, err_r_ptr: int = 0,
+                     stream: int = 0) -> None:
+        """``ofdis_lr_check`` on raw device pointers (0 = that output is not wanted)."""
+        check(lib().ofdis_lr_check(self._h, l_ptr or None, r_ptr or None, n, width, height, alpha, beta,
+                                   occ_l_ptr or None, occ_r_ptr or None, err_l_ptr or None, err_r_ptr or None,
+                                   stream or None), "ofdis_lr_check")
+
+    def lr_check(self, disp_l, disp_r, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False):
+        """Left-right consistency of two disparity fields: float32 CUDA tensors [n, h, w] (or [h, w]) ->
+        (occ_l, occ_r[, err_l, err_r]); occ uint8 [n, h, w] with 0 consistent, 1 inconsistent, 2 the disparity
+        leaves the frame; err float32 [n, h, w], the squared round-trip error (+inf where occ is 2)."""
+        import torch
+        single = disp_l.dim() == 2
+        dl, dr = (disp_l[None], disp_r[None]) if single else (disp_l, disp_r)
+        if (dl.dim() != 3 or dl.shape != dr.shape or dl.dtype != torch.float32 or dr.dtype != torch.float32
+                or not (dl.is_cuda and dr.is_cuda)):
+            raise ValueError("expected two float32 CUDA tensors [n, h, w] of one shape")
+        dl, dr = dl.contiguous(), dr.contiguous()
+        n, h, w = dl.shape
+        occ = [torch.empty((n, h, w), dtype=torch.uint8, device=dl.device) for _ in range(2)]
+        err = [torch.empty((n, h, w), dtype=torch.float32, device=dl.device) for _ in range(2 if want_err else 0)]
+        stream = torch.cuda.current_stream(dl.device).cuda_stream
+        self.lr_check_ptr(dl.data_ptr(), dr.data_ptr(), n, w, h, alpha, beta, occ[0].data_ptr(), occ[1].data_ptr(),
+                          err[0].data_ptr() if want_err else 0, err[1].data_ptr() if want_err else 0, stream)
+        out = tuple(occ + err)
+        return tuple(t[0] for t in out) if single else out
+
+    def run_stereo_ptr(self, l_ptr: int, r_ptr: int, n: int, width: int, height: int, p: Params, alpha: float,
+                       beta: float, disp_l_ptr: int, disp_r_ptr: int = 0, occ_l_ptr: int = 0, occ_r_ptr: int = 0,
+                       err_l_ptr: int = 0, err_r_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_run_stereo_u8`` on raw device pointers, asynchronous on `stream`; every output but the left
+        view's disparity is optional (0)."""
+        check(lib().ofdis_run_stereo_u8(self._h, l_ptr, r_ptr, n, width, height, C.byref(p), alpha, beta,
+                                        disp_l_ptr or None, disp_r_ptr or None, occ_l_ptr or None, occ_r_ptr or None,
+                                        err_l_ptr or None, err_r_ptr or None, stream or None), "ofdis_run_stereo_u8")
+
+    def run_stereo(self, left, right, p: Params, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False):
+        """Both views' disparities of each rectified pair from one batch, and their left-right check: torch.uint8
+        CUDA tensors [n, h, w] or [n, h, w, noc] -> (disp_l, disp_r, occ_l, occ_r[, err_l, err_r]).  disp_l is
+        run(left, right) (values <= 0); disp_r is the right view's disparity in its own coordinates (values >= 0):
+        -run(flip(right), flip(left)) flipped back, bit for bit; masks and errors as in lr_check.  Depth only."""
+        import torch
+        if left.dim() == 3:
+            left, right = left.unsqueeze(-1), right.unsqueeze(-1)
+        n, h, w, noc = left.shape
+        if (noc != p.noc or left.dtype != torch.uint8 or left.shape != right.shape
+                or not (left.is_cuda and right.is_cuda)):
+            raise ValueError("expected uint8 CUDA tensors with noc channels")
+        left, right = left.contiguous(), right.contiguous()
+        disp = [torch.empty((n, h, w), dtype=torch.float32, device=left.device) for _ in range(2)]
+        occ = [torch.empty((n, h, w), dtype=torch.uint8, device=left.device) for _ in range(2)]
+        err = [torch.empty((n, h, w), dtype=torch.float32, device=left.device) for _ in range(2 if want_err else 0)]
+        stream = torch.cuda.current_stream(left.device).cuda_stream
+        self.run_stereo_ptr(left.data_ptr(), right.data_ptr(), n, w, h, p, alpha, beta, disp[0].data_ptr(),
+                            disp[1].data_ptr(), occ[0].data_ptr(), occ[1].data_ptr(),
+                            err[0].data_ptr() if want_err else 0, err[1].data_ptr() if want_err else 0, stream)
+        return tuple(disp + occ + err)
+
+    def run_stereo_host(self, left: np.ndarray, right: np.ndarray, p: Params, alpha: float = 0.01, beta: float = 0.5,
+                        want_err: bool = False):
+        """run_stereo on numpy u8 [n,h,w,noc] (or a single [h,w,noc] pair); synchronous."""
+        single = left.ndim == 3
+        l4 = np.ascontiguousarray(left[None] if single else left, np.uint8)
+        r4 = np.ascontiguousarray(right[None] if single else right, np.uint8)
+        n, h, w = l4.shape[:3]
+        disp = [np.empty((n, h, w), _f32) for _ in range(2)]
+        occ = [np.empty((n, h, w), np.uint8) for _ in range(2)]
+        err = [np.empty((n, h, w), _f32) for _ in range(2 if want_err else 0)]
+        check(lib().ofdis_run_stereo_u8_host(self._h, l4.ctypes.data, r4.ctypes.data, n, w, h, C.byref(p), alpha, beta,
+                                             disp[0].ctypes.data, disp[1].ctypes.data, occ[0].ctypes.data,
+                                             occ[1].ctypes.data, err[0].ctypes.data if want_err else None,
+                                             err[1].ctypes.data if want_err else None), "ofdis_run_stereo_u8_host")
+        out = tuple(disp + occ + err)
+        return tuple(t[0] for t in out) if single else out
+
     def run_sequence_ptr(self, frames_ptr: int, nframes: int, stride: int, width: int, height: int, p: Params,
                          fw_ptr: int, init_ptr: int = 0, alpha: float = 0.01, beta: float = 0.5, bw_ptr: int = 0,
                          occ_fw_ptr: int = 0, occ_bw_ptr: int = 0, err_fw_ptr: int = 0, err_bw_ptr: int = 0,
