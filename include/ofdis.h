@@ -379,6 +379,74 @@ int ofdis_run_warp_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *i
 int ofdis_run_warp_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
                            int height, const ofdis_params *p, float scale, int out_dtype, void *out, uint8_t *valid);
 
+/* ------------------------------------------------------------------ frame interpolation
+ *
+ * Not in the reference.  The frame between two frames at time t in [0, 1] (frame-rate conversion, slow motion), from
+ * the two flows of the pair: every pixel of the new frame reads both frames along flows scaled to its time and blends
+ * the two samples.
+ *
+ * ofdis_interp_u8: n pairs of u8 frames img_a, img_b ([n][height][width][noc], noc 1 or 3), the forward flow F (a -> b,
+ * on a's pixel grid) and the backward flow B (b -> a, on b's pixel grid), both described by the one `view`, and nt times
+ * t[k] (a host array, copied at the call).  out: u8 or float32 (out_dtype) [n][nt][height][width][noc]; valid: u8
+ * [n][nt][height][width] or NULL.  occ_a / occ_b: u8 [n][height][width] occlusion masks of frame a / frame b
+ * (ofdis_fb_check's occ_fw / occ_bw), either may be NULL.  All pointers but t are device pointers.
+ *
+ * Definition, pixel (x, y), time t, (fu, fv) = F and (bu, bv) = B at that pixel as float32 (a binary16 value converted
+ * exactly; a level view expanded exactly as ofdis_warp_u8 defines); all arithmetic float32 in this order, every
+ * operation rounded on its own (no fused multiply-add):
+ *   c  = 1 - t
+ *   ua = t*(t*bu - c*fu);   va = t*(t*bv - c*fv)        (flow from time t back to frame a: -(1-t)t F + t^2 B)
+ *   ub = c*(c*fu - t*bu);   vb = c*(c*fv - t*bv)        (flow from time t on to frame b: (1-t)^2 F - t(1-t) B)
+ *   A[ch], in_a, (pxc_a, pyc_a) = ofdis_warp_u8's val / inside / clamped position for img_a at (x + ua, y + va), scale 1
+ *   Bv[ch], in_b, (pxc_b, pyc_b) = the same for img_b at (x + ub, y + vb)
+ *   use_a = in_a;  use_b = in_b
+ *   with masks:
+ *     xa = (int)rintf(pxc_a), ya = (int)rintf(pyc_a);  if occ_a[ya][xa] != 0: use_b = false
+ *                                                   (a's content there has no consistent match in b)
+ *     xb, yb likewise from b's position;               if occ_b[yb][xb] != 0: use_a = false
+ *   val = (use_a == use_b) ? A + t*(Bv - A) : (use_a ? A : Bv)
+ *   float32 output: val.   u8 output: (uint8_t)rintf(val), no clamp
+ *   valid = (use_a ? 1 : 0) | (use_b ? 2 : 0)
+ * valid: 3 both frames, 1 frame a only, 2 frame b only, 0 neither -- the plain blend of two border samples.
+ * Consequences: without masks and for finite flows, t = 0 returns frame a and t = 1 returns frame b, exactly in the u8
+ * form (the displacements towards the returned frame are exact zeros; float32: t = 0 gives a exactly, t = 1 gives
+ * A + (Bv - A), Bv to within one rounding).  With masks this does not hold: occ_a set at the sampled position at t = 1
+ * leaves A alone, the sample of frame a, and occ_b set at t = 0 leaves Bv alone.  The u8 form needs no clamp, by the
+ * warp's argument: both
+ * samples lie in [0, 255] and every rounding is monotonic.  A NaN flow clamps the position to column or row 0 and
+ * clears that frame's bit.
+ *
+ * Flow view: any dtype, layout and grid ofdis_warp_u8 accepts; for a level view both grids share the geometry of
+ * ofdis_out_geometry, and the pictures equal those of the full-resolution float32 fields bit for bit.
+ *
+ * Refused before anything is enqueued (OFDIS_ERR_INVALID_ARGUMENT, the context stays usable): everything ofdis_warp_u8
+ * refuses; a NULL img_b, flow_bw or t; nt outside 1..OFDIS_INTERP_MAX_T; any t[k] not finite or outside [0, 1].
+ * Stream, ordering and workspace rules are those of ofdis_fb_check. */
+#define OFDIS_INTERP_MAX_T 16
+int ofdis_interp_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, const void *flow_fw,
+                    const void *flow_bw, const ofdis_flow_view *view, int n, int width, int height, int noc,
+                    const float *t, int nt, const uint8_t *occ_a, const uint8_t *occ_b, int out_dtype, void *out,
+                    uint8_t *valid, void *stream);
+
+/* Both flows of each pair from one pyramid, then the nt frames between them.  By definition out / valid ==
+ * ofdis_interp_u8(img_a, img_b, F, B, no masks) bit for bit, with F, B the two flows of ofdis_run_bidir_u8 -- but both
+ * flows leave the coarse-to-fine loop as float32 level grids, 2 * n * bytes_per_pair bytes in the buffer the context
+ * owns, and the interpolation expands them on the fly: no full-resolution flow is allocated or written and no upsample
+ * runs, and every further time of a pair reuses the expanded flows.  valid may be NULL.
+ * The fused call takes no masks: the consistency check is defined on full-resolution fields.  A caller who wants them
+ * composes ofdis_run_bidir_u8 and ofdis_interp_u8(occ_a = occ_fw, occ_b = occ_bw).
+ * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED.  No initial flow.  verbosity is ignored.  A stage
+ * capture that is set is refused as in ofdis_run_bidir_u8 (OFDIS_ERR_UNSUPPORTED).  Argument errors as for
+ * ofdis_run_batch_u8 and ofdis_interp_u8; stream, ordering, chunking, round-robin, graph and workspace rules are those
+ * of ofdis_run_batch_u8 (the graph is recorded anew when out, valid, out_dtype, nt or a t[k] changes). */
+int ofdis_run_interp_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                        const ofdis_params *p, const float *t, int nt, int out_dtype, void *out, uint8_t *valid,
+                        void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_interp_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
+                             int height, const ofdis_params *p, const float *t, int nt, int out_dtype, void *out,
+                             uint8_t *valid);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -494,7 +562,8 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * when it writes masks only and as "fb_check_err" when it also writes an error map; the upsample as "upsample" when
  * it writes the plain format alone, else as "upsample_f16", "upsample_planar" or "upsample_planar_f16", and the
  * level-grid output that replaces it as "level_out"; the warp as "warp" with a full-resolution flow view and as
- * "warp_level" with a level-grid view; the left-right check as "lr_check" / "lr_check_err" like the forward-backward one. */
+ * "warp_level" with a level-grid view; the left-right check as "lr_check" / "lr_check_err" like the forward-backward
+ * one; the interpolation as "interp" with full-resolution flow views and as "interp_level" with level-grid views. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
@@ -502,7 +571,11 @@ const char *ofdis_kernel_names(void);
  * of image read per pixel, the flow view (8 bytes per pixel; the level grid's gw * gh * 2 * 4 bytes per frame), noc
  * bytes of u8 output and the mask byte -- the float32 views and the u8 output with its mask, as ofdis_run_warp_u8
  * issues them.  "lr_check" / "lr_check_err": both views, the pixel's own disparity and the gathered one (8 bytes), the
- * mask byte, and the 4-byte error with "lr_check_err" -- 2 * W * H * (8 + 1 [+ 4]). */
+ * mask byte, and the 4-byte error with "lr_check_err" -- 2 * W * H * (8 + 1 [+ 4]).  "interp" / "interp_level": per
+ * intermediate frame (the function has no nt argument; a call with nt times reads its flows once and does the rest nt
+ * times): the two float32 flow views (16 bytes per pixel; the two level grids' 2 * gw * gh * 8 bytes per pair), 2 noc
+ * bytes of image read, noc bytes of u8 output and the mask byte per pixel -- W * H * (16 + 3 noc + 1) and
+ * 2 * gw * gh * 8 + W * H * (3 noc + 1). */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */

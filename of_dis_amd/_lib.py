@@ -31,6 +31,8 @@ OUT_INTERLEAVED, OUT_PLANAR = 0, 1
 OUT_FULL, OUT_LEVEL = 0, 1
 # out_dtype of the warp entry points
 IMG_U8, IMG_F32 = 0, 1
+# OFDIS_INTERP_MAX_T: the most times one interpolation call takes
+INTERP_MAX_T = 16
 
 
 class OfdisError(RuntimeError):
@@ -154,6 +156,9 @@ def lib():
         "ofdis_warp_u8": ([vp, vp, vp, V, i, i, i, i, f, i, vp, vp, vp], i),
         "ofdis_run_warp_u8": ([vp, vp, vp, i, i, i, P, f, i, vp, vp, vp], i),
         "ofdis_run_warp_u8_host": ([vp, vp, vp, i, i, i, P, f, i, vp, vp], i),
+        "ofdis_interp_u8": ([vp, vp, vp, vp, vp, V, i, i, i, i, vp, i, vp, vp, i, vp, vp, vp], i),
+        "ofdis_run_interp_u8": ([vp, vp, vp, i, i, i, P, vp, i, i, vp, vp, vp], i),
+        "ofdis_run_interp_u8_host": ([vp, vp, vp, i, i, i, P, vp, i, i, vp, vp], i),
         "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),

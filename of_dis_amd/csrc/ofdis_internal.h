@@ -210,7 +210,25 @@ struct WarpArgs {
   int gw, gh, log2c, offx, offy;  // level grid: its size, log2 of the cell, the frame's offset in it (ofdis_out_geometry)
 };
 
+// The frame between two frames at nt times (include/ofdis.h: ofdis_interp_u8).  One view describes both flows.
+constexpr int kInterpMaxT = 16;  // OFDIS_INTERP_MAX_T
+struct InterpArgs {
+  const uint8_t *img_a, *img_b;      // [n][H][W][noc]
+  const void *flow_fw, *flow_bw;     // a -> b on a's grid, b -> a on b's grid; the layouts of WarpArgs::flow
+  const uint8_t *occ_a, *occ_b;      // [n][H][W] occlusion masks of the two frames, or NULL
+  void *out;                         // u8 or float [n][nt][H][W][noc]
+  uint8_t *valid;                    // [n][nt][H][W] bit 0: frame a used, bit 1: frame b used; or NULL
+  int n, W, H, noc;                  // W * H < 2^31
+  int out_f32;
+  int f16, planar, level;
+  int gw, gh, log2c, offx, offy;
+  int srows, scols;                  // level form: rows and columns of a staged window (set by launch_interp)
+  int nt;
+  float t[kInterpMaxT];
+};
+
 void launch_warp(const WarpArgs &a, hipStream_t s);
+void launch_interp(const InterpArgs &a, hipStream_t s);
 void launch_fb_check(const FbArgs &a, hipStream_t s);
 void launch_lr_check(const LrArgs &a, hipStream_t s);
 void launch_init_area(const InitArgs &a, hipStream_t s);

@@ -33,6 +33,8 @@
 //   fb check     k_fb_check<OCC, ERR, PX>  forward-backward consistency masks of two flow fields (no reference code)
 //   warp         k_warp<OT, NOC, FT, PLANAR, PX>, k_warp_level<OT, NOC, PX>  backward warp of u8 frames along a flow
 //                field / along the level grid expanded on the fly (no reference code)
+//   interp       k_interp<OT, NOC, FT, PLANAR, PX>, k_interp_level<OT, NOC, PX>  the frames between two u8 frames from
+//                their two flows, full-resolution fields / level grids (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -6116,6 +6118,230 @@ void launch_warp(const WarpArgs &a0, hipStream_t s) {
       else if (a.f16) k_warp<O, NOC, _Float16, false, PX><<<grid, 256, 0, s>>>(a);
       else if (a.planar) k_warp<O, NOC, float, true, PX><<<grid, 256, 0, s>>>(a);
       else k_warp<O, NOC, float, false, PX><<<grid, 256, 0, s>>>(a);
+    };
+    pick_noc(a.noc, [&](auto NOC) {
+      pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {
+        if (vec) go(OT, NOC, Int<4>{});
+        else go(OT, NOC, Int<1>{});
+      });
+    });
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ interpolation
+// The frame between two frames of include/ofdis.h (ofdis_interp_u8): at time t every pixel reads frame a at
+// (x, y) + t (t B - (1 - t) F) and frame b at (x, y) + (1 - t) ((1 - t) F - t B) through warp_pixel and blends the two
+// samples, or keeps the one whose position stayed inside its frame (and, with masks, whose counterpart is not marked
+// occluded).  Every operation and its order are fixed by the definition, as for the warp.
+//   k_interp<OT, NOC, FT, PLANAR, PX>  both flows are full-resolution fields of one format
+//   k_interp_level<OT, NOC, PX>        both flows are level grids of one geometry, expanded as k_warp_level does
+// A thread holds its pixels' four flow components and loops over the nt times: the flows are read (or expanded) once
+// per pair, whatever the number of intermediate frames.
+namespace {
+
+// The rounded clamped position warp_pixel takes its taps at for pixel x (or y) and flow component u at scale 1, as a
+// column (row) of a frame of n columns (rows): warp_pixel's own expressions (1 * u is u), which the compiler merges
+// with them after inlining; the integer min as there.
+__device__ __forceinline__ unsigned interp_round_pos(int x, float u, int n) {
+  const float pc = fminf(fmaxf((float)x + u, 0.f), (float)(n - 1));
+  return (unsigned)min((int)rintf(pc), n - 1);
+}
+
+// The store of PX pixels' values and mask bytes (m: one byte per pixel) at pixel index o of the pictures `out_` /
+// `valid` (NULL: no mask), in warp_emit's forms.  PX = 4: four u8 values as one dword, four float32 values as one
+// 16-byte store (NOC = 3: three of them), the four mask bytes as one dword.
+template <class OT, int NOC, int PX>
+__device__ __forceinline__ void interp_store(void *out_, uint8_t *valid, long o, const float *val, unsigned m) {
+  OT *out = reinterpret_cast<OT *>(out_) + o * NOC;
+  if constexpr (std::is_same<OT, float>::value) {
+    if constexpr (PX == 4) {
+#pragma unroll
+      for (int j = 0; j < NOC; ++j)
+        *reinterpret_cast<float4_v *>(out + 4 * j) = float4_v{val[4 * j], val[4 * j + 1], val[4 * j + 2], val[4 * j + 3]};
+    } else {
+#pragma unroll
+      for (int c = 0; c < NOC; ++c) out[c] = val[c];
+    }
+  } else {  // u8: round half to even
+    unsigned b[PX * NOC];
+#pragma unroll
+    for (int k = 0; k < PX * NOC; ++k) b[k] = (unsigned)(int)rintf(val[k]);
+    if constexpr (PX == 4) {
+#pragma unroll
+      for (int j = 0; j < NOC; ++j)
+        *reinterpret_cast<unsigned *>(out + 4 * j) = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
+    } else {
+#pragma unroll
+      for (int c = 0; c < NOC; ++c) out[c] = (uint8_t)b[c];
+    }
+  }
+  if (valid) {
+    if constexpr (PX == 4)
+      *reinterpret_cast<unsigned *>(valid + o) = m;
+    else
+      valid[o] = (uint8_t)m;
+  }
+}
+
+// The PX pixels (x .. x + PX - 1, y) of frame f at time a.t[k] from their four flow components: the two samples, the
+// blend or the choice between them, the store into the pair's k-th picture.
+template <class OT, int NOC, int PX>
+__device__ __forceinline__ void interp_emit(const InterpArgs &a, int f, int k, int x, int y, const float *fu,
+                                            const float *fv, const float *bu, const float *bv) {
+  const long plane = (long)a.W * a.H, o = ((long)f * a.nt + k) * plane + (long)y * a.W + x;
+  const uint8_t *Ia = a.img_a + (long)f * plane * NOC, *Ib = a.img_b + (long)f * plane * NOC;
+  const uint8_t *oa = a.occ_a ? a.occ_a + (long)f * plane : nullptr, *ob = a.occ_b ? a.occ_b + (long)f * plane : nullptr;
+  const float t = a.t[k], c = 1.f - t;
+  float val[PX * NOC];
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    const float ua = t * (t * bu[i] - c * fu[i]), va = t * (t * bv[i] - c * fv[i]);
+    const float ub = c * (c * fu[i] - t * bu[i]), vb = c * (c * fv[i] - t * bv[i]);
+    float A[NOC], B[NOC];
+    bool use_a = warp_pixel<NOC>(Ia, a.W, a.H, x + i, y, ua, va, 1.f, A) != 0;
+    bool use_b = warp_pixel<NOC>(Ib, a.W, a.H, x + i, y, ub, vb, 1.f, B) != 0;
+    // the mask bytes at the rounded positions (inside the frame: the positions are clamped); the gathers depend on
+    // the positions alone and go out with the image taps
+    unsigned ma = 0, mb = 0;
+    if (oa) ma = oa[interp_round_pos(y, va, a.H) * (unsigned)a.W + interp_round_pos(x + i, ua, a.W)];
+    if (ob) mb = ob[interp_round_pos(y, vb, a.H) * (unsigned)a.W + interp_round_pos(x + i, ub, a.W)];
+    if (ma) use_b = false;  // a's content there has no consistent match in b
+    if (mb) use_a = false;
+#pragma unroll
+    for (int ch = 0; ch < NOC; ++ch) val[i * NOC + ch] = use_a == use_b ? A[ch] + t * (B[ch] - A[ch]) : (use_a ? A[ch] : B[ch]);
+    m |= ((use_a ? 1u : 0u) | (use_b ? 2u : 0u)) << (8 * i);
+  }
+  // u8: both samples lie in [0, 255] and every rounding is monotonic, so the blend does too -- no clamp
+  interp_store<OT, NOC, PX>(a.out, a.valid, o, val, m);
+}
+
+// Thread layout, vector loads and alignment rules of k_warp.
+template <class OT, int NOC, class FT, bool PLANAR, int PX>
+__global__ __launch_bounds__(256) void k_interp(InterpArgs a) {
+  const int f = blockIdx.z;
+  const unsigned wq = (unsigned)a.W / PX;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= wq * (unsigned)a.H) return;
+  const int y = (int)(q / wq), x = (int)(q - (unsigned)y * wq) * PX;
+  const long plane = (long)a.W * a.H, o = (long)y * a.W + x;
+  float fu[PX], fv[PX], bu[PX], bv[PX];
+  warp_own_flow<FT, PLANAR, PX>(reinterpret_cast<const FT *>(a.flow_fw) + (long)f * 2 * plane, o, plane, fu, fv);
+  warp_own_flow<FT, PLANAR, PX>(reinterpret_cast<const FT *>(a.flow_bw) + (long)f * 2 * plane, o, plane, bu, bv);
+  for (int k = 0; k < a.nt; ++k) interp_emit<OT, NOC, PX>(a, f, k, x, y, fu, fv, bu, bv);
+}
+
+// Block shape and staging of k_warp_level, for two grids of one geometry (0 forward, 1 backward).  The windows live in
+// dynamic LDS sized by the launch's cell (launch_interp: a.srows rows of a.scols columns per grid and component; the
+// two windows at k_warp_level's fixed size, 41 KB, would hold the kernel at three blocks per CU whatever the cell).
+// A row's expanded flows stay in registers across the nt times.
+extern __shared__ float interp_src[];  // [grid][row][comp][col]
+template <class OT, int NOC, int PX>
+__global__ __launch_bounds__(256) void k_interp_level(InterpArgs a) {
+  constexpr int kCols = 256 * PX;
+  auto src = [&](int g, int row, int comp) { return interp_src + ((g * a.srows + row) * 2 + comp) * a.scols; };
+  const unsigned ncb = ((unsigned)a.W + kCols - 1) / kCols;
+  const int y0 = (int)(blockIdx.x / ncb) * kWarpRows, f = blockIdx.z;
+  const long xb = (long)(blockIdx.x % ncb) * kCols;
+  const long xl = xb + threadIdx.x * PX;
+  const int x = (int)(xl < a.W ? xl : a.W);
+  const long gplane = (long)a.gw * a.gh;
+  auto cell = [&](int g, long i, int k) {  // component k of cell i of frame f of grid g
+    const void *F = g ? a.flow_bw : a.flow_fw;
+    const long e = a.planar ? ((long)f * 2 + k) * gplane + i : ((long)f * gplane + i) * 2 + k;
+    return a.f16 ? (float)reinterpret_cast<const _Float16 *>(F)[e] : reinterpret_cast<const float *>(F)[e];
+  };
+  float fu[PX], fv[PX], bu[PX], bv[PX];
+  if (a.log2c == 0) {
+    if (x >= a.W) return;
+    for (int r = 0; r < kWarpRows; ++r) {
+      const int y = y0 + r;
+      if (y >= a.H) break;
+#pragma unroll
+      for (int i = 0; i < PX; ++i) {
+        const long o = (long)(y + a.offy) * a.gw + (x + i + a.offx);
+        fu[i] = cell(0, o, 0), fv[i] = cell(0, o, 1);
+        bu[i] = cell(1, o, 0), bv[i] = cell(1, o, 1);
+      }
+      for (int k = 0; k < a.nt; ++k) interp_emit<OT, NOC, PX>(a, f, k, x, y, fu, fv, bu, bv);
+    }
+    return;
+  }
+  const double scale = 1.0 / (double)(1 << a.log2c);
+  const int ylast = min(y0 + kWarpRows, a.H) - 1;
+  const int r_first = ytap(y0 + a.offy, scale, a.gh).r0;
+  const int nr = min(ytap(ylast + a.offy, scale, a.gh).r1 - r_first + 1, a.srows);
+  const long c_raw = (2 * (xb + a.offx) + 1 - (1 << a.log2c)) >> (a.log2c + 1);  // (as k_warp_level)
+  const int c_lo = (int)(c_raw > 0 ? c_raw : 0);
+  const int ncol = a.scols;  // ceil(kCols / cell) + 2 columns and a spare
+  for (int k = threadIdx.x; k < 2 * nr * 2 * ncol; k += 256) {
+    const int col = k % ncol, rc = k / ncol;  // rc = (grid * nr + row) * 2 + comp
+    const int g = (rc >> 1) / nr, row = (rc >> 1) - g * nr;
+    const int sc = min(c_lo + col, a.gw - 1);
+    src(g, row, rc & 1)[col] = cell(g, (long)(r_first + row) * a.gw + sc, rc & 1);
+  }
+  __syncthreads();
+  if (x >= a.W) return;
+  XTap xt[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    xt[i] = xtap(x + i + a.offx, scale, a.gw);
+    xt[i].sx = min(max(xt[i].sx - c_lo, 0), ncol - 2);  // (inside the staged window by construction)
+  }
+  for (int r = 0; r < kWarpRows; ++r) {
+    const int y = y0 + r;
+    if (y >= a.H) break;
+    const YTap yt = ytap(y + a.offy, scale, a.gh);
+    const int j0 = min(max(yt.r0 - r_first, 0), nr - 1), j1 = min(max(yt.r1 - r_first, 0), nr - 1);
+    const float b0 = 1.f - yt.fy, b1 = yt.fy;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      fu[i] = up_px_s(src(0, j0, 0), src(0, j1, 0), xt[i], b0, b1);
+      fv[i] = up_px_s(src(0, j0, 1), src(0, j1, 1), xt[i], b0, b1);
+      bu[i] = up_px_s(src(1, j0, 0), src(1, j1, 0), xt[i], b0, b1);
+      bv[i] = up_px_s(src(1, j0, 1), src(1, j1, 1), xt[i], b0, b1);
+    }
+    for (int k = 0; k < a.nt; ++k) interp_emit<OT, NOC, PX>(a, f, k, x, y, fu, fv, bu, bv);
+  }
+}
+
+}  // namespace
+// ---- launch
+// Frames go in grid z, 65535 per launch; the vector forms under launch_warp's conditions, for both flows.  (W % 4 == 0
+// keeps every one of the nt planes of a pair as aligned as the picture's base.)
+void launch_interp(const InterpArgs &a0, hipStream_t s) {
+  const bool vec = a0.W % 4 == 0 && (a0.level || ((uintptr_t)a0.flow_fw % 16 == 0 && (uintptr_t)a0.flow_bw % 16 == 0)) &&
+                   (uintptr_t)a0.out % (a0.out_f32 ? 16 : 4) == 0 && (uintptr_t)a0.valid % 4 == 0;
+  const long frame = (long)a0.W * a0.H;
+  const long flow_frame = (a0.level ? (long)a0.gw * a0.gh : frame) * 2 * (a0.f16 ? 2 : 4);  // bytes
+  const int kSlice = 65535;  // grid z
+  for (int f0 = 0; f0 < a0.n; f0 += kSlice) {
+    InterpArgs a = a0;
+    a.n = std::min(kSlice, a0.n - f0);
+    a.img_a += f0 * frame * a0.noc;
+    a.img_b += f0 * frame * a0.noc;
+    a.flow_fw = (const char *)a0.flow_fw + f0 * flow_frame;
+    a.flow_bw = (const char *)a0.flow_bw + f0 * flow_frame;
+    if (a.occ_a) a.occ_a += f0 * frame;
+    if (a.occ_b) a.occ_b += f0 * frame;
+    a.out = (char *)a0.out + f0 * a0.nt * frame * a0.noc * (a0.out_f32 ? 4 : 1);
+    if (a.valid) a.valid += f0 * a0.nt * frame;
+    auto go = [&](auto OT, auto NOC, auto PX) {
+      using O = std::conditional_t<OT != 0, float, uint8_t>;
+      if (a.level) {
+        const dim3 grid(ceil_div(a.H, kWarpRows) * ceil_div(a.W, 256 * PX), 1, a.n);
+        // the staged windows: the rows of cells four output rows touch (at most 4 / cell + 3) and the block's columns
+        a.srows = a.log2c ? std::min((kWarpRows >> a.log2c) + 3, kWarpSrcRows) : 0;
+        a.scols = a.log2c ? std::min(((256 * PX) >> a.log2c) + 3, kWarpSrcCols) : 0;
+        const size_t lds = sizeof(float) * 2 * a.srows * 2 * a.scols;
+        k_interp_level<O, NOC, PX><<<grid, 256, lds, s>>>(a);
+        return;
+      }
+      const dim3 grid(ceil_div(frame / PX, 256), 1, a.n);
+      if (a.f16 && a.planar) k_interp<O, NOC, _Float16, true, PX><<<grid, 256, 0, s>>>(a);
+      else if (a.f16) k_interp<O, NOC, _Float16, false, PX><<<grid, 256, 0, s>>>(a);
+      else if (a.planar) k_interp<O, NOC, float, true, PX><<<grid, 256, 0, s>>>(a);
+      else k_interp<O, NOC, float, false, PX><<<grid, 256, 0, s>>>(a);
     };
     pick_noc(a.noc, [&](auto NOC) {
       pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {

@@ -35,7 +35,9 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     // the warp with a full-resolution flow view / with a level-grid view
                                     "warp", "warp_level",
                                     // the left-right check writing masks only / also an error map
-                                    "lr_check", "lr_check_err"};
+                                    "lr_check", "lr_check_err",
+                                    // the interpolation with full-resolution flow views / with level-grid views
+                                    "interp", "interp_level"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -83,7 +85,8 @@ struct ofdis_context {
   hipStream_t stream = nullptr;
   char *ws = nullptr;
   size_t ws_cap = 0;
-  // ofdis_run_warp_u8: the call's flow as the float32 level grid, [n] x bytes_per_pair (ofdis_out_geometry)
+  // ofdis_run_warp_u8: the call's flow as the float32 level grid, [n] x bytes_per_pair (ofdis_out_geometry);
+  // ofdis_run_interp_u8: the forward grids of the n pairs, then their backward grids
   char *warp_buf = nullptr;
   size_t warp_cap = 0;
   // stage capture (frame 0), indexed by scale
@@ -117,6 +120,12 @@ struct ofdis_context {
     ofdis_params p{};
   } gkey;
   hipGraphExec_t gexec = nullptr;
+  // ofdis_run_interp_u8 records gkey with warp = 2 (warp_out / warp_valid / warp_buf / warp_f32 its picture, mask,
+  // buffer and dtype) and its times here; the graph of such a call is replayed only while both agree
+  struct InterpKey {
+    int nt = 0;
+    float t[kInterpMaxT] = {};
+  } ikey;
   int opt_nt_store = 0;        // upsample output with non-temporal stores (A/B)
   // flow upsample: 0 per-output-row horizontal taps (k_upsample_rows), 1 / 2 once per staged source row (k_upsample_h,
   // 4 / 8 rows), 3 auto: 1 when the frame spans a whole 1024-column block and the call runs on two or more lanes or
@@ -1024,6 +1033,55 @@ int run_warp(ofdis_context *c, const uint8_t *img, const void *flow, const ofdis
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
+// The pictures of an interpolation (ofdis_interp_u8, ofdis_run_interp_u8); at() is a chunk's share.
+struct InterpOut {
+  void *out = nullptr;
+  uint8_t *valid = nullptr;
+  const uint8_t *occ_a = nullptr, *occ_b = nullptr;
+  int f32 = 0, nt = 0;
+  float t[kInterpMaxT] = {};
+  InterpOut at(size_t f0, size_t px, int noc) const {
+    InterpOut o = *this;
+    o.out = (char *)out + f0 * nt * px * noc * (f32 ? 4 : 1);
+    if (valid) o.valid += f0 * nt * px;
+    return o;
+  }
+};
+
+// The frames between n pairs along two flow views of one description (timer "interp_level" for level-grid views,
+// else "interp").
+int run_interp(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, const void *flow_fw, const void *flow_bw,
+               const ofdis_flow_view &v, int n, int width, int height, int noc, const InterpOut &o, hipStream_t s) {
+  InterpArgs ia{};
+  ia.img_a = img_a;
+  ia.img_b = img_b;
+  ia.flow_fw = flow_fw;
+  ia.flow_bw = flow_bw;
+  ia.occ_a = o.occ_a;
+  ia.occ_b = o.occ_b;
+  ia.out = o.out;
+  ia.valid = o.valid;
+  ia.n = n;
+  ia.W = width;
+  ia.H = height;
+  ia.noc = noc;
+  ia.out_f32 = o.f32;
+  ia.f16 = v.dtype == OFDIS_OUT_F16;
+  ia.planar = v.layout == OFDIS_OUT_PLANAR;
+  ia.level = v.grid == OFDIS_OUT_LEVEL;
+  if (ia.level) {
+    ia.gw = v.gw;
+    ia.gh = v.gh;
+    ia.offx = v.off_x;
+    ia.offy = v.off_y;
+    while ((1 << ia.log2c) < v.cell) ++ia.log2c;
+  }
+  ia.nt = o.nt;
+  std::memcpy(ia.t, o.t, sizeof(ia.t));
+  timed(c, ia.level ? 23 : 22, s, [&] { launch_interp(ia, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
 // One chunk of frames through the whole pipeline on stream s with workspace ws.  bd (P.bidir): the backward flow
 // of the same pyramid upsampled too -- into the workspace when the caller wants only the masks -- and the check.
 int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
@@ -1048,6 +1106,30 @@ int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, 
   float *flow_bw = bd->flow_bw ? bd->flow_bw : (float *)(ws + P.off_up_bw);
   if ((rc = run_upsample(c, ws, P, p, flow_bw, s, true))) return rc;
   return bd->checks() ? run_fb_check(c, (const float *)flow_out, flow_bw, P.n, P.W0, P.H0, *bd, s) : OFDIS_OK;
+}
+
+// One chunk of ofdis_run_interp_u8 (P a bidirectional plan, no initial flow): the pipeline of run_chunk, then both
+// flows of the finest level x 2^sc_l as float32 interleaved level grids (grid_fw, grid_bw: the chunk's share of the
+// context's buffer) and the pictures from them.  No upsample runs.
+int run_chunk_interp(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
+                     const uint8_t *img_b, void *grid_fw, void *grid_bw, const InterpOut &io, hipStream_t s) {
+  int rc = run_pyramid(c, ws, P, img_a, img_b, s);
+  if (rc) return rc;
+  if ((rc = run_levels(c, ws, P, p, s, nullptr, nullptr))) return rc;
+  for (int dir = 0; dir < 2; ++dir) {
+    LevelOutArgs lo{};
+    lo.flow = (const float *)(ws + (dir ? P.off_flow_bw[0] : P.off_flow[0]));
+    lo.out = dir ? grid_bw : grid_fw;
+    lo.n = P.n;
+    lo.nop = P.nop;
+    lo.wl = P.lv[0].w;
+    lo.hl = P.lv[0].h;
+    lo.log2s = p->sc_l;
+    timed(c, 17, s, [&] { launch_level_out(lo, s); });
+    if (hipGetLastError() != hipSuccess) return OFDIS_ERR_DEVICE;
+  }
+  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
+  return run_interp(c, img_a, img_b, grid_fw, grid_bw, v, P.n, P.W0, P.H0, P.noc, io, s);
 }
 
 // k lanes (stream, done event, workspace of `bytes`).
@@ -1167,6 +1249,30 @@ int issue(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_param
   }
 }
 
+// ofdis_run_interp_u8's issue, in the same two kinds: the whole batch on stream s, or chunks round-robin over the
+// lanes (fork from s, join into s).  grids: the context's buffer, the n forward grids and then the n backward ones.
+int issue_interp(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *img_a,
+                 const uint8_t *img_b, char *grids, const InterpOut &io) {
+  char *grids_bw = grids + (size_t)cp.n * cp.out_pair;
+  if (cp.kind == CallPlan::kSingle) return run_chunk_interp(c, c->ws, cp.whole, p, img_a, img_b, grids, grids_bw, io, s);
+  const int k = cp.lanes;
+  HIP_OK(hipEventRecord(c->entry, s));
+  for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
+  const size_t px = (size_t)cp.width * cp.height, in_frame = px * p->noc;
+  for (int ch = 0; ch < cp.nchunks; ++ch) {
+    const size_t f0 = (size_t)ch * cp.chunk;
+    auto &L = c->lanes[ch % k];
+    int rc = run_chunk_interp(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b + f0 * in_frame,
+                              grids + f0 * cp.out_pair, grids_bw + f0 * cp.out_pair, io.at(f0, px, p->noc), L.s);
+    if (rc) return rc;
+  }
+  for (int i = 0; i < k; ++i) {
+    HIP_OK(hipEventRecord(c->lanes[i].done, c->lanes[i].s));
+    HIP_OK(hipStreamWaitEvent(s, c->lanes[i].done, 0));
+  }
+  return OFDIS_OK;
+}
+
 // Start of a call on stream s: NULL is the legacy default stream (torch's default), which the context's
 // non-blocking stream does not order against -- hand its queued work over with an event; and the
 // workspaces are shared by every call on this context, whatever its stream -- wait for the previous call.
@@ -1267,6 +1373,52 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
   }
   HIP_OK(hipGraphLaunch(c->gexec, s));
   OFDIS_TRACE("graph: launched");
+  return OFDIS_OK;
+}
+
+// ofdis_run_interp_u8 on stream s (no stage capture is set): the bidirectional plan with nothing kept at full
+// resolution, the 2 n level grids in the context's buffer, and run_batch's chunk, lane and graph rules.
+int run_batch_interp(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
+                     int height, const ofdis_params *p, const InterpOut &io) {
+  CallPlan cp;
+  int rc = prepare(c, p, n, width, height, false, false, cp, 1);
+  if (rc) return rc;
+  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
+  cp.out_pair = (size_t)P1.lv[0].w * P1.lv[0].h * P1.nop * 4;  // a pair's float32 level grid
+  if ((rc = ensure_warp_buf(c, 2 * (size_t)n * cp.out_pair))) return rc;  // (drops the graph before it grows)
+  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
+  if (!graph || c->timing) return issue_interp(c, cp, s, p, img_a, img_b, c->warp_buf, io);
+  ofdis_context::GraphKey key;
+  std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
+  key.a = img_a; key.b = img_b; key.out = c->warp_buf; key.ws = c->ws;
+  key.n = n; key.w = width; key.h = height; key.p = *p;
+  key.out_level = 1;
+  key.warp = 2; key.warp_out = io.out; key.warp_valid = io.valid; key.warp_buf = c->warp_buf; key.warp_f32 = io.f32;
+  ofdis_context::InterpKey ikey;
+  std::memset(&ikey, 0, sizeof(ikey));
+  ikey.nt = io.nt;
+  std::memcpy(ikey.t, io.t, sizeof(float) * io.nt);
+  if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0 || std::memcmp(&ikey, &c->ikey, sizeof(ikey)) != 0) {
+    if ((rc = drop_graph(c))) return rc;
+    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    rc = issue_interp(c, cp, c->stream, p, img_a, img_b, c->warp_buf, io);
+    hipGraph_t graph = nullptr;
+    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
+    if (rc) {
+      if (graph) hipGraphDestroy(graph);
+      return rc;
+    }
+    if (ce != hipSuccess || !graph) return OFDIS_ERR_DEVICE;
+    const hipError_t ie = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    if (ie != hipSuccess) {
+      c->gexec = nullptr;
+      return OFDIS_ERR_DEVICE;
+    }
+    std::memcpy(&c->gkey, &key, sizeof(key));
+    std::memcpy(&c->ikey, &ikey, sizeof(ikey));
+  }
+  HIP_OK(hipGraphLaunch(c->gexec, s));
   return OFDIS_OK;
 }
 
@@ -1856,6 +2008,114 @@ int ofdis_run_warp_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t
   return rc;
 }
 
+// ------------------------------------------------------------------ frame interpolation (include/ofdis.h)
+
+static_assert(OFDIS_INTERP_MAX_T == kInterpMaxT, "the header's limit is the kernel argument's array");
+
+namespace {
+// A flow view an interpolation of width x height frames can read: what ofdis_warp_u8 accepts.
+bool flow_view_ok(const ofdis_flow_view *v, int width, int height) {
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return false;
+  if (v->grid == OFDIS_OUT_LEVEL) {
+    if (v->cell < 1 || v->cell > 512 || (v->cell & (v->cell - 1)) || v->gw <= 0 || v->gh <= 0 || v->off_x < 0 ||
+        v->off_y < 0 || (long)v->gw * v->cell < (long)width + v->off_x || (long)v->gh * v->cell < (long)height + v->off_y)
+      return false;
+  }
+  return true;
+}
+
+// The times of an interpolation: 1 .. OFDIS_INTERP_MAX_T finite values in [0, 1].
+bool interp_times_ok(const float *t, int nt) {
+  if (!t || nt < 1 || nt > OFDIS_INTERP_MAX_T) return false;
+  for (int k = 0; k < nt; ++k)
+    if (!(t[k] >= 0.0f && t[k] <= 1.0f)) return false;  // (false for NaN)
+  return true;
+}
+}  // namespace
+
+int ofdis_interp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, const void *flow_fw,
+                    const void *flow_bw, const ofdis_flow_view *v, int n, int width, int height, int noc, const float *t,
+                    int nt, const uint8_t *occ_a, const uint8_t *occ_b, int out_dtype, void *out, uint8_t *valid,
+                    void *stream) {
+  if (!c || !img_a || !img_b || !flow_fw || !flow_bw || !v || !out || n <= 0 || width <= 0 || height <= 0 ||
+      (noc != 1 && noc != 3) || !img_dtype_ok(out_dtype) || (long)width * height > 0x7fffffffL ||
+      !interp_times_ok(t, nt) || !flow_view_ok(v, width, height))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  InterpOut o;
+  o.out = out;
+  o.valid = valid;
+  o.occ_a = occ_a;
+  o.occ_b = occ_b;
+  o.f32 = out_dtype == OFDIS_IMG_F32;
+  o.nt = nt;
+  std::memcpy(o.t, t, sizeof(float) * nt);
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
+  if (rc) return rc;
+  rc = run_interp(c, img_a, img_b, flow_fw, flow_bw, *v, n, width, height, noc, o, s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_interp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                        const ofdis_params *p, const float *t, int nt, int out_dtype, void *out, uint8_t *valid,
+                        void *stream) {
+  if (!c || !img_a || !img_b || !out || n <= 0 || width <= 0 || height <= 0 || !p || !img_dtype_ok(out_dtype) ||
+      (long)width * height > 0x7fffffffL || !interp_times_ok(t, nt))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // (as ofdis_run_bidir_u8)
+  InterpOut o;
+  o.out = out;
+  o.valid = valid;
+  o.f32 = out_dtype == OFDIS_IMG_F32;
+  o.nt = nt;
+  std::memcpy(o.t, t, sizeof(float) * nt);
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch_interp(c, s, img_a, img_b, n, width, height, p, o);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_interp_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                             const ofdis_params *p, const float *t, int nt, int out_dtype, void *out, uint8_t *valid) {
+  if (!c || !img_a || !img_b || !out || n <= 0 || width <= 0 || height <= 0 || !p || !img_dtype_ok(out_dtype) ||
+      (p->noc != 1 && p->noc != 3) || !interp_times_ok(t, nt))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)n * width * height, in = px * p->noc, outb = in * nt * (out_dtype == OFDIS_IMG_F32 ? 4 : 1);
+  // one device block: the two images, the pictures, the masks (each at a multiple of 256 bytes)
+  const size_t off_b = align_up(in), off_out = 2 * align_up(in), off_valid = off_out + align_up(outb);
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_valid + (valid ? px * nt : 0)));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  if (step(hipMemcpyAsync(d, img_a, in, hipMemcpyHostToDevice, c->stream)) &&
+      step(hipMemcpyAsync(d + off_b, img_b, in, hipMemcpyHostToDevice, c->stream))) {
+    rc = ofdis_run_interp_u8(c, (const uint8_t *)d, (const uint8_t *)(d + off_b), n, width, height, p, t, nt, out_dtype,
+                             d + off_out, valid ? (uint8_t *)(d + off_valid) : nullptr, c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      step(hipMemcpy(out, d + off_out, outb, hipMemcpyDeviceToHost));
+      if (valid) step(hipMemcpy(valid, d + off_valid, px * nt, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -2036,6 +2296,11 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   // float32 flow view -- 8 bytes per pixel, or the level grid once per frame
   if (k == "warp") b = (double)width * height * (2.0 * noc + 1.0 + 8.0);
   if (k == "warp_level") b = (double)width * height * (2.0 * noc + 1.0) + (double)P.lv[0].w * P.lv[0].h * 2 * 4.0;
+  // the interpolation as ofdis_run_interp_u8 issues it, per intermediate frame (nt = 1): image taps of both frames
+  // (2 noc), the u8 picture (noc) and the mask byte per pixel, and the two float32 flow views -- 16 bytes per pixel, or
+  // the two level grids once per pair
+  if (k == "interp") b = (double)width * height * (16.0 + 3.0 * noc + 1.0);
+  if (k == "interp_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * (3.0 * noc + 1.0);
   *bytes = b;
   return OFDIS_OK;
 }

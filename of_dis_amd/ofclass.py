@@ -593,6 +593,125 @@ class Context:
                                            valid.ctypes.data if want_valid else None), "ofdis_run_warp_u8_host")
         return (out, valid) if want_valid else out
 
+    def interp_ptr(self, a_ptr: int, b_ptr: int, fw_ptr: int, bw_ptr: int, view: FlowView, n: int, width: int,
+                   height: int, noc: int, t, out_dtype: int, out_ptr: int, valid_ptr: int = 0, occ_a_ptr: int = 0,
+                   occ_b_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_interp_u8`` on raw device pointers (0: no mask output / no occlusion mask); t a scalar or a sequence
+        of times; out_dtype IMG_U8 / IMG_F32."""
+        tt = _times(t)
+        check(lib().ofdis_interp_u8(self._h, a_ptr or None, b_ptr or None, fw_ptr or None, bw_ptr or None,
+                                    C.byref(view), n, width, height, noc, tt.ctypes.data, tt.size, occ_a_ptr or None,
+                                    occ_b_ptr or None, out_dtype, out_ptr or None, valid_ptr or None, stream or None),
+              "ofdis_interp_u8")
+
+    def interp(self, a, b, flow_fw, flow_bw, t=0.5, occ_fw=None, occ_bw=None, out_dtype=None, layout: str = "nhwc",
+               grid: str = "full", p: Optional[Params] = None, want_valid: bool = False):
+        """The frames between a and b at the times t (a scalar or a sequence of at most INTERP_MAX_T values in [0, 1])
+        from the pair's two flows (the definition is in ofdis.h): torch.uint8 CUDA tensors [n, h, w] or [n, h, w, 3] ->
+        [n, nt, h, w] or [n, nt, h, w, 3], torch.uint8 (the default) or torch.float32; with want_valid the tuple
+        (pictures, valid uint8 [n, nt, h, w]: 3 both frames, 1 frame a only, 2 frame b only, 0 neither).
+        flow_fw (a -> b) and flow_bw (b -> a): two outputs of ``run`` / ``run_bidir`` in one format, described as for
+        ``warp`` (dtype from the tensors, layout, grid; grid "level" needs `p`).  occ_fw / occ_bw: the occlusion masks
+        of ``run_bidir`` / ``fb_check`` ([n, h, w] uint8); a pixel that samples a marked position of one frame takes the
+        other frame alone."""
+        import torch
+        gray = a.dim() == 3
+        a4, b4 = (a.unsqueeze(-1), b.unsqueeze(-1)) if gray else (a, b)
+        if (a4.dim() != 4 or a4.shape[-1] not in (1, 3) or a4.dtype != torch.uint8 or a.shape != b.shape
+                or b.dtype != torch.uint8 or not (a.is_cuda and b.is_cuda and flow_fw.is_cuda and flow_bw.is_cuda)):
+            raise ValueError("expected two uint8 CUDA tensors [n, h, w] or [n, h, w, 3] of one shape and two CUDA flow tensors")
+        n, h, w, noc = a4.shape
+        if flow_fw.dtype != flow_bw.dtype:
+            raise ValueError("the two flows must have one dtype")
+        fmt = out_format(flow_fw.dtype, layout, grid)
+        view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        if grid == "level":
+            if p is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'interp: grid="level" needs the parameters the flows were computed with')
+            g = out_geometry(p, w, h, False, flow_fw.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        want = (n, 2, view.gh, view.gw) if fmt.layout else (n, view.gh, view.gw, 2)
+        if tuple(flow_fw.shape) != want or tuple(flow_bw.shape) != want:
+            raise ValueError(f"flows have shapes {tuple(flow_fw.shape)} and {tuple(flow_bw.shape)}, expected {want}")
+        for occ in (occ_fw, occ_bw):
+            if occ is not None and (tuple(occ.shape) != (n, h, w) or occ.dtype != torch.uint8 or not occ.is_cuda):
+                raise ValueError(f"expected uint8 CUDA occlusion masks of shape {(n, h, w)}")
+        if out_dtype not in (None, torch.uint8, torch.float32):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"interp: out_dtype {out_dtype!r}")
+        f32 = out_dtype == torch.float32
+        tt = _times(t)
+        a4, b4, flow_fw, flow_bw = a4.contiguous(), b4.contiguous(), flow_fw.contiguous(), flow_bw.contiguous()
+        occ_fw = occ_fw.contiguous() if occ_fw is not None else None
+        occ_bw = occ_bw.contiguous() if occ_bw is not None else None
+        shape = (n, tt.size, h, w) if gray else (n, tt.size, h, w, 3)
+        out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=a.device)
+        valid = torch.empty((n, tt.size, h, w), dtype=torch.uint8, device=a.device) if want_valid else None
+        self.interp_ptr(a4.data_ptr(), b4.data_ptr(), flow_fw.data_ptr(), flow_bw.data_ptr(), view, n, w, h, noc, tt,
+                        IMG_F32 if f32 else IMG_U8, out.data_ptr(), valid.data_ptr() if want_valid else 0,
+                        occ_fw.data_ptr() if occ_fw is not None else 0, occ_bw.data_ptr() if occ_bw is not None else 0,
+                        torch.cuda.current_stream(a.device).cuda_stream)
+        return (out, valid) if want_valid else out
+
+    def run_interp_ptr(self, a_ptr: int, b_ptr: int, n: int, width: int, height: int, p: Params, t, out_dtype: int,
+                       out_ptr: int, valid_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_run_interp_u8`` on raw device pointers, asynchronous on `stream` (valid_ptr 0: no mask)."""
+        tt = _times(t)
+        check(lib().ofdis_run_interp_u8(self._h, a_ptr or None, b_ptr or None, n, width, height, C.byref(p),
+                                        tt.ctypes.data, tt.size, out_dtype, out_ptr or None, valid_ptr or None,
+                                        stream or None), "ofdis_run_interp_u8")
+
+    def run_interp(self, a, b, p: Params, t=0.5, out_dtype=None, want_valid: bool = False):
+        """Frame interpolation in one call: both flows of each pair from one pyramid, then the frames at the times t.
+        torch.uint8 CUDA tensors [n, h, w] or [n, h, w, 3] -> [n, nt, h, w] or [n, nt, h, w, 3] (torch.uint8, or
+        torch.float32), with want_valid the tuple (pictures, valid [n, nt, h, w]).  Bit for bit
+        ``interp(a, b, *run_bidir(a, b, p)[:2], t)``, but both flows stay on their level grids: no full-resolution
+        flow is written.  Takes no occlusion masks (compose ``run_bidir`` and ``interp`` for those)."""
+        import torch
+        gray = a.dim() == 3
+        a4, b4 = (a.unsqueeze(-1), b.unsqueeze(-1)) if gray else (a, b)
+        if (a4.dim() != 4 or a4.shape[-1] != p.noc or a4.dtype != torch.uint8 or a.shape != b.shape
+                or b.dtype != torch.uint8 or not (a.is_cuda and b.is_cuda)):
+            raise ValueError("expected two uint8 CUDA tensors of one shape with noc channels")
+        if out_dtype not in (None, torch.uint8, torch.float32):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_interp: out_dtype {out_dtype!r}")
+        f32 = out_dtype == torch.float32
+        tt = _times(t)
+        n, h, w, _ = a4.shape
+        a4, b4 = a4.contiguous(), b4.contiguous()
+        shape = (n, tt.size, h, w) if gray else (n, tt.size, h, w, 3)
+        out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=a.device)
+        valid = torch.empty((n, tt.size, h, w), dtype=torch.uint8, device=a.device) if want_valid else None
+        self.run_interp_ptr(a4.data_ptr(), b4.data_ptr(), n, w, h, p, tt, IMG_F32 if f32 else IMG_U8, out.data_ptr(),
+                            valid.data_ptr() if want_valid else 0, torch.cuda.current_stream(a.device).cuda_stream)
+        return (out, valid) if want_valid else out
+
+    def run_interp_host(self, a: np.ndarray, b: np.ndarray, p: Params, t=0.5, out_dtype=np.uint8,
+                        want_valid: bool = False):
+        """run_interp on numpy u8 arrays; synchronous.  The inputs as for ``run_warp_host``; the pictures have the
+        input's shape with an axis of nt times in front of the frame axes ([n, nt, h, w(, c)]; [nt, h, w(, c)] for a
+        single pair), valid is [n, nt, h, w] ([nt, h, w])."""
+        if np.dtype(out_dtype) not in (np.dtype(np.uint8), np.dtype(_f32)):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_interp_host: out_dtype {out_dtype!r}")
+        a = np.ascontiguousarray(a, np.uint8)
+        b = np.ascontiguousarray(b, np.uint8)
+        if a.shape != b.shape or a.ndim < 2 or a.ndim > 4:
+            raise ValueError("expected two uint8 arrays of one shape")
+        channels = a.ndim == 4 or (a.ndim == 3 and a.shape[-1] == p.noc and (p.noc == 3 or a.shape[-1] == 1))
+        if channels and a.shape[-1] != p.noc:
+            raise ValueError("expected noc channels")
+        h, w = a.shape[-3:-1] if channels else a.shape[-2:]
+        single = a.ndim == (3 if channels else 2)
+        n = 1 if single else a.shape[0]
+        tt = _times(t)
+        lead = () if single else (n,)
+        out = np.empty(lead + (tt.size,) + a.shape[a.ndim - (3 if channels else 2):], out_dtype)
+        valid = np.empty(lead + (tt.size, h, w), np.uint8) if want_valid else None
+        check(lib().ofdis_run_interp_u8_host(self._h, a.ctypes.data, b.ctypes.data, n, w, h, C.byref(p), tt.ctypes.data,
+                                             tt.size, IMG_F32 if np.dtype(out_dtype) == _f32 else IMG_U8,
+                                             out.ctypes.data, valid.ctypes.data if want_valid else None),
+              "ofdis_run_interp_u8_host")
+        return (out, valid) if want_valid else out
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
@@ -653,6 +772,11 @@ def _out_shape(p: Params, width: int, height: int, n: int, with_init: bool, fmt:
     check(lib().ofdis_out_geometry(C.byref(p), width, height, int(with_init), C.byref(fmt), C.byref(ow), C.byref(oh),
                                    None, None, None, None), "ofdis_out_geometry")
     return (n, p.nop, oh.value, ow.value) if fmt.layout else (n, oh.value, ow.value, p.nop)
+
+
+def _times(t) -> np.ndarray:
+    """The times of an interpolation call, a scalar or a sequence, as the float32 array the library copies."""
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(t, _f32)).reshape(-1))
 
 
 def write_pnm(path: str, pixels: np.ndarray) -> None:
