@@ -433,8 +433,7 @@ int ofdis_interp_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img
  * flows leave the coarse-to-fine loop as float32 level grids, 2 * n * bytes_per_pair bytes in the buffer the context
  * owns, and the interpolation expands them on the fly: no full-resolution flow is allocated or written and no upsample
  * runs, and every further time of a pair reuses the expanded flows.  valid may be NULL.
- * The fused call takes no masks: the consistency check is defined on full-resolution fields.  A caller who wants them
- * composes ofdis_run_bidir_u8 and ofdis_interp_u8(occ_a = occ_fw, occ_b = occ_bw).
+ * This call takes no masks; ofdis_run_interp_occ_u8 (below) is the fused call with them.
  * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED.  No initial flow.  verbosity is ignored.  A stage
  * capture that is set is refused as in ofdis_run_bidir_u8 (OFDIS_ERR_UNSUPPORTED).  Argument errors as for
  * ofdis_run_batch_u8 and ofdis_interp_u8; stream, ordering, chunking, round-robin, graph and workspace rules are those
@@ -446,6 +445,61 @@ int ofdis_run_interp_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t 
 int ofdis_run_interp_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
                              int height, const ofdis_params *p, const float *t, int nt, int out_dtype, void *out,
                              uint8_t *valid);
+
+/* ------------------------------------------------------------------ occlusion masks on level grids, video interpolation
+ *
+ * ofdis_fb_check_level: ofdis_fb_check evaluated directly on two level grids.  grid_fw, grid_bw: device float32
+ * [n][gh][gw][2], the forward and backward level grids of ofdis_run_batch_u8_fmt ({F32, INTERLEAVED, LEVEL}); view: that
+ * format with the geometry ofdis_out_geometry reports (gw, gh, cell, off_x, off_y).  With E(G) the full-resolution
+ * field ofdis_warp_u8's level view defines for grid G -- xtap on column x + off_x, ytap on row y + off_y, up_px_s: the
+ * value the plain call's upsample computes; the cell at (x + off_x, y + off_y) itself when cell = 1 -- the outputs are
+ * ofdis_fb_check(E(grid_fw), E(grid_bw)) bit for bit: masks, errors, the codes 0 / 1 / 2, +inf outside the frame and the
+ * canonical NaN.  Neither expanded field is written: a pixel's own flow is expanded from its grid as the warp does it,
+ * the other field at the four taps of x + flow from the other grid's cells.
+ * Any other dtype, layout or grid in `view` returns OFDIS_ERR_UNSUPPORTED (a valid enum value; an unknown one is
+ * OFDIS_ERR_INVALID_ARGUMENT); a NULL view or a geometry ofdis_warp_u8 refuses returns OFDIS_ERR_INVALID_ARGUMENT.
+ * Thresholds, NULL rules (all four outputs NULL: OFDIS_OK, nothing enqueued), stream and ordering rules are those of
+ * ofdis_fb_check. */
+int ofdis_fb_check_level(ofdis_context *ctx, const float *grid_fw, const float *grid_bw, const ofdis_flow_view *view,
+                         int n, int width, int height, float alpha, float beta, uint8_t *occ_fw, uint8_t *occ_bw,
+                         float *err_fw, float *err_bw, void *stream);
+
+/* ofdis_run_interp_u8 with occlusion masks.  By definition out / valid == ofdis_interp_u8(img_a, img_b, F, B,
+ * occ_a = occ_fw, occ_b = occ_bw) bit for bit, where F, B, occ_fw, occ_bw are the four outputs of
+ * ofdis_run_bidir_u8(alpha, beta) -- but per chunk the two level grids are written, ofdis_fb_check_level computes the
+ * masks from them and the interpolation reads grids and masks: no upsample runs and no full-resolution flow exists.
+ * occ_fw / occ_bw: optional device u8 [n][height][width] outputs, equal to ofdis_run_bidir_u8's; a mask that is NULL
+ * lives in the chunk's workspace (sized per chunk, not per call).
+ * Refusals and modes are those of ofdis_run_interp_u8, plus ofdis_fb_check's threshold rules.  The graph is recorded
+ * anew when, beyond ofdis_run_interp_u8's list, alpha, beta or a mask pointer changes, and a call with masks never
+ * replays the graph of one without. */
+int ofdis_run_interp_occ_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                            const ofdis_params *p, const float *t, int nt, float alpha, float beta, int out_dtype,
+                            void *out, uint8_t *valid, uint8_t *occ_fw, uint8_t *occ_bw, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_interp_occ_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
+                                 int height, const ofdis_params *p, const float *t, int nt, float alpha, float beta,
+                                 int out_dtype, void *out, uint8_t *valid, uint8_t *occ_fw, uint8_t *occ_bw);
+
+/* The frames between the frames of one video.  frames: device u8 [nframes][height][width][noc]; n = nframes - stride
+ * pairs, pair i being (frame i, frame i + stride); out [n][nt][height][width][noc], valid [n][nt][height][width] or
+ * NULL.  use_occ = 0: out / valid == ofdis_run_interp_u8(frames, frames + stride frames, n) bit for bit (alpha, beta,
+ * occ_fw, occ_bw are ignored); use_occ = 1: == ofdis_run_interp_occ_u8 on those arrays, occ_fw / occ_bw optional
+ * [n][height][width] outputs.  Every frame's pyramid is built once, nframes of them where the pair call builds 2n
+ * (ofdis_run_sequence_u8's plan); the interpolation reads frame b of pair i at frame i + stride of the same array.
+ * Chunked calls overlap by `stride` frames as documented for ofdis_run_sequence_u8.  Refusals: those of
+ * ofdis_run_sequence_u8's bidirectional form (stride < 1, nframes <= stride, OFDIS_MODE_DE, a set stage capture) and
+ * those of ofdis_run_interp_u8 / ofdis_run_interp_occ_u8.  A graph recorded by the pair call is never replayed by the
+ * sequence call on the same pointers, nor one of another stride. */
+int ofdis_run_sequence_interp_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, int stride, int width,
+                                 int height, const ofdis_params *p, const float *t, int nt, int use_occ, float alpha,
+                                 float beta, int out_dtype, void *out, uint8_t *valid, uint8_t *occ_fw,
+                                 uint8_t *occ_bw, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_sequence_interp_u8_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int stride, int width,
+                                      int height, const ofdis_params *p, const float *t, int nt, int use_occ,
+                                      float alpha, float beta, int out_dtype, void *out, uint8_t *valid,
+                                      uint8_t *occ_fw, uint8_t *occ_bw);
 
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
@@ -563,7 +617,8 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * it writes the plain format alone, else as "upsample_f16", "upsample_planar" or "upsample_planar_f16", and the
  * level-grid output that replaces it as "level_out"; the warp as "warp" with a full-resolution flow view and as
  * "warp_level" with a level-grid view; the left-right check as "lr_check" / "lr_check_err" like the forward-backward
- * one; the interpolation as "interp" with full-resolution flow views and as "interp_level" with level-grid views. */
+ * one; the interpolation as "interp" with full-resolution flow views and as "interp_level" with level-grid views; the
+ * forward-backward check on level grids as "fb_check_level", whatever it writes. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
@@ -575,7 +630,8 @@ const char *ofdis_kernel_names(void);
  * intermediate frame (the function has no nt argument; a call with nt times reads its flows once and does the rest nt
  * times): the two float32 flow views (16 bytes per pixel; the two level grids' 2 * gw * gh * 8 bytes per pair), 2 noc
  * bytes of image read, noc bytes of u8 output and the mask byte per pixel -- W * H * (16 + 3 noc + 1) and
- * 2 * gw * gh * 8 + W * H * (3 noc + 1). */
+ * 2 * gw * gh * 8 + W * H * (3 noc + 1).  "fb_check_level": both grids once, the mask byte and the 4-byte error per
+ * pixel and direction -- 2 * gw * gh * 8 + 2 * W * H * (1 + 4). */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */

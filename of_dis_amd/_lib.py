@@ -159,6 +159,11 @@ def lib():
         "ofdis_interp_u8": ([vp, vp, vp, vp, vp, V, i, i, i, i, vp, i, vp, vp, i, vp, vp, vp], i),
         "ofdis_run_interp_u8": ([vp, vp, vp, i, i, i, P, vp, i, i, vp, vp, vp], i),
         "ofdis_run_interp_u8_host": ([vp, vp, vp, i, i, i, P, vp, i, i, vp, vp], i),
+        "ofdis_fb_check_level": ([vp, vp, vp, V, i, i, i, f, f, vp, vp, vp, vp, vp], i),
+        "ofdis_run_interp_occ_u8": ([vp, vp, vp, i, i, i, P, vp, i, f, f, i, vp, vp, vp, vp, vp], i),
+        "ofdis_run_interp_occ_u8_host": ([vp, vp, vp, i, i, i, P, vp, i, f, f, i, vp, vp, vp, vp], i),
+        "ofdis_run_sequence_interp_u8": ([vp, vp, i, i, i, i, P, vp, i, i, f, f, i, vp, vp, vp, vp, vp], i),
+        "ofdis_run_sequence_interp_u8_host": ([vp, vp, i, i, i, i, P, vp, i, i, f, f, i, vp, vp, vp, vp], i),
         "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),

@@ -188,6 +188,17 @@ struct FbArgs {
   float alpha, beta;
 };
 
+// Forward-backward consistency of two float32 interleaved level grids of one geometry, as if on the fields they
+// expand to (include/ofdis.h: ofdis_fb_check_level).
+struct FbLevelArgs {
+  const float *gfw, *gbw;    // [n][gh][gw][2]
+  uint8_t *occ_fw, *occ_bw;  // [n][H][W] mask codes 0 / 1 / 2, or NULL
+  float *err_fw, *err_bw;    // [n][H][W] squared round-trip error, or NULL
+  int n, W, H;               // W * H < 2^31
+  float alpha, beta;
+  int gw, gh, log2c, offx, offy;  // as WarpArgs
+};
+
 // Left-right consistency of two full-resolution disparity fields (include/ofdis.h: ofdis_lr_check).
 struct LrArgs {
   const float *dl, *dr;    // [n][H][W]
@@ -230,6 +241,7 @@ struct InterpArgs {
 void launch_warp(const WarpArgs &a, hipStream_t s);
 void launch_interp(const InterpArgs &a, hipStream_t s);
 void launch_fb_check(const FbArgs &a, hipStream_t s);
+void launch_fb_check_level(const FbLevelArgs &a, hipStream_t s);
 void launch_lr_check(const LrArgs &a, hipStream_t s);
 void launch_init_area(const InitArgs &a, hipStream_t s);
 void warm_kernels_module(hipStream_t s);  // one empty launch per kernel translation unit: loads its code object

@@ -30,7 +30,8 @@
 //                k_tv_final<TH>      refine_variational.cpp:209-227,305-323
 //   output       k_upsample, k_upsample_rows, k_upsample_h<R>, k_upsample_rows1  run_dense.cpp:407-415
 //                (<T, PLANAR>: the float16 / planar output formats), k_level_out  (ofdis_out_format)
-//   fb check     k_fb_check<OCC, ERR, PX>  forward-backward consistency masks of two flow fields (no reference code)
+//   fb check     k_fb_check<OCC, ERR, PX>  forward-backward consistency masks of two flow fields (no reference code);
+//                k_fb_check_level<OCC, ERR, PX>  the same on two level grids, expanded on the fly
 //   warp         k_warp<OT, NOC, FT, PLANAR, PX>, k_warp_level<OT, NOC, PX>  backward warp of u8 frames along a flow
 //                field / along the level grid expanded on the fly (no reference code)
 //   interp       k_interp<OT, NOC, FT, PLANAR, PX>, k_interp_level<OT, NOC, PX>  the frames between two u8 frames from
@@ -6349,6 +6350,202 @@ void launch_interp(const InterpArgs &a0, hipStream_t s) {
         else go(OT, NOC, Int<1>{});
       });
     });
+  }
+}
+
+// ------------------------------------------------------------------------------ forward-backward check on level grids
+// ofdis_fb_check on the two fields that two float32 interleaved level grids of one geometry expand to (include/ofdis.h:
+// ofdis_fb_check_level), neither of which is written.  Block shape and own-flow staging of k_warp_level -- the pixel's
+// own (u, v) is the upsample's expression on the staged window of its direction's grid -- and the directions in
+// blockIdx.z as in k_fb_check.  The other field is needed at the four taps of x + (u, v), which land anywhere in the
+// frame: each tap is expanded from the other grid's cells in global memory (a frame's grid is a few dozen KB and stays
+// in L2) with the same three functions, and fb_pixel's arithmetic follows on the four values.
+namespace {
+
+// One component of the other field at the four taps from the 3 x 3 cells c[row][col] that hold every cell they read:
+// rows ytap(y0).r0, ytap(y0).r1, ytap(y1).r1 and three columns from xtap(x0).sx.  dx: tap x1's first cell lies one
+// column on; jb0: ytap(y1).r0 is the second row, not the first.  up_px_s on two-element rows, so the operations are
+// k_upsample's.
+__device__ __forceinline__ void fb_level_comp(const float (&c)[3][3], bool dx, bool jb0, XTap xa, XTap xb,
+                                              const YTap &ya, const YTap &yb, float (&b)[4]) {
+  xa.sx = xb.sx = 0;
+#pragma unroll
+  for (int tx = 0; tx < 2; ++tx) {
+    float r[3][2];  // [row][s0 | s1] of this x tap
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      r[j][0] = tx && dx ? c[j][1] : c[j][0];
+      r[j][1] = tx && dx ? c[j][2] : c[j][1];
+    }
+    const float m[2] = {jb0 ? r[1][0] : r[0][0], jb0 ? r[1][1] : r[0][1]};
+    b[tx] = up_px_s(r[0], r[1], tx ? xb : xa, 1.f - ya.fy, ya.fy);   // b00, b01
+    b[2 + tx] = up_px_s(m, r[2], tx ? xb : xa, 1.f - yb.fy, yb.fy);  // b10, b11
+  }
+}
+
+// fb_pixel with the other field expanded from its grid G ([gh][gw][2], the frame's): the same positions, taps and
+// arithmetic.  x1 - x0 and y1 - y0 are 0 or 1 and a pixel step moves the source position by at most half a cell
+// (cell >= 2), so xtap(x1).sx is xtap(x0).sx or the column after it and ytap(y1).r0 is ytap(y0).r0 or ytap(y0).r1: the
+// cells of the four expansions lie in three columns from xtap(x0).sx of the rows ytap(y0).r0, ytap(y0).r1 and
+// ytap(y1).r1 -- nine 8-byte loads serve their sixteen cell reads.  cell = 1: the four cells themselves.
+__device__ __forceinline__ unsigned fb_level_pixel(const float *__restrict__ G, const FbLevelArgs &a, double scale,
+                                                   int x, int y, float u, float v, float &err) {
+  const int W = a.W, H = a.H;
+  const float px = (float)x + u, py = (float)y + v;
+  const bool inside = px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);  // false for NaN
+  const float pxs = inside ? px : 0.f, pys = inside ? py : 0.f;  // (no branch around the gather, as fb_pixel)
+  const int x0 = (int)floorf(pxs), y0 = (int)floorf(pys);  // in [0, W - 1] x [0, H - 1]
+  const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+  const float ax = pxs - (float)x0, ay = pys - (float)y0;
+  float bx[4], by[4];  // the other field at (x0, y0), (x1, y0), (x0, y1), (x1, y1): fb_pixel's b00, b01, b10, b11
+  if (a.log2c == 0) {
+    const long r0 = (long)(y0 + a.offy) * a.gw + a.offx, r1 = (long)(y1 + a.offy) * a.gw + a.offx;
+    const long o[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float2_u c = *reinterpret_cast<const float2_u *>(G + 2 * o[k]);
+      bx[k] = c.x, by[k] = c.y;
+    }
+  } else {
+    const XTap xa = xtap(x0 + a.offx, scale, a.gw), xb = xtap(x1 + a.offx, scale, a.gw);
+    const YTap ya = ytap(y0 + a.offy, scale, a.gh), yb = ytap(y1 + a.offy, scale, a.gh);
+    const int rows[3] = {ya.r0, ya.r1, yb.r1};
+    const int cols[3] = {xa.sx, min(xa.sx + 1, a.gw - 1), min(xa.sx + 2, a.gw - 1)};
+    float cu[3][3], cv[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float *R = G + 2 * ((long)rows[j] * a.gw);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float2_u c = *reinterpret_cast<const float2_u *>(R + 2 * cols[i]);
+        cu[j][i] = c.x, cv[j][i] = c.y;
+      }
+    }
+    const bool dx = xb.sx != xa.sx, jb0 = yb.r0 != ya.r0;
+    fb_level_comp(cu, dx, jb0, xa, xb, ya, yb, bx);
+    fb_level_comp(cv, dx, jb0, xa, xb, ya, yb, by);
+  }
+  const float top0 = bx[0] + ax * (bx[1] - bx[0]), bot0 = bx[2] + ax * (bx[3] - bx[2]);
+  const float top1 = by[0] + ax * (by[1] - by[0]), bot1 = by[2] + ax * (by[3] - by[2]);
+  const float bu = top0 + ay * (bot0 - top0), bv = top1 + ay * (bot1 - top1);
+  const float du = u + bu, dv = v + bv;
+  const float e = du * du + dv * dv;
+  const float mag = (u * u + v * v) + (bu * bu + bv * bv);
+  const float thr = a.alpha * mag + a.beta;
+  err = inside ? (e != e ? __builtin_nanf("") : e) : __builtin_inff();  // the canonical quiet NaN (fb_pixel)
+  return inside ? (e <= thr ? 0u : 1u) : 2u;  // NaN err -> 1
+}
+
+// PX = 4 / 1 and OCC / ERR as in k_fb_check (the vector stores under launch_fb_check_level's conditions).
+template <bool OCC, bool ERR, int PX>
+__global__ __launch_bounds__(256) void k_fb_check_level(FbLevelArgs a) {
+  __shared__ float src[kWarpSrcRows][2][kWarpSrcCols];  // [row][comp][col] of the direction's own grid
+  constexpr int kCols = 256 * PX;
+  const int dir = blockIdx.z & 1, f = blockIdx.z >> 1;
+  uint8_t *occ = OCC ? (dir ? a.occ_bw : a.occ_fw) : nullptr;
+  float *errp = ERR ? (dir ? a.err_bw : a.err_fw) : nullptr;
+  if (!occ && !errp) return;
+  const unsigned ncb = ((unsigned)a.W + kCols - 1) / kCols;
+  const int y0 = (int)(blockIdx.x / ncb) * kWarpRows;
+  const long xb = (long)(blockIdx.x % ncb) * kCols;
+  const long xl = xb + threadIdx.x * PX;
+  const int x = (int)(xl < a.W ? xl : a.W);
+  const long gplane = (long)a.gw * a.gh;
+  const float *F = (dir ? a.gbw : a.gfw) + 2 * f * gplane;  // the walked grid
+  const float *G = (dir ? a.gfw : a.gbw) + 2 * f * gplane;  // the gathered one
+  const double scale = 1.0 / (double)(1 << a.log2c);
+  auto emit = [&](int y, const float *u, const float *v) {
+    const long o = (long)f * a.H * a.W + (long)y * a.W + x;
+    float e[PX];
+    unsigned m = 0;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) m |= fb_level_pixel(G, a, scale, x + i, y, u[i], v[i], e[i]) << (8 * i);
+    if constexpr (PX == 4) {
+      if (occ) *reinterpret_cast<unsigned *>(occ + o) = m;
+      if (errp) *reinterpret_cast<float4_v *>(errp + o) = float4_v{e[0], e[1], e[2], e[3]};
+    } else {
+      if (occ) occ[o] = (uint8_t)m;
+      if (errp) errp[o] = e[0];
+    }
+  };
+  float u[PX], v[PX];
+  if (a.log2c == 0) {
+    if (x >= a.W) return;
+    for (int r = 0; r < kWarpRows; ++r) {
+      const int y = y0 + r;
+      if (y >= a.H) break;
+#pragma unroll
+      for (int i = 0; i < PX; ++i) {
+        const long c = (long)(y + a.offy) * a.gw + (x + i + a.offx);
+        u[i] = F[2 * c], v[i] = F[2 * c + 1];
+      }
+      emit(y, u, v);
+    }
+    return;
+  }
+  const int ylast = min(y0 + kWarpRows, a.H) - 1;
+  const int r_first = ytap(y0 + a.offy, scale, a.gh).r0;
+  const int nr = min(ytap(ylast + a.offy, scale, a.gh).r1 - r_first + 1, kWarpSrcRows);
+  const long c_raw = (2 * (xb + a.offx) + 1 - (1 << a.log2c)) >> (a.log2c + 1);  // (as k_warp_level)
+  const int c_lo = (int)(c_raw > 0 ? c_raw : 0);
+  const int ncol = min((kCols >> a.log2c) + 3, kWarpSrcCols);
+  for (int k = threadIdx.x; k < nr * 2 * ncol; k += 256) {
+    const int col = k % ncol, rc = k / ncol;  // rc = row * 2 + comp
+    const int sc = min(c_lo + col, a.gw - 1);
+    src[rc >> 1][rc & 1][col] = F[2 * ((long)(r_first + (rc >> 1)) * a.gw + sc) + (rc & 1)];
+  }
+  __syncthreads();
+  if (x >= a.W) return;
+  XTap xt[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    xt[i] = xtap(x + i + a.offx, scale, a.gw);
+    xt[i].sx = min(max(xt[i].sx - c_lo, 0), kWarpSrcCols - 2);  // (inside the staged window by construction)
+  }
+  for (int r = 0; r < kWarpRows; ++r) {
+    const int y = y0 + r;
+    if (y >= a.H) break;
+    const YTap yt = ytap(y + a.offy, scale, a.gh);
+    const int j0 = min(max(yt.r0 - r_first, 0), nr - 1), j1 = min(max(yt.r1 - r_first, 0), nr - 1);
+    const float b0 = 1.f - yt.fy, b1 = yt.fy;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      u[i] = up_px_s(src[j0][0], src[j1][0], xt[i], b0, b1);
+      v[i] = up_px_s(src[j0][1], src[j1][1], xt[i], b0, b1);
+    }
+    emit(y, u, v);
+  }
+}
+
+}  // namespace
+// ---- launch
+// Frames and directions go in grid z as in launch_fb_check, 32767 frames per launch.  The vector stores need
+// W % 4 == 0, the error maps 16-byte and the masks 4-byte aligned; the grids are read cell by cell.
+void launch_fb_check_level(const FbLevelArgs &a0, hipStream_t s) {
+  const bool occ = a0.occ_fw || a0.occ_bw, err = a0.err_fw || a0.err_bw;
+  if (!occ && !err) return;
+  const bool vec = a0.W % 4 == 0 && ((uintptr_t)a0.err_fw | (uintptr_t)a0.err_bw) % 16 == 0 &&
+                   ((uintptr_t)a0.occ_fw | (uintptr_t)a0.occ_bw) % 4 == 0;
+  const long frame = (long)a0.W * a0.H, gframe = (long)a0.gw * a0.gh * 2;
+  const int kSlice = 32767;  // 2 * frames <= 65535 (grid z)
+  for (int f0 = 0; f0 < a0.n; f0 += kSlice) {
+    FbLevelArgs a = a0;
+    a.n = std::min(kSlice, a0.n - f0);
+    a.gfw += f0 * gframe;
+    a.gbw += f0 * gframe;
+    if (a.occ_fw) a.occ_fw += f0 * frame;
+    if (a.occ_bw) a.occ_bw += f0 * frame;
+    if (a.err_fw) a.err_fw += f0 * frame;
+    if (a.err_bw) a.err_bw += f0 * frame;
+    auto go = [&](auto O, auto E) {
+      if (vec)
+        k_fb_check_level<O != 0, E != 0, 4><<<dim3(ceil_div(a.H, kWarpRows) * ceil_div(a.W, 1024), 1, 2 * a.n), 256, 0, s>>>(a);
+      else
+        k_fb_check_level<O != 0, E != 0, 1><<<dim3(ceil_div(a.H, kWarpRows) * ceil_div(a.W, 256), 1, 2 * a.n), 256, 0, s>>>(a);
+    };
+    if (occ && err) go(Int<1>{}, Int<1>{});
+    else if (occ) go(Int<1>{}, Int<0>{});
+    else go(Int<0>{}, Int<1>{});
   }
 }
 

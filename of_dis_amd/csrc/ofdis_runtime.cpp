@@ -37,7 +37,9 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     // the left-right check writing masks only / also an error map
                                     "lr_check", "lr_check_err",
                                     // the interpolation with full-resolution flow views / with level-grid views
-                                    "interp", "interp_level"};
+                                    "interp", "interp_level",
+                                    // the forward-backward check on two level grids
+                                    "fb_check_level"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -63,7 +65,8 @@ struct Plan {
   bool fb = false;      // usefbcon: backward grid, flow and refinement
   bool bidir = false;   // ofdis_run_bidir_u8: the backward grid, flow and refinement at every level, sc_l included
   size_t off_up_bw = 0; // bidir without a caller's flow_bw: the full-resolution backward flow [n][H0][W0][2];
-                        // stereo without a caller's disp_r: the right view's disparity [n / 2][H0][W0]
+                        // stereo without a caller's disp_r: the right view's disparity [n / 2][H0][W0];
+                        // an interpolation with masks: the chunk's two masks, u8 [2][n][H0][W0]
   bool gradmag = false; // SELECTCHANNEL 2: float level 0 (gradient magnitude) halved down to sc_l
   size_t off_gm = 0;    // its scratch: [nfr][Hp][Wp] + [nfr][Hp/2][Wp/2] (ping-pong)
   size_t total = 0;
@@ -121,7 +124,8 @@ struct ofdis_context {
   } gkey;
   hipGraphExec_t gexec = nullptr;
   // ofdis_run_interp_u8 records gkey with warp = 2 (warp_out / warp_valid / warp_buf / warp_f32 its picture, mask,
-  // buffer and dtype) and its times here; the graph of such a call is replayed only while both agree
+  // buffer and dtype) and its times here; the graph of such a call is replayed only while both agree.  With masks
+  // (ofdis_run_interp_occ_u8) gkey.bidir, occ_fw, occ_bw, alpha and beta say so; the sequence form sets seq / stride
   struct InterpKey {
     int nt = 0;
     float t[kInterpMaxT] = {};
@@ -791,7 +795,8 @@ int run_pyramid(ofdis_context *c, char *ws, const Plan &P, const uint8_t *a, con
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
-// bidir: 0 plain, 1 both directions, 2 both directions and the full-resolution backward flow kept in the workspace
+// bidir: 0 plain, 1 both directions, 2 both directions and the full-resolution backward flow kept in the workspace,
+//        3 both directions and the two occlusion masks of the pairs kept in the workspace (ofdis_run_interp_occ_u8)
 // stride: 0 two arrays of n frames, k > 0 one sequence of n + k frames
 // stereo: 0 no, 1 n stereo pairs as 2n flow pairs, 2 the same and the right view's disparity kept in the workspace
 Plan batch_plan(const ofdis_params *p, int n, int width, int height, bool init = false, int bidir = 0,
@@ -802,6 +807,7 @@ Plan batch_plan(const ofdis_params *p, int n, int width, int height, bool init =
   P.stereo = stereo != 0;
   P.off_up_bw = P.total;
   if (bidir == 2 || stereo == 2) P.total = align_up(P.total + sizeof(float) * (size_t)n * width * height * P.nop);
+  if (bidir == 3) P.total = align_up(P.total + 2 * (size_t)n * width * height);
   P.W0 = width;
   P.H0 = height;
   P.padw = padw;
@@ -972,6 +978,31 @@ int run_fb_check(ofdis_context *c, const float *fw, const float *bw, int n, int 
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
+// The consistency check of n frames on their two float32 interleaved level grids of geometry v (timer
+// "fb_check_level").
+int run_fb_check_level(ofdis_context *c, const float *gfw, const float *gbw, const ofdis_flow_view &v, int n, int width,
+                       int height, const BidirOut &o, hipStream_t s) {
+  FbLevelArgs fa{};
+  fa.gfw = gfw;
+  fa.gbw = gbw;
+  fa.occ_fw = o.occ_fw;
+  fa.occ_bw = o.occ_bw;
+  fa.err_fw = o.err_fw;
+  fa.err_bw = o.err_bw;
+  fa.n = n;
+  fa.W = width;
+  fa.H = height;
+  fa.alpha = o.alpha;
+  fa.beta = o.beta;
+  fa.gw = v.gw;
+  fa.gh = v.gh;
+  fa.offx = v.off_x;
+  fa.offy = v.off_y;
+  while ((1 << fa.log2c) < v.cell) ++fa.log2c;
+  timed(c, 24, s, [&] { launch_fb_check_level(fa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
 // The left-right check of n frames (timer "lr_check_err" when an error map is written, else "lr_check").
 int run_lr_check(ofdis_context *c, const float *dl, const float *dr, int n, int width, int height, const BidirOut &o,
                  hipStream_t s) {
@@ -1040,10 +1071,17 @@ struct InterpOut {
   const uint8_t *occ_a = nullptr, *occ_b = nullptr;
   int f32 = 0, nt = 0;
   float t[kInterpMaxT] = {};
+  // the fused calls with masks (ofdis_run_interp_occ_u8): the masks come from the chunk's level grids at these
+  // thresholds and go to the caller's arrays, or where one is NULL to the chunk's workspace
+  bool use_occ = false;
+  uint8_t *occ_fw = nullptr, *occ_bw = nullptr;
+  float alpha = 0.f, beta = 0.f;
   InterpOut at(size_t f0, size_t px, int noc) const {
     InterpOut o = *this;
     o.out = (char *)out + f0 * nt * px * noc * (f32 ? 4 : 1);
     if (valid) o.valid += f0 * nt * px;
+    if (occ_fw) o.occ_fw += f0 * px;
+    if (occ_bw) o.occ_bw += f0 * px;
     return o;
   }
 };
@@ -1110,10 +1148,12 @@ int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, 
 
 // One chunk of ofdis_run_interp_u8 (P a bidirectional plan, no initial flow): the pipeline of run_chunk, then both
 // flows of the finest level x 2^sc_l as float32 interleaved level grids (grid_fw, grid_bw: the chunk's share of the
-// context's buffer) and the pictures from them.  No upsample runs.
+// context's buffer) and the pictures from them.  No upsample runs.  io.use_occ: the check on the two grids in between,
+// its masks read by the interpolation.  A sequence plan: img_a is the chunk's first frame and the pyramid reads its
+// n + stride frames from there; img_b, frame b of the chunk's first pair, is read by the interpolation alone.
 int run_chunk_interp(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
                      const uint8_t *img_b, void *grid_fw, void *grid_bw, const InterpOut &io, hipStream_t s) {
-  int rc = run_pyramid(c, ws, P, img_a, img_b, s);
+  int rc = run_pyramid(c, ws, P, img_a, P.seq ? nullptr : img_b, s);
   if (rc) return rc;
   if ((rc = run_levels(c, ws, P, p, s, nullptr, nullptr))) return rc;
   for (int dir = 0; dir < 2; ++dir) {
@@ -1129,7 +1169,18 @@ int run_chunk_interp(ofdis_context *c, char *ws, const Plan &P, const ofdis_para
     if (hipGetLastError() != hipSuccess) return OFDIS_ERR_DEVICE;
   }
   ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
-  return run_interp(c, img_a, img_b, grid_fw, grid_bw, v, P.n, P.W0, P.H0, P.noc, io, s);
+  if (!io.use_occ) return run_interp(c, img_a, img_b, grid_fw, grid_bw, v, P.n, P.W0, P.H0, P.noc, io, s);
+  const size_t px = (size_t)P.n * P.W0 * P.H0;
+  BidirOut bo;
+  bo.occ_fw = io.occ_fw ? io.occ_fw : (uint8_t *)(ws + P.off_up_bw);
+  bo.occ_bw = io.occ_bw ? io.occ_bw : (uint8_t *)(ws + P.off_up_bw) + px;
+  bo.alpha = io.alpha;
+  bo.beta = io.beta;
+  if ((rc = run_fb_check_level(c, (const float *)grid_fw, (const float *)grid_bw, v, P.n, P.W0, P.H0, bo, s))) return rc;
+  InterpOut masked = io;
+  masked.occ_a = bo.occ_fw;
+  masked.occ_b = bo.occ_bw;
+  return run_interp(c, img_a, img_b, grid_fw, grid_bw, v, P.n, P.W0, P.H0, P.noc, masked, s);
 }
 
 // k lanes (stream, done event, workspace of `bytes`).
@@ -1378,10 +1429,12 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
 
 // ofdis_run_interp_u8 on stream s (no stage capture is set): the bidirectional plan with nothing kept at full
 // resolution, the 2 n level grids in the context's buffer, and run_batch's chunk, lane and graph rules.
+// stride > 0: img_a is a sequence of n + stride frames (the sequence plan) and img_b its frame `stride`.
 int run_batch_interp(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
-                     int height, const ofdis_params *p, const InterpOut &io) {
+                     int height, const ofdis_params *p, const InterpOut &io, int stride = 0) {
   CallPlan cp;
-  int rc = prepare(c, p, n, width, height, false, false, cp, 1);
+  // (masks the caller does not take live in the chunk's workspace)
+  int rc = prepare(c, p, n, width, height, false, false, cp, io.use_occ && !(io.occ_fw && io.occ_bw) ? 3 : 1, stride);
   if (rc) return rc;
   const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
   cp.out_pair = (size_t)P1.lv[0].w * P1.lv[0].h * P1.nop * 4;  // a pair's float32 level grid
@@ -1394,6 +1447,10 @@ int run_batch_interp(ofdis_context *c, hipStream_t s, const uint8_t *img_a, cons
   key.n = n; key.w = width; key.h = height; key.p = *p;
   key.out_level = 1;
   key.warp = 2; key.warp_out = io.out; key.warp_valid = io.valid; key.warp_buf = c->warp_buf; key.warp_f32 = io.f32;
+  key.seq = stride > 0; key.stride = stride;  // a sequence call on a pair call's buffers records anew
+  if (io.use_occ) {  // and so does a call with masks after one without, or with other thresholds or mask arrays
+    key.bidir = 1; key.occ_fw = io.occ_fw; key.occ_bw = io.occ_bw; key.alpha = io.alpha; key.beta = io.beta;
+  }
   ofdis_context::InterpKey ikey;
   std::memset(&ikey, 0, sizeof(ikey));
   ikey.nt = io.nt;
@@ -2116,6 +2173,153 @@ int ofdis_run_interp_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8
   return rc;
 }
 
+// ------------------------------------------------- occlusion masks on level grids, video interpolation (include/ofdis.h)
+
+int ofdis_fb_check_level(ofdis_context *c, const float *grid_fw, const float *grid_bw, const ofdis_flow_view *v, int n,
+                         int width, int height, float alpha, float beta, uint8_t *occ_fw, uint8_t *occ_bw,
+                         float *err_fw, float *err_bw, void *stream) {
+  if (!c || !grid_fw || !grid_bw || !v || n <= 0 || width <= 0 || height <= 0 || !fb_thresholds_ok(alpha, beta) ||
+      (long)width * height > 0x7fffffffL)
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED || v->grid != OFDIS_OUT_LEVEL)
+    return OFDIS_ERR_UNSUPPORTED;  // the float32 interleaved level grid alone
+  if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  BidirOut o;
+  o.occ_fw = occ_fw;
+  o.occ_bw = occ_bw;
+  o.err_fw = err_fw;
+  o.err_bw = err_bw;
+  o.alpha = alpha;
+  o.beta = beta;
+  if (!o.checks()) return OFDIS_OK;
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
+  if (rc) return rc;
+  rc = run_fb_check_level(c, grid_fw, grid_bw, *v, n, width, height, o, s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+namespace {
+// The fused interpolation calls beyond ofdis_run_interp_u8: masks (use_occ) and the sequence plan (stride > 0: img_a is
+// the array of n + stride frames).  Arguments checked as ofdis_run_interp_u8 checks them, plus the thresholds.
+int run_interp_call(ofdis_context *c, const uint8_t *img_a, int n, int stride, const uint8_t *img_b, int width,
+                    int height, const ofdis_params *p, const float *t, int nt, bool use_occ, float alpha, float beta,
+                    int out_dtype, void *out, uint8_t *valid, uint8_t *occ_fw, uint8_t *occ_bw, void *stream) {
+  if (!c || !img_a || !out || n <= 0 || width <= 0 || height <= 0 || !p || !img_dtype_ok(out_dtype) ||
+      (long)width * height > 0x7fffffffL || !interp_times_ok(t, nt) || (use_occ && !fb_thresholds_ok(alpha, beta)))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // (as ofdis_run_bidir_u8)
+  InterpOut o;
+  o.out = out;
+  o.valid = valid;
+  o.f32 = out_dtype == OFDIS_IMG_F32;
+  o.nt = nt;
+  std::memcpy(o.t, t, sizeof(float) * nt);
+  if (use_occ) {
+    o.use_occ = true;
+    o.occ_fw = occ_fw;
+    o.occ_bw = occ_bw;
+    o.alpha = alpha;
+    o.beta = beta;
+  }
+  if (stride > 0) img_b = img_a + (size_t)stride * width * height * p->noc;
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch_interp(c, s, img_a, img_b, n, width, height, p, o, stride);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+// Host form of run_interp_call (synchronous): one device block -- the in_a bytes of img_a, the in_b bytes of img_b (a
+// sequence has none), the pictures, and the masks asked for, each at a multiple of 256 bytes.
+int run_interp_call_host(ofdis_context *c, const uint8_t *img_a, size_t in_a, const uint8_t *img_b, size_t in_b, int n,
+                         int stride, int width, int height, const ofdis_params *p, const float *t, int nt, bool use_occ,
+                         float alpha, float beta, int out_dtype, void *out, uint8_t *valid, uint8_t *occ_fw,
+                         uint8_t *occ_bw) {
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)n * width * height, outb = px * p->noc * nt * (out_dtype == OFDIS_IMG_F32 ? 4 : 1);
+  uint8_t *const host_u[3] = {valid, use_occ ? occ_fw : nullptr, use_occ ? occ_bw : nullptr};
+  const size_t bytes_u[3] = {px * nt, px, px};
+  const size_t off_b = align_up(in_a), off_out = off_b + align_up(in_b);
+  size_t off_u[3], total = off_out + align_up(outb);
+  for (int k = 0; k < 3; ++k) {
+    off_u[k] = total;
+    if (host_u[k]) total += align_up(bytes_u[k]);
+  }
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, total));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  auto dev_u = [&](int k) { return host_u[k] ? (uint8_t *)(d + off_u[k]) : nullptr; };
+  if (step(hipMemcpyAsync(d, img_a, in_a, hipMemcpyHostToDevice, c->stream)) &&
+      (!in_b || step(hipMemcpyAsync(d + off_b, img_b, in_b, hipMemcpyHostToDevice, c->stream)))) {
+    rc = run_interp_call(c, (const uint8_t *)d, n, stride, in_b ? (const uint8_t *)(d + off_b) : nullptr, width, height,
+                         p, t, nt, use_occ, alpha, beta, out_dtype, d + off_out, dev_u(0), dev_u(1), dev_u(2), c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      step(hipMemcpy(out, d + off_out, outb, hipMemcpyDeviceToHost));
+      for (int k = 0; k < 3; ++k)
+        if (host_u[k]) step(hipMemcpy(host_u[k], d + off_u[k], bytes_u[k], hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+}  // namespace
+
+int ofdis_run_interp_occ_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                            const ofdis_params *p, const float *t, int nt, float alpha, float beta, int out_dtype,
+                            void *out, uint8_t *valid, uint8_t *occ_fw, uint8_t *occ_bw, void *stream) {
+  if (!img_b) return OFDIS_ERR_INVALID_ARGUMENT;
+  return run_interp_call(c, img_a, n, 0, img_b, width, height, p, t, nt, true, alpha, beta, out_dtype, out, valid, occ_fw,
+                         occ_bw, stream);
+}
+
+int ofdis_run_interp_occ_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
+                                 int height, const ofdis_params *p, const float *t, int nt, float alpha, float beta,
+                                 int out_dtype, void *out, uint8_t *valid, uint8_t *occ_fw, uint8_t *occ_bw) {
+  if (!c || !img_a || !img_b || !out || n <= 0 || width <= 0 || height <= 0 || !p || !img_dtype_ok(out_dtype) ||
+      (p->noc != 1 && p->noc != 3) || !interp_times_ok(t, nt))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  const size_t in = (size_t)n * width * height * p->noc;
+  return run_interp_call_host(c, img_a, in, img_b, in, n, 0, width, height, p, t, nt, true, alpha, beta, out_dtype, out,
+                              valid, occ_fw, occ_bw);
+}
+
+int ofdis_run_sequence_interp_u8(ofdis_context *c, const uint8_t *frames, int nframes, int stride, int width,
+                                 int height, const ofdis_params *p, const float *t, int nt, int use_occ, float alpha,
+                                 float beta, int out_dtype, void *out, uint8_t *valid, uint8_t *occ_fw,
+                                 uint8_t *occ_bw, void *stream) {
+  if (stride < 1 || nframes <= stride) return OFDIS_ERR_INVALID_ARGUMENT;
+  return run_interp_call(c, frames, nframes - stride, stride, nullptr, width, height, p, t, nt, use_occ != 0, alpha,
+                         beta, out_dtype, out, valid, occ_fw, occ_bw, stream);
+}
+
+int ofdis_run_sequence_interp_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int stride, int width,
+                                      int height, const ofdis_params *p, const float *t, int nt, int use_occ,
+                                      float alpha, float beta, int out_dtype, void *out, uint8_t *valid,
+                                      uint8_t *occ_fw, uint8_t *occ_bw) {
+  if (!c || !frames || !out || stride < 1 || nframes <= stride || width <= 0 || height <= 0 || !p ||
+      !img_dtype_ok(out_dtype) || (p->noc != 1 && p->noc != 3) || !interp_times_ok(t, nt))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  return run_interp_call_host(c, frames, (size_t)nframes * width * height * p->noc, nullptr, 0, nframes - stride, stride,
+                              width, height, p, t, nt, use_occ != 0, alpha, beta, out_dtype, out, valid, occ_fw, occ_bw);
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -2301,6 +2505,8 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   // the two level grids once per pair
   if (k == "interp") b = (double)width * height * (16.0 + 3.0 * noc + 1.0);
   if (k == "interp_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * (3.0 * noc + 1.0);
+  // the check on level grids: both grids once, the mask byte and the 4-byte error per pixel and direction
+  if (k == "fb_check_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + 2.0 * width * height * (1.0 + 4.0);
   *bytes = b;
   return OFDIS_OK;
 }

@@ -261,10 +261,24 @@ class Context:
                                    occ_fw_ptr or None, occ_bw_ptr or None, err_fw_ptr or None, err_bw_ptr or None,
                                    stream or None), "ofdis_fb_check")
 
-    def fb_check(self, flow_fw, flow_bw, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False):
+    def fb_check_level_ptr(self, gfw_ptr: int, gbw_ptr: int, view: FlowView, n: int, width: int, height: int,
+                           alpha: float, beta: float, occ_fw_ptr: int = 0, occ_bw_ptr: int = 0, err_fw_ptr: int = 0,
+                           err_bw_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_fb_check_level`` on raw device pointers (0 = that output is not wanted): the check of the fields
+        that the two float32 level grids described by `view` expand to."""
+        check(lib().ofdis_fb_check_level(self._h, gfw_ptr or None, gbw_ptr or None,
+                                         None if view is None else C.byref(view), n, width, height, alpha, beta,
+                                         occ_fw_ptr or None, occ_bw_ptr or None, err_fw_ptr or None, err_bw_ptr or None,
+                                         stream or None), "ofdis_fb_check_level")
+
+    def fb_check(self, flow_fw, flow_bw, alpha: float = 0.01, beta: float = 0.5, want_err: bool = False,
+                 grid: str = "full", p: Optional[Params] = None, size=None):
         """Forward-backward consistency of two flow fields: float32 CUDA tensors [n, h, w, 2] (or [h, w, 2]) ->
         (occ_fw, occ_bw[, err_fw, err_bw]); occ uint8 [n, h, w] with 0 consistent, 1 inconsistent, 2 the flow
-        leaves the frame; err float32 [n, h, w], the squared round-trip error (+inf where occ is 2)."""
+        leaves the frame; err float32 [n, h, w], the squared round-trip error (+inf where occ is 2).
+        grid="level": the two flows are the level grids of ``run(..., grid="level")`` with the parameters `p` for
+        frames of size = (width, height); the result is that of the full-resolution flows, bit for bit, and neither of
+        them is ever written."""
         import torch
         single = flow_fw.dim() == 3
         fw, bw = (flow_fw[None], flow_bw[None]) if single else (flow_fw, flow_bw)
@@ -272,6 +286,25 @@ class Context:
                 or bw.dtype != torch.float32 or not (fw.is_cuda and bw.is_cuda)):
             raise ValueError("expected two float32 CUDA tensors [n, h, w, 2] of one shape")
         fw, bw = fw.contiguous(), bw.contiguous()
+        if grid != "full":
+            fmt = out_format(fw.dtype, "nhwc", grid)
+            if p is None or size is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'fb_check: grid="level" needs the parameters the flows were '
+                                 "computed with and the frame size")
+            w, h = int(size[0]), int(size[1])
+            g = out_geometry(p, w, h, False, fw.dtype, "nhwc", grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+            n = fw.shape[0]
+            if tuple(fw.shape) != (n, view.gh, view.gw, 2):
+                raise ValueError(f"flows have shape {tuple(fw.shape)}, expected {(n, view.gh, view.gw, 2)}")
+            occ = [torch.empty((n, h, w), dtype=torch.uint8, device=fw.device) for _ in range(2)]
+            err = [torch.empty((n, h, w), dtype=torch.float32, device=fw.device) for _ in range(2 if want_err else 0)]
+            self.fb_check_level_ptr(fw.data_ptr(), bw.data_ptr(), view, n, w, h, alpha, beta, occ[0].data_ptr(),
+                                    occ[1].data_ptr(), err[0].data_ptr() if want_err else 0,
+                                    err[1].data_ptr() if want_err else 0,
+                                    torch.cuda.current_stream(fw.device).cuda_stream)
+            out = tuple(occ + err)
+            return tuple(t[0] for t in out) if single else out
         n, h, w = fw.shape[:3]
         occ = [torch.empty((n, h, w), dtype=torch.uint8, device=fw.device) for _ in range(2)]
         err = [torch.empty((n, h, w), dtype=torch.float32, device=fw.device) for _ in range(2 if want_err else 0)]
@@ -660,13 +693,30 @@ class Context:
                                         tt.ctypes.data, tt.size, out_dtype, out_ptr or None, valid_ptr or None,
                                         stream or None), "ofdis_run_interp_u8")
 
-    def run_interp(self, a, b, p: Params, t=0.5, out_dtype=None, want_valid: bool = False):
+    def run_interp_occ_ptr(self, a_ptr: int, b_ptr: int, n: int, width: int, height: int, p: Params, t, alpha: float,
+                           beta: float, out_dtype: int, out_ptr: int, valid_ptr: int = 0, occ_fw_ptr: int = 0,
+                           occ_bw_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_run_interp_occ_u8`` on raw device pointers, asynchronous on `stream` (0: that output is not
+        wanted)."""
+        tt = _times(t)
+        check(lib().ofdis_run_interp_occ_u8(self._h, a_ptr or None, b_ptr or None, n, width, height, C.byref(p),
+                                            tt.ctypes.data, tt.size, alpha, beta, out_dtype, out_ptr or None,
+                                            valid_ptr or None, occ_fw_ptr or None, occ_bw_ptr or None, stream or None),
+              "ofdis_run_interp_occ_u8")
+
+    def run_interp(self, a, b, p: Params, t=0.5, out_dtype=None, want_valid: bool = False, occ: bool = False,
+                   alpha: float = 0.01, beta: float = 0.5, want_occ: bool = False):
         """Frame interpolation in one call: both flows of each pair from one pyramid, then the frames at the times t.
         torch.uint8 CUDA tensors [n, h, w] or [n, h, w, 3] -> [n, nt, h, w] or [n, nt, h, w, 3] (torch.uint8, or
         torch.float32), with want_valid the tuple (pictures, valid [n, nt, h, w]).  Bit for bit
         ``interp(a, b, *run_bidir(a, b, p)[:2], t)``, but both flows stay on their level grids: no full-resolution
-        flow is written.  Takes no occlusion masks (compose ``run_bidir`` and ``interp`` for those)."""
+        flow is written.
+        occ: with the pair's occlusion masks at the thresholds alpha / beta, computed from the level grids -- bit for
+        bit ``interp(a, b, fw, bw, t, occ_fw, occ_bw)`` on the four outputs of ``run_bidir(a, b, p, alpha, beta)``;
+        want_occ appends (occ_fw, occ_bw), ``run_bidir``'s masks, to the result."""
         import torch
+        if want_occ and not occ:
+            raise ValueError("want_occ needs occ=True")
         gray = a.dim() == 3
         a4, b4 = (a.unsqueeze(-1), b.unsqueeze(-1)) if gray else (a, b)
         if (a4.dim() != 4 or a4.shape[-1] != p.noc or a4.dtype != torch.uint8 or a.shape != b.shape
@@ -681,15 +731,26 @@ class Context:
         shape = (n, tt.size, h, w) if gray else (n, tt.size, h, w, 3)
         out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=a.device)
         valid = torch.empty((n, tt.size, h, w), dtype=torch.uint8, device=a.device) if want_valid else None
+        if occ:
+            masks = [torch.empty((n, h, w), dtype=torch.uint8, device=a.device) for _ in range(2 if want_occ else 0)]
+            self.run_interp_occ_ptr(a4.data_ptr(), b4.data_ptr(), n, w, h, p, tt, alpha, beta,
+                                    IMG_F32 if f32 else IMG_U8, out.data_ptr(), valid.data_ptr() if want_valid else 0,
+                                    masks[0].data_ptr() if want_occ else 0, masks[1].data_ptr() if want_occ else 0,
+                                    torch.cuda.current_stream(a.device).cuda_stream)
+            res = [out] + ([valid] if want_valid else []) + masks
+            return tuple(res) if len(res) > 1 else out
         self.run_interp_ptr(a4.data_ptr(), b4.data_ptr(), n, w, h, p, tt, IMG_F32 if f32 else IMG_U8, out.data_ptr(),
                             valid.data_ptr() if want_valid else 0, torch.cuda.current_stream(a.device).cuda_stream)
         return (out, valid) if want_valid else out
 
     def run_interp_host(self, a: np.ndarray, b: np.ndarray, p: Params, t=0.5, out_dtype=np.uint8,
-                        want_valid: bool = False):
+                        want_valid: bool = False, occ: bool = False, alpha: float = 0.01, beta: float = 0.5,
+                        want_occ: bool = False):
         """run_interp on numpy u8 arrays; synchronous.  The inputs as for ``run_warp_host``; the pictures have the
         input's shape with an axis of nt times in front of the frame axes ([n, nt, h, w(, c)]; [nt, h, w(, c)] for a
-        single pair), valid is [n, nt, h, w] ([nt, h, w])."""
+        single pair), valid is [n, nt, h, w] ([nt, h, w]), the masks of want_occ [n, h, w] ([h, w])."""
+        if want_occ and not occ:
+            raise ValueError("want_occ needs occ=True")
         if np.dtype(out_dtype) not in (np.dtype(np.uint8), np.dtype(_f32)):
             raise OfdisError(ERR_INVALID_ARGUMENT, f"run_interp_host: out_dtype {out_dtype!r}")
         a = np.ascontiguousarray(a, np.uint8)
@@ -706,11 +767,94 @@ class Context:
         lead = () if single else (n,)
         out = np.empty(lead + (tt.size,) + a.shape[a.ndim - (3 if channels else 2):], out_dtype)
         valid = np.empty(lead + (tt.size, h, w), np.uint8) if want_valid else None
+        if occ:
+            masks = [np.empty(lead + (h, w), np.uint8) for _ in range(2 if want_occ else 0)]
+            check(lib().ofdis_run_interp_occ_u8_host(self._h, a.ctypes.data, b.ctypes.data, n, w, h, C.byref(p),
+                                                     tt.ctypes.data, tt.size, alpha, beta,
+                                                     IMG_F32 if np.dtype(out_dtype) == _f32 else IMG_U8, out.ctypes.data,
+                                                     valid.ctypes.data if want_valid else None,
+                                                     masks[0].ctypes.data if want_occ else None,
+                                                     masks[1].ctypes.data if want_occ else None),
+                  "ofdis_run_interp_occ_u8_host")
+            res = [out] + ([valid] if want_valid else []) + masks
+            return tuple(res) if len(res) > 1 else out
         check(lib().ofdis_run_interp_u8_host(self._h, a.ctypes.data, b.ctypes.data, n, w, h, C.byref(p), tt.ctypes.data,
                                              tt.size, IMG_F32 if np.dtype(out_dtype) == _f32 else IMG_U8,
                                              out.ctypes.data, valid.ctypes.data if want_valid else None),
               "ofdis_run_interp_u8_host")
         return (out, valid) if want_valid else out
+
+    def run_sequence_interp_ptr(self, frames_ptr: int, nframes: int, stride: int, width: int, height: int, p: Params,
+                                t, out_dtype: int, out_ptr: int, valid_ptr: int = 0, occ: bool = False,
+                                alpha: float = 0.01, beta: float = 0.5, occ_fw_ptr: int = 0, occ_bw_ptr: int = 0,
+                                stream: int = 0) -> None:
+        """``ofdis_run_sequence_interp_u8`` on raw device pointers, asynchronous on `stream`: frames u8
+        [nframes, h, w, noc], pair i = (frame i, frame i + stride), pictures for nframes - stride pairs (0: that
+        output is not wanted)."""
+        tt = _times(t)
+        check(lib().ofdis_run_sequence_interp_u8(self._h, frames_ptr or None, nframes, stride, width, height,
+                                                 C.byref(p), tt.ctypes.data, tt.size, int(bool(occ)), alpha, beta,
+                                                 out_dtype, out_ptr or None, valid_ptr or None, occ_fw_ptr or None,
+                                                 occ_bw_ptr or None, stream or None), "ofdis_run_sequence_interp_u8")
+
+    def run_sequence_interp(self, frames, p: Params, t=0.5, stride: int = 1, out_dtype=None, want_valid: bool = False,
+                            occ: bool = False, alpha: float = 0.01, beta: float = 0.5, want_occ: bool = False):
+        """The frames between the frames of a video: torch.uint8 CUDA tensor [T, h, w] or [T, h, w, 3] -> the pictures
+        of the T - stride pairs (frame i, frame i + stride), [T - stride, nt, h, w(, 3)] -- bit for bit
+        ``run_interp(frames[:-stride], frames[stride:], p, t, ...)`` with the same options, every frame's pyramid
+        built once.  The result is ordered as ``run_interp``'s: pictures[, valid][, occ_fw, occ_bw]."""
+        import torch
+        if want_occ and not occ:
+            raise ValueError("want_occ needs occ=True")
+        gray = frames.dim() == 3
+        f4 = frames.unsqueeze(-1) if gray else frames
+        if f4.dim() != 4 or f4.shape[-1] != p.noc or f4.dtype != torch.uint8 or not f4.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor with noc channels")
+        if out_dtype not in (None, torch.uint8, torch.float32):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_sequence_interp: out_dtype {out_dtype!r}")
+        f32 = out_dtype == torch.float32
+        tt = _times(t)
+        nf, h, w, _ = f4.shape
+        n = max(nf - stride, 0) if stride >= 1 else 0  # (the library refuses stride < 1 and nf <= stride)
+        f4 = f4.contiguous()
+        shape = (n, tt.size, h, w) if gray else (n, tt.size, h, w, 3)
+        out = torch.empty(shape, dtype=torch.float32 if f32 else torch.uint8, device=f4.device)
+        valid = torch.empty((n, tt.size, h, w), dtype=torch.uint8, device=f4.device) if want_valid else None
+        masks = [torch.empty((n, h, w), dtype=torch.uint8, device=f4.device) for _ in range(2 if want_occ else 0)]
+        self.run_sequence_interp_ptr(f4.data_ptr(), nf, stride, w, h, p, tt, IMG_F32 if f32 else IMG_U8,
+                                     out.data_ptr(), valid.data_ptr() if want_valid else 0, occ, alpha, beta,
+                                     masks[0].data_ptr() if want_occ else 0, masks[1].data_ptr() if want_occ else 0,
+                                     torch.cuda.current_stream(f4.device).cuda_stream)
+        res = [out] + ([valid] if want_valid else []) + masks
+        return tuple(res) if len(res) > 1 else out
+
+    def run_sequence_interp_host(self, frames: np.ndarray, p: Params, t=0.5, stride: int = 1, out_dtype=np.uint8,
+                                 want_valid: bool = False, occ: bool = False, alpha: float = 0.01, beta: float = 0.5,
+                                 want_occ: bool = False):
+        """run_sequence_interp on a numpy u8 array [T, h, w] or [T, h, w, noc]; synchronous."""
+        if want_occ and not occ:
+            raise ValueError("want_occ needs occ=True")
+        if np.dtype(out_dtype) not in (np.dtype(np.uint8), np.dtype(_f32)):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_sequence_interp_host: out_dtype {out_dtype!r}")
+        gray = frames.ndim == 3
+        f4 = np.ascontiguousarray(frames[..., None] if gray else frames, np.uint8)
+        if f4.ndim != 4 or f4.shape[-1] != p.noc:
+            raise ValueError("expected a uint8 array with noc channels")
+        nf, h, w = f4.shape[:3]
+        n = max(nf - stride, 0) if stride >= 1 else 0
+        tt = _times(t)
+        out = np.empty((n, tt.size, h, w) if gray else (n, tt.size, h, w, p.noc), out_dtype)
+        valid = np.empty((n, tt.size, h, w), np.uint8) if want_valid else None
+        masks = [np.empty((n, h, w), np.uint8) for _ in range(2 if want_occ else 0)]
+        check(lib().ofdis_run_sequence_interp_u8_host(self._h, f4.ctypes.data, nf, stride, w, h, C.byref(p),
+                                                      tt.ctypes.data, tt.size, int(bool(occ)), alpha, beta,
+                                                      IMG_F32 if np.dtype(out_dtype) == _f32 else IMG_U8,
+                                                      out.ctypes.data, valid.ctypes.data if want_valid else None,
+                                                      masks[0].ctypes.data if want_occ else None,
+                                                      masks[1].ctypes.data if want_occ else None),
+              "ofdis_run_sequence_interp_u8_host")
+        res = [out] + ([valid] if want_valid else []) + masks
+        return tuple(res) if len(res) > 1 else out
 
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
