@@ -501,6 +501,76 @@ int ofdis_run_sequence_interp_u8_host(ofdis_context *ctx, const uint8_t *frames,
                                       float alpha, float beta, int out_dtype, void *out, uint8_t *valid,
                                       uint8_t *occ_fw, uint8_t *occ_bw);
 
+/* ------------------------------------------------------------------ point tracking along a video
+ *
+ * Not in the reference.  Points followed through the frames of a video along its flows (long-range correspondence,
+ * dense trajectories, stabilisation), each with a flag that says where its track stopped being trustworthy.
+ *
+ * ofdis_track_points: npts points through a chain of m fields.  All pointers are device pointers.
+ * flow_fw: m fields back to back, field j the flow from frame j to frame j + 1 on frame j's pixel grid --
+ * ofdis_run_sequence_u8's flow_fw (stride 1), or its level-grid form.  flow_bw: NULL, or the m backward fields, field j
+ * the flow from frame j + 1 to frame j on frame j + 1's grid (ofdis_run_sequence_u8's flow_bw).  Both are described by
+ * the one `view`: a full view of any dtype and layout ofdis_warp_u8 takes, or a level view, float32 interleaved only, with
+ * the geometry of ofdis_out_geometry (any other valid enum value in a level view returns OFDIS_ERR_UNSUPPORTED, as in
+ * ofdis_fb_check_level).  points: float [npts][2], (x, y) in pixels.  start: NULL (= 0) or int32 [npts], the frame at
+ * which point k enters, clamped on the device to [0, m].
+ * Outputs, frame-major: tracks float [m + 1][npts][2], status u8 [m + 1][npts]; with flags & OFDIS_TRACK_LAST only entry
+ * m is written, tracks [npts][2] and status [npts].  Either may be NULL (both NULL: OFDIS_OK, nothing enqueued).
+ * Status codes: 0 tracked, every step so far consistent; 1 tracked, but some step so far failed the forward-backward
+ * check (sticky; the position keeps advancing); 2 left the frame (the position is frozen); 3 not started yet.
+ *
+ * Definition; all arithmetic float32 in this order, every operation rounded on its own (no fused multiply-add).
+ * S(G, px, py), field G at an in-frame position, is ofdis_fb_check's bilinear gather:
+ *   x0 = (int)floorf(px);  x1 = min(x0+1, W-1);  ax = px - (float)x0;  y0, y1, ay likewise
+ *   for each of the two components:  top = G[y0][x0] + ax*(G[y0][x1] - G[y0][x0])
+ *                                    bot = G[y1][x0] + ax*(G[y1][x1] - G[y1][x0])
+ *                                    S   = top + ay*(bot - top)
+ * G at integer pixels holds the values the view defines: a binary16 value converted exactly; for a level view the value
+ * the plain call's upsample computes, E(G) of ofdis_fb_check_level.
+ *   in(px, py) = px >= 0 && px <= (float)(W-1) && py >= 0 && py <= (float)(H-1)       (false for NaN)
+ * Point k, s0 = its clamped start:
+ *   entries j < s0 hold the query point itself, status 3;
+ *   entry s0 holds the point, status in(x, y) ? 0 : 2;
+ *   a step from entry j at (px, py) with status s in {0, 1}:
+ *     (fu, fv) = S(F_j, px, py);  qx = px + fu;  qy = py + fv;  entry j + 1 is (qx, qy)
+ *     if !in(qx, qy): its status is 2, and every later entry repeats entry j + 1 with status 2
+ *     else with flow_bw:  (bu, bv) = S(B_j, qx, qy);  du = fu + bu;  dv = fv + bv;  err = du*du + dv*dv
+ *                         mag = (fu*fu + fv*fv) + (bu*bu + bv*bv);  thr = alpha*mag + beta
+ *                         fail = !(err <= thr)   (a NaN fails);   the status of entry j + 1 is s | fail
+ *     else (no flow_bw): the status stays s
+ *   a point whose status at entry s0 is 2 is frozen there; a NaN coordinate is stored as the canonical quiet NaN 0x7fc00000.
+ * Consequences: positions never depend on flow_bw, alpha or beta; a point on the last row or column is inside; zero
+ * fields return the points unchanged.
+ * Refused before anything is enqueued (OFDIS_ERR_INVALID_ARGUMENT, the context stays usable): whatever ofdis_warp_u8
+ * refuses of a view and a size; NULL flow_fw or points; m < 1 or npts < 1; unknown flag bits; with flow_bw, the threshold
+ * rules of ofdis_fb_check.  Stream and ordering rules are those of ofdis_fb_check.  Index arithmetic over npts * (m + 1)
+ * is 64-bit. */
+enum { OFDIS_TRACK_LAST = 1 }; /* flags */
+int ofdis_track_points(ofdis_context *ctx, const void *flow_fw, const void *flow_bw, const ofdis_flow_view *view,
+                       int m, int width, int height, const float *points, const int32_t *start, int npts,
+                       float alpha, float beta, int flags, float *tracks, uint8_t *status, void *stream);
+
+/* The flows of a video and the tracks through them from one call: frames u8 [nframes][height][width][noc], m = nframes - 1,
+ * pair j = (frame j, frame j + 1).  By definition tracks / status == ofdis_track_points on the fields of
+ * ofdis_run_sequence_u8(frames, stride 1), bit for bit -- the forward and backward fields when use_fb, the forward ones
+ * alone otherwise (alpha, beta ignored) -- but every pair's flows leave the coarse-to-fine loop as float32 level grids,
+ * m * (1 or 2) * bytes_per_pair bytes in the buffer the context owns, and one launch marches every point through all
+ * of them after the last chunk: no upsample runs, no full-resolution field exists, and every frame's pyramid is built
+ * once (chunked calls overlap by one frame as documented for ofdis_run_sequence_u8).
+ * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED, and so does a call while a stage capture is set.  No
+ * initial flow.  verbosity is ignored.  Argument errors are those of ofdis_run_sequence_u8 (nframes < 2, ...) and of
+ * ofdis_track_points; stream, ordering, chunking, round-robin, graph and workspace rules are those of
+ * ofdis_run_batch_u8 (the graph is recorded anew when a point, start or output pointer, npts, flags, use_fb, alpha or
+ * beta changes; the point values are read at every replay). */
+int ofdis_run_sequence_track_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                const ofdis_params *p, const float *points, const int32_t *start, int npts,
+                                int use_fb, float alpha, float beta, int flags, float *tracks, uint8_t *status,
+                                void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_sequence_track_u8_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                     const ofdis_params *p, const float *points, const int32_t *start, int npts,
+                                     int use_fb, float alpha, float beta, int flags, float *tracks, uint8_t *status);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -618,7 +688,8 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * level-grid output that replaces it as "level_out"; the warp as "warp" with a full-resolution flow view and as
  * "warp_level" with a level-grid view; the left-right check as "lr_check" / "lr_check_err" like the forward-backward
  * one; the interpolation as "interp" with full-resolution flow views and as "interp_level" with level-grid views; the
- * forward-backward check on level grids as "fb_check_level", whatever it writes. */
+ * forward-backward check on level grids as "fb_check_level", whatever it writes; the point tracker as "track" with
+ * full-resolution flow views and as "track_level" with level-grid views. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the

@@ -33,6 +33,8 @@ OUT_FULL, OUT_LEVEL = 0, 1
 IMG_U8, IMG_F32 = 0, 1
 # OFDIS_INTERP_MAX_T: the most times one interpolation call takes
 INTERP_MAX_T = 16
+# OFDIS_TRACK_LAST: a tracking call writes only the last frame's entry
+TRACK_LAST = 1
 
 
 class OfdisError(RuntimeError):
@@ -164,6 +166,9 @@ def lib():
         "ofdis_run_interp_occ_u8_host": ([vp, vp, vp, i, i, i, P, vp, i, f, f, i, vp, vp, vp, vp], i),
         "ofdis_run_sequence_interp_u8": ([vp, vp, i, i, i, i, P, vp, i, i, f, f, i, vp, vp, vp, vp, vp], i),
         "ofdis_run_sequence_interp_u8_host": ([vp, vp, i, i, i, i, P, vp, i, i, f, f, i, vp, vp, vp, vp], i),
+        "ofdis_track_points": ([vp, vp, vp, V, i, i, i, vp, vp, i, f, f, i, vp, vp, vp], i),
+        "ofdis_run_sequence_track_u8": ([vp, vp, i, i, i, P, vp, vp, i, i, f, f, i, vp, vp, vp], i),
+        "ofdis_run_sequence_track_u8_host": ([vp, vp, i, i, i, P, vp, vp, i, i, f, f, i, vp, vp], i),
         "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),

@@ -238,7 +238,22 @@ struct InterpArgs {
   float t[kInterpMaxT];
 };
 
+// Points followed along a chain of m flow fields (include/ofdis.h: ofdis_track_points).  One view describes both chains.
+struct TrackArgs {
+  const void *fw, *bw;   // m fields back to back in the layouts of WarpArgs::flow; bw NULL: no consistency check
+  const float *points;   // [npts][2]
+  const int32_t *start;  // [npts] or NULL
+  float *tracks;         // [m + 1][npts][2] ([npts][2] with last), or NULL
+  uint8_t *status;       // [m + 1][npts] ([npts] with last), or NULL
+  int m, npts, W, H;     // W * H < 2^31
+  float alpha, beta;
+  int last;              // OFDIS_TRACK_LAST: only entry m is written
+  int f16, planar, level;
+  int gw, gh, log2c, offx, offy;  // as WarpArgs
+};
+
 void launch_warp(const WarpArgs &a, hipStream_t s);
+void launch_track(const TrackArgs &a, hipStream_t s);
 void launch_interp(const InterpArgs &a, hipStream_t s);
 void launch_fb_check(const FbArgs &a, hipStream_t s);
 void launch_fb_check_level(const FbLevelArgs &a, hipStream_t s);

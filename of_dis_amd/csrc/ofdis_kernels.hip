@@ -36,6 +36,8 @@
 //                field / along the level grid expanded on the fly (no reference code)
 //   interp       k_interp<OT, NOC, FT, PLANAR, PX>, k_interp_level<OT, NOC, PX>  the frames between two u8 frames from
 //                their two flows, full-resolution fields / level grids (no reference code)
+//   track        k_track<FT, PLANAR>, k_track_level  points followed along a chain of flow fields / level grids, one
+//                thread per point (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -6383,23 +6385,19 @@ __device__ __forceinline__ void fb_level_comp(const float (&c)[3][3], bool dx, b
   }
 }
 
-// fb_pixel with the other field expanded from its grid G ([gh][gw][2], the frame's): the same positions, taps and
-// arithmetic.  x1 - x0 and y1 - y0 are 0 or 1 and a pixel step moves the source position by at most half a cell
-// (cell >= 2), so xtap(x1).sx is xtap(x0).sx or the column after it and ytap(y1).r0 is ytap(y0).r0 or ytap(y0).r1: the
-// cells of the four expansions lie in three columns from xtap(x0).sx of the rows ytap(y0).r0, ytap(y0).r1 and
-// ytap(y1).r1 -- nine 8-byte loads serve their sixteen cell reads.  cell = 1: the four cells themselves.
-__device__ __forceinline__ unsigned fb_level_pixel(const float *__restrict__ G, const FbLevelArgs &a, double scale,
-                                                   int x, int y, float u, float v, float &err) {
-  const int W = a.W, H = a.H;
-  const float px = (float)x + u, py = (float)y + v;
-  const bool inside = px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);  // false for NaN
-  const float pxs = inside ? px : 0.f, pys = inside ? py : 0.f;  // (no branch around the gather, as fb_pixel)
-  const int x0 = (int)floorf(pxs), y0 = (int)floorf(pys);  // in [0, W - 1] x [0, H - 1]
-  const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
-  const float ax = pxs - (float)x0, ay = pys - (float)y0;
-  float bx[4], by[4];  // the other field at (x0, y0), (x1, y0), (x0, y1), (x1, y1): fb_pixel's b00, b01, b10, b11
-  if (a.log2c == 0) {
-    const long r0 = (long)(y0 + a.offy) * a.gw + a.offx, r1 = (long)(y1 + a.offy) * a.gw + a.offx;
+// The field a level grid G ([gh][gw][2], one frame's) expands to, at the four pixels (x0, y0), (x1, y0), (x0, y1),
+// (x1, y1) of a bilinear gather -- fb_pixel's b00, b01, b10, b11, both components.  x1 - x0 and y1 - y0 are 0 or 1 and a
+// pixel step moves the source position by at most half a cell (cell >= 2), so xtap(x1).sx is xtap(x0).sx or the column
+// after it and ytap(y1).r0 is ytap(y0).r0 or ytap(y0).r1: the cells of the four expansions lie in three columns from
+// xtap(x0).sx of the rows ytap(y0).r0, ytap(y0).r1 and ytap(y1).r1 -- nine 8-byte loads serve their sixteen cell reads.
+// cell = 1: the four cells themselves.  Shared by the check on level grids and the point tracker.
+struct LevelGeo {
+  int gw, gh, log2c, offx, offy;
+};
+__device__ __forceinline__ void level_taps(const float *__restrict__ G, const LevelGeo &g, double scale, int x0, int x1,
+                                           int y0, int y1, float (&bx)[4], float (&by)[4]) {
+  if (g.log2c == 0) {
+    const long r0 = (long)(y0 + g.offy) * g.gw + g.offx, r1 = (long)(y1 + g.offy) * g.gw + g.offx;
     const long o[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -6407,14 +6405,14 @@ __device__ __forceinline__ unsigned fb_level_pixel(const float *__restrict__ G, 
       bx[k] = c.x, by[k] = c.y;
     }
   } else {
-    const XTap xa = xtap(x0 + a.offx, scale, a.gw), xb = xtap(x1 + a.offx, scale, a.gw);
-    const YTap ya = ytap(y0 + a.offy, scale, a.gh), yb = ytap(y1 + a.offy, scale, a.gh);
+    const XTap xa = xtap(x0 + g.offx, scale, g.gw), xb = xtap(x1 + g.offx, scale, g.gw);
+    const YTap ya = ytap(y0 + g.offy, scale, g.gh), yb = ytap(y1 + g.offy, scale, g.gh);
     const int rows[3] = {ya.r0, ya.r1, yb.r1};
-    const int cols[3] = {xa.sx, min(xa.sx + 1, a.gw - 1), min(xa.sx + 2, a.gw - 1)};
+    const int cols[3] = {xa.sx, min(xa.sx + 1, g.gw - 1), min(xa.sx + 2, g.gw - 1)};
     float cu[3][3], cv[3][3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      const float *R = G + 2 * ((long)rows[j] * a.gw);
+      const float *R = G + 2 * ((long)rows[j] * g.gw);
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const float2_u c = *reinterpret_cast<const float2_u *>(R + 2 * cols[i]);
@@ -6425,6 +6423,21 @@ __device__ __forceinline__ unsigned fb_level_pixel(const float *__restrict__ G, 
     fb_level_comp(cu, dx, jb0, xa, xb, ya, yb, bx);
     fb_level_comp(cv, dx, jb0, xa, xb, ya, yb, by);
   }
+}
+
+// fb_pixel with the other field expanded from its grid G ([gh][gw][2], the frame's): the same positions, taps and
+// arithmetic (level_taps).
+__device__ __forceinline__ unsigned fb_level_pixel(const float *__restrict__ G, const FbLevelArgs &a, double scale,
+                                                   int x, int y, float u, float v, float &err) {
+  const int W = a.W, H = a.H;
+  const float px = (float)x + u, py = (float)y + v;
+  const bool inside = px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);  // false for NaN
+  const float pxs = inside ? px : 0.f, pys = inside ? py : 0.f;  // (no branch around the gather, as fb_pixel)
+  const int x0 = (int)floorf(pxs), y0 = (int)floorf(pys);  // in [0, W - 1] x [0, H - 1]
+  const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+  const float ax = pxs - (float)x0, ay = pys - (float)y0;
+  float bx[4], by[4];  // the other field at (x0, y0), (x1, y0), (x0, y1), (x1, y1): fb_pixel's b00, b01, b10, b11
+  level_taps(G, LevelGeo{a.gw, a.gh, a.log2c, a.offx, a.offy}, scale, x0, x1, y0, y1, bx, by);
   const float top0 = bx[0] + ax * (bx[1] - bx[0]), bot0 = bx[2] + ax * (bx[3] - bx[2]);
   const float top1 = by[0] + ax * (by[1] - by[0]), bot1 = by[2] + ax * (by[3] - by[2]);
   const float bu = top0 + ay * (bot0 - top0), bv = top1 + ay * (bot1 - top1);
@@ -6547,6 +6560,144 @@ void launch_fb_check_level(const FbLevelArgs &a0, hipStream_t s) {
     else if (occ) go(Int<1>{}, Int<0>{});
     else go(Int<0>{}, Int<1>{});
   }
+}
+
+// ------------------------------------------------------------------------------ point tracking
+// Points followed along a chain of m flow fields (include/ofdis.h: ofdis_track_points): one thread per point, the frame
+// loop inside the thread -- a step's position is the next step's gather address, so the chain is serial per point and
+// the parallelism is across points.  Every step gathers the forward field at the point's sub-pixel position with
+// fb_pixel's bilinear expression and, with a backward chain, the backward field at the new position for fb_pixel's
+// consistency test.  The outputs are frame-major, so the 64 points of a wave store 512 contiguous bytes of positions
+// and 64 of status per frame.
+//   k_track<FT, PLANAR>  the fields are full-resolution (float32 / binary16, interleaved / planar)
+//   k_track_level        the fields are float32 interleaved level grids: the four taps come from level_taps, the gather
+//                        of the check on level grids, so a tap carries the bits k_upsample would have written
+namespace {
+
+struct TrackTaps {
+  int x0, x1, y0, y1;
+  float ax, ay;
+};
+// The taps of an in-frame position.  (The integer min is a no-op below 2^24 columns / rows, where (float)(W - 1) is
+// exact; beyond, it keeps the taps inside the frame when (float)(W - 1) rounds up -- as warp_pixel.)
+__device__ __forceinline__ TrackTaps track_taps(int W, int H, float px, float py) {
+  TrackTaps t;
+  t.x0 = min((int)floorf(px), W - 1), t.y0 = min((int)floorf(py), H - 1);
+  t.x1 = t.x0 + 1 < W ? t.x0 + 1 : W - 1, t.y1 = t.y0 + 1 < H ? t.y0 + 1 : H - 1;
+  t.ax = px - (float)t.x0, t.ay = py - (float)t.y0;
+  return t;
+}
+// fb_pixel's blend of the four taps b00, b01, b10, b11, per component.
+__device__ __forceinline__ void track_blend(const float (&bx)[4], const float (&by)[4], float ax, float ay, float &u,
+                                            float &v) {
+  const float top0 = bx[0] + ax * (bx[1] - bx[0]), bot0 = bx[2] + ax * (bx[3] - bx[2]);
+  const float top1 = by[0] + ax * (by[1] - by[0]), bot1 = by[2] + ax * (by[3] - by[2]);
+  u = top0 + ay * (bot0 - top0), v = top1 + ay * (bot1 - top1);
+}
+
+// S(G, px, py) on a full-resolution field F (one frame), binary16 converted exactly.
+template <class FT, bool PLANAR>
+struct TrackFull {
+  int W, H;
+  long field;  // elements per field: 2 W H
+  __device__ __forceinline__ void operator()(const void *base, int j, float px, float py, float &u, float &v) const {
+    const FT *F = reinterpret_cast<const FT *>(base) + (long)j * field;
+    const TrackTaps t = track_taps(W, H, px, py);
+    const long r0 = (long)t.y0 * W, r1 = (long)t.y1 * W, plane = field >> 1;
+    const long o[4] = {r0 + t.x0, r0 + t.x1, r1 + t.x0, r1 + t.x1};
+    float bx[4], by[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if constexpr (PLANAR) {
+        bx[k] = (float)F[o[k]], by[k] = (float)F[plane + o[k]];
+      } else if constexpr (std::is_same<FT, float>::value) {
+        const float2_u c = *reinterpret_cast<const float2_u *>(F + 2 * o[k]);
+        bx[k] = c.x, by[k] = c.y;
+      } else {
+        bx[k] = (float)F[2 * o[k]], by[k] = (float)F[2 * o[k] + 1];
+      }
+    }
+    track_blend(bx, by, t.ax, t.ay, u, v);
+  }
+};
+
+// S(E(G), px, py) on a float32 interleaved level grid.
+struct TrackLevel {
+  int W, H;
+  long field;  // floats per grid: 2 gw gh
+  LevelGeo g;
+  double scale;
+  __device__ __forceinline__ void operator()(const void *base, int j, float px, float py, float &u, float &v) const {
+    const float *G = reinterpret_cast<const float *>(base) + (long)j * field;
+    const TrackTaps t = track_taps(W, H, px, py);
+    float bx[4], by[4];
+    level_taps(G, g, scale, t.x0, t.x1, t.y0, t.y1, bx, by);
+    track_blend(bx, by, t.ax, t.ay, u, v);
+  }
+};
+
+__device__ __forceinline__ float track_canon(float x) { return x != x ? __builtin_nanf("") : x; }  // (fb_pixel's NaN)
+
+// Point k through the m fields.  Status: 0 tracked, 1 tracked with a failed check behind it (sticky), 2 left the frame
+// (frozen), 3 not started.  last: only entry m is written.
+template <class S>
+__device__ __forceinline__ void track_point(const TrackArgs &a, const S &sample) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.npts) return;
+  const float wm = (float)(a.W - 1), hm = (float)(a.H - 1);
+  auto in = [&](float x, float y) { return x >= 0.f && x <= wm && y >= 0.f && y <= hm; };  // false for NaN
+  float px = a.points[2 * k], py = a.points[2 * k + 1];
+  int s0 = a.start ? a.start[k] : 0;
+  s0 = s0 < 0 ? 0 : (s0 > a.m ? a.m : s0);
+  auto store = [&](int j, unsigned st) {
+    if (a.last && j != a.m) return;
+    const long e = (a.last ? 0 : (long)j * a.npts) + k;  // 64-bit: npts * (m + 1) may pass 2^31
+    if (a.tracks) *reinterpret_cast<float2_u *>(a.tracks + 2 * e) = float2_u{track_canon(px), track_canon(py)};
+    if (a.status) a.status[e] = (uint8_t)st;
+  };
+  unsigned st = 3u;
+  for (int j = 0; j <= a.m; ++j) {
+    if (j == s0) st = in(px, py) ? 0u : 2u;
+    store(j, st);
+    if (j == a.m || st >= 2u) continue;  // the last entry; not started, or frozen: the next entry repeats this one
+    float fu, fv;
+    sample(a.fw, j, px, py, fu, fv);
+    const float qx = px + fu, qy = py + fv;
+    px = qx, py = qy;
+    if (!in(qx, qy)) {
+      st = 2u;
+    } else if (a.bw) {
+      float bu, bv;
+      sample(a.bw, j, qx, qy, bu, bv);
+      const float du = fu + bu, dv = fv + bv;
+      const float err = du * du + dv * dv;
+      const float mag = (fu * fu + fv * fv) + (bu * bu + bv * bv);
+      const float thr = a.alpha * mag + a.beta;
+      st |= err <= thr ? 0u : 1u;  // a NaN fails
+    }
+  }
+}
+
+template <class FT, bool PLANAR>
+__global__ __launch_bounds__(256) void k_track(TrackArgs a) {
+  track_point(a, TrackFull<FT, PLANAR>{a.W, a.H, 2 * (long)a.W * a.H});
+}
+
+__global__ __launch_bounds__(256) void k_track_level(TrackArgs a) {
+  track_point(a, TrackLevel{a.W, a.H, 2 * (long)a.gw * a.gh, LevelGeo{a.gw, a.gh, a.log2c, a.offx, a.offy},
+                            1.0 / (double)(1 << a.log2c)});
+}
+
+}  // namespace
+// ---- launch
+void launch_track(const TrackArgs &a, hipStream_t s) {
+  if (!a.tracks && !a.status) return;
+  const dim3 grid(ceil_div(a.npts, 256));
+  if (a.level) k_track_level<<<grid, 256, 0, s>>>(a);
+  else if (a.f16 && a.planar) k_track<_Float16, true><<<grid, 256, 0, s>>>(a);
+  else if (a.f16) k_track<_Float16, false><<<grid, 256, 0, s>>>(a);
+  else if (a.planar) k_track<float, true><<<grid, 256, 0, s>>>(a);
+  else k_track<float, false><<<grid, 256, 0, s>>>(a);
 }
 
 // Code-object warm-up: HIP loads a translation unit's code object on the first launch of any of its kernels, which

@@ -39,7 +39,9 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     // the interpolation with full-resolution flow views / with level-grid views
                                     "interp", "interp_level",
                                     // the forward-backward check on two level grids
-                                    "fb_check_level"};
+                                    "fb_check_level",
+                                    // the point tracker on full-resolution fields / on level grids
+                                    "track", "track_level"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -119,6 +121,9 @@ struct ofdis_context {
     const void *warp_out = nullptr, *warp_valid = nullptr, *warp_buf = nullptr;
     float warp_scale = 0.f;
     int warp = 0, warp_f32 = 0;
+    // ofdis_run_sequence_track_u8 (warp = 3; warp_buf the level grids, bidir / alpha / beta its use_fb and thresholds)
+    const void *trk_points = nullptr, *trk_start = nullptr, *trk_tracks = nullptr, *trk_status = nullptr;
+    int trk_npts = 0, trk_flags = 0;
     int n = 0, w = 0, h = 0;
     ofdis_params p{};
   } gkey;
@@ -2318,6 +2323,253 @@ int ofdis_run_sequence_interp_u8_host(ofdis_context *c, const uint8_t *frames, i
     return OFDIS_ERR_INVALID_ARGUMENT;
   return run_interp_call_host(c, frames, (size_t)nframes * width * height * p->noc, nullptr, 0, nframes - stride, stride,
                               width, height, p, t, nt, use_occ != 0, alpha, beta, out_dtype, out, valid, occ_fw, occ_bw);
+}
+
+// ------------------------------------------------------------------ point tracking (include/ofdis.h)
+
+namespace {
+// The points and outputs of a tracking call (ofdis_track_points, ofdis_run_sequence_track_u8).
+struct TrackIo {
+  const float *points = nullptr;
+  const int32_t *start = nullptr;
+  int npts = 0, flags = 0;
+  bool use_fb = false;
+  float alpha = 0.f, beta = 0.f;
+  float *tracks = nullptr;
+  uint8_t *status = nullptr;
+};
+
+// What every tracking call checks of its points, flags, thresholds and frame size.
+bool track_io_ok(const TrackIo &io, int width, int height) {
+  return io.points && io.npts >= 1 && !(io.flags & ~OFDIS_TRACK_LAST) && width > 0 && height > 0 &&
+         (long)width * height <= 0x7fffffffL && (!io.use_fb || fb_thresholds_ok(io.alpha, io.beta));
+}
+
+// The points through m fields of view v (timer "track_level" for a level-grid view, else "track").
+int run_track(ofdis_context *c, const void *fw, const void *bw, const ofdis_flow_view &v, int m, int width, int height,
+              const TrackIo &io, hipStream_t s) {
+  TrackArgs ta{};
+  ta.fw = fw;
+  ta.bw = bw;
+  ta.points = io.points;
+  ta.start = io.start;
+  ta.tracks = io.tracks;
+  ta.status = io.status;
+  ta.m = m;
+  ta.npts = io.npts;
+  ta.W = width;
+  ta.H = height;
+  ta.alpha = io.alpha;
+  ta.beta = io.beta;
+  ta.last = (io.flags & OFDIS_TRACK_LAST) != 0;
+  ta.f16 = v.dtype == OFDIS_OUT_F16;
+  ta.planar = v.layout == OFDIS_OUT_PLANAR;
+  ta.level = v.grid == OFDIS_OUT_LEVEL;
+  if (ta.level) {
+    ta.gw = v.gw;
+    ta.gh = v.gh;
+    ta.offx = v.off_x;
+    ta.offy = v.off_y;
+    while ((1 << ta.log2c) < v.cell) ++ta.log2c;
+  }
+  timed(c, ta.level ? 26 : 25, s, [&] { launch_track(ta, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// One chunk of ofdis_run_sequence_track_u8 (P a sequence plan of stride 1, bidirectional when the backward grids are
+// wanted): the pipeline of run_chunk, then the finest level's flows x 2^sc_l as float32 interleaved level grids into the
+// chunk's share of the context's buffer (grid_bw NULL: the forward grids alone).  No upsample runs.
+int run_chunk_track(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *frames,
+                    void *grid_fw, void *grid_bw, hipStream_t s) {
+  int rc = run_pyramid(c, ws, P, frames, nullptr, s);
+  if (rc) return rc;
+  if ((rc = run_levels(c, ws, P, p, s, nullptr, nullptr))) return rc;
+  for (int dir = 0; dir < (grid_bw ? 2 : 1); ++dir) {
+    LevelOutArgs lo{};
+    lo.flow = (const float *)(ws + (dir ? P.off_flow_bw[0] : P.off_flow[0]));
+    lo.out = dir ? grid_bw : grid_fw;
+    lo.n = P.n;
+    lo.nop = P.nop;
+    lo.wl = P.lv[0].w;
+    lo.hl = P.lv[0].h;
+    lo.log2s = p->sc_l;
+    timed(c, 17, s, [&] { launch_level_out(lo, s); });
+    if (hipGetLastError() != hipSuccess) return OFDIS_ERR_DEVICE;
+  }
+  return OFDIS_OK;
+}
+
+// The call's issue in run_batch's two kinds -- the whole video on stream s, or chunks round-robin over the lanes (fork
+// from s, join into s) -- and after the join the one track launch on s over all grids.  grids: the context's buffer,
+// the m forward grids and then the m backward ones.
+int issue_track(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *frames,
+                char *grids, const TrackIo &io) {
+  char *grids_bw = io.use_fb ? grids + (size_t)cp.n * cp.out_pair : nullptr;
+  if (cp.kind == CallPlan::kSingle) {
+    int rc = run_chunk_track(c, c->ws, cp.whole, p, frames, grids, grids_bw, s);
+    if (rc) return rc;
+  } else {
+    const int k = cp.lanes;
+    HIP_OK(hipEventRecord(c->entry, s));
+    for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
+    const size_t in_frame = (size_t)cp.width * cp.height * p->noc;
+    for (int ch = 0; ch < cp.nchunks; ++ch) {
+      const size_t f0 = (size_t)ch * cp.chunk;
+      auto &L = c->lanes[ch % k];
+      int rc = run_chunk_track(c, L.ws, cp.parts[ch], p, frames + f0 * in_frame, grids + f0 * cp.out_pair,
+                               grids_bw ? grids_bw + f0 * cp.out_pair : nullptr, L.s);
+      if (rc) return rc;
+    }
+    for (int i = 0; i < k; ++i) {
+      HIP_OK(hipEventRecord(c->lanes[i].done, c->lanes[i].s));
+      HIP_OK(hipStreamWaitEvent(s, c->lanes[i].done, 0));
+    }
+  }
+  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
+  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P1.lv[0].w, P1.lv[0].h, 1 << p->sc_l, P1.padl, P1.padt};
+  return run_track(c, grids, grids_bw, v, cp.n, cp.width, cp.height, io, s);
+}
+
+// ofdis_run_sequence_track_u8 on stream s (no stage capture is set): the sequence plan of stride 1, the m or 2 m level
+// grids in the context's buffer, and run_batch's chunk, lane and graph rules.
+int run_batch_track(ofdis_context *c, hipStream_t s, const uint8_t *frames, int m, int width, int height,
+                    const ofdis_params *p, const TrackIo &io) {
+  CallPlan cp;
+  int rc = prepare(c, p, m, width, height, false, false, cp, io.use_fb ? 1 : 0, 1);
+  if (rc) return rc;
+  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
+  cp.out_pair = (size_t)P1.lv[0].w * P1.lv[0].h * P1.nop * 4;  // a pair's float32 level grid
+  if ((rc = ensure_warp_buf(c, (io.use_fb ? 2 : 1) * (size_t)m * cp.out_pair))) return rc;  // (drops the graph before it grows)
+  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
+  if (!graph || c->timing) return issue_track(c, cp, s, p, frames, c->warp_buf, io);
+  ofdis_context::GraphKey key;
+  std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
+  key.a = frames; key.out = c->warp_buf; key.ws = c->ws;
+  key.n = m; key.w = width; key.h = height; key.p = *p;
+  key.out_level = 1; key.seq = 1; key.stride = 1;
+  key.warp = 3; key.warp_buf = c->warp_buf;
+  key.trk_points = io.points; key.trk_start = io.start; key.trk_tracks = io.tracks; key.trk_status = io.status;
+  key.trk_npts = io.npts; key.trk_flags = io.flags;
+  if (io.use_fb) {
+    key.bidir = 1; key.alpha = io.alpha; key.beta = io.beta;
+  }
+  if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0) {
+    if ((rc = drop_graph(c))) return rc;
+    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    rc = issue_track(c, cp, c->stream, p, frames, c->warp_buf, io);
+    hipGraph_t graph = nullptr;
+    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
+    if (rc) {
+      if (graph) hipGraphDestroy(graph);
+      return rc;
+    }
+    if (ce != hipSuccess || !graph) return OFDIS_ERR_DEVICE;
+    const hipError_t ie = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    if (ie != hipSuccess) {
+      c->gexec = nullptr;
+      return OFDIS_ERR_DEVICE;
+    }
+    std::memcpy(&c->gkey, &key, sizeof(key));
+  }
+  HIP_OK(hipGraphLaunch(c->gexec, s));
+  return OFDIS_OK;
+}
+}  // namespace
+
+int ofdis_track_points(ofdis_context *c, const void *flow_fw, const void *flow_bw, const ofdis_flow_view *v, int m,
+                       int width, int height, const float *points, const int32_t *start, int npts, float alpha,
+                       float beta, int flags, float *tracks, uint8_t *status, void *stream) {
+  TrackIo io;
+  io.points = points;
+  io.start = start;
+  io.npts = npts;
+  io.flags = flags;
+  io.use_fb = flow_bw != nullptr;
+  io.alpha = alpha;
+  io.beta = beta;
+  io.tracks = tracks;
+  io.status = status;
+  if (!c || !flow_fw || !v || m < 1 || !track_io_ok(io, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->grid == OFDIS_OUT_LEVEL && (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED))
+    return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_fb_check_level)
+  if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  if (!tracks && !status) return OFDIS_OK;
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
+  if (rc) return rc;
+  rc = run_track(c, flow_fw, flow_bw, *v, m, width, height, io, s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_sequence_track_u8(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                const ofdis_params *p, const float *points, const int32_t *start, int npts, int use_fb,
+                                float alpha, float beta, int flags, float *tracks, uint8_t *status, void *stream) {
+  TrackIo io;
+  io.points = points;
+  io.start = start;
+  io.npts = npts;
+  io.flags = flags;
+  io.use_fb = use_fb != 0;
+  io.alpha = alpha;
+  io.beta = beta;
+  io.tracks = tracks;
+  io.status = status;
+  if (!c || !frames || !p || nframes < 2 || !track_io_ok(io, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
+  if (!tracks && !status) return OFDIS_OK;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch_track(c, s, frames, nframes - 1, width, height, p, io);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_sequence_track_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                     const ofdis_params *p, const float *points, const int32_t *start, int npts,
+                                     int use_fb, float alpha, float beta, int flags, float *tracks, uint8_t *status) {
+  if (!c || !frames || !p || nframes < 2 || width <= 0 || height <= 0 || !points || npts < 1 ||
+      (flags & ~OFDIS_TRACK_LAST) || (p->noc != 1 && p->noc != 3))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t in = (size_t)nframes * width * height * p->noc, np = (size_t)npts;
+  const size_t entries = (flags & OFDIS_TRACK_LAST) ? np : np * (size_t)nframes;
+  // one device block: the frames, the points, the starts, the tracks, the status (each at a multiple of 256 bytes)
+  const size_t off_pts = align_up(in), off_start = off_pts + align_up(np * 8), off_tr = off_start + align_up(np * 4);
+  const size_t off_st = off_tr + align_up(entries * 8);
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_st + align_up(entries)));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  if (step(hipMemcpyAsync(d, frames, in, hipMemcpyHostToDevice, c->stream)) &&
+      step(hipMemcpyAsync(d + off_pts, points, np * 8, hipMemcpyHostToDevice, c->stream)) &&
+      (!start || step(hipMemcpyAsync(d + off_start, start, np * 4, hipMemcpyHostToDevice, c->stream)))) {
+    rc = ofdis_run_sequence_track_u8(c, (const uint8_t *)d, nframes, width, height, p, (const float *)(d + off_pts),
+                                     start ? (const int32_t *)(d + off_start) : nullptr, npts, use_fb, alpha, beta, flags,
+                                     tracks ? (float *)(d + off_tr) : nullptr, status ? (uint8_t *)(d + off_st) : nullptr,
+                                     c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      if (tracks) step(hipMemcpy(tracks, d + off_tr, entries * 8, hipMemcpyDeviceToHost));
+      if (status) step(hipMemcpy(status, d + off_st, entries, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
 }
 
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,

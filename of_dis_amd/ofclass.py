@@ -14,8 +14,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, IMG_F32, IMG_U8, MODE_DE, MODE_OF, FlowView, OfdisError,
-                   OutFormat, Params, check, lib, out_format)
+from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, IMG_F32, IMG_U8, MODE_DE, MODE_OF, TRACK_LAST, FlowView,
+                   OfdisError, OutFormat, Params, check, lib, out_format)
 
 _f32 = np.float32
 
@@ -856,6 +856,121 @@ class Context:
         res = [out] + ([valid] if want_valid else []) + masks
         return tuple(res) if len(res) > 1 else out
 
+    def track_points_ptr(self, fw_ptr: int, bw_ptr: int, view: FlowView, m: int, width: int, height: int,
+                         points_ptr: int, npts: int, start_ptr: int = 0, alpha: float = 0.01, beta: float = 0.5,
+                         flags: int = 0, tracks_ptr: int = 0, status_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_track_points`` on raw device pointers (0: no backward chain / no start array / that output is not
+        wanted); flags 0 or TRACK_LAST."""
+        check(lib().ofdis_track_points(self._h, fw_ptr or None, bw_ptr or None, None if view is None else C.byref(view),
+                                       m, width, height, points_ptr or None, start_ptr or None, npts, alpha, beta, flags,
+                                       tracks_ptr or None, status_ptr or None, stream or None), "ofdis_track_points")
+
+    def track_points(self, flow_fw, points, flow_bw=None, start=None, alpha: float = 0.01, beta: float = 0.5,
+                     layout: str = "nhwc", grid: str = "full", p: Optional[Params] = None, size=None,
+                     last_only: bool = False):
+        """Points followed along a chain of flow fields (the definition is in ofdis.h).  flow_fw: the m forward fields
+        of a video, field j from frame j to frame j + 1 -- ``run_sequence``'s flow in any format, described as for
+        ``warp`` (dtype from the tensor, layout, grid; grid "level" takes float32 "nhwc" grids and needs the parameters
+        `p` and size = (width, height)).  flow_bw: the m backward fields in the same format, or None (no consistency
+        check).  points: float32 CUDA tensor [N, 2], (x, y) in pixels; start: None or int32 CUDA tensor [N], the frame
+        at which each point enters.  Returns (tracks float32 [m + 1, N, 2], status uint8 [m + 1, N]) -- status 0 tracked,
+        1 tracked past a failed forward-backward check, 2 left the frame (frozen), 3 not started -- or with last_only
+        the last entry alone, [N, 2] and [N]."""
+        import torch
+        if not (flow_fw.is_cuda and points.is_cuda) or points.dim() != 2 or points.shape[1] != 2 or points.dtype != torch.float32:
+            raise ValueError("expected a CUDA flow tensor and a float32 CUDA tensor of points [N, 2]")
+        if flow_fw.dim() != 4:
+            raise ValueError("expected the m fields of a chain as one tensor of four dimensions")
+        fmt = out_format(flow_fw.dtype, layout, grid)
+        m = flow_fw.shape[0]
+        if grid == "level":
+            if p is None or size is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'track_points: grid="level" needs the parameters the flows were '
+                                 "computed with and the frame size")
+            w, h = int(size[0]), int(size[1])
+            g = out_geometry(p, w, h, False, flow_fw.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        else:
+            h, w = (flow_fw.shape[2], flow_fw.shape[3]) if fmt.layout else (flow_fw.shape[1], flow_fw.shape[2])
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        want = (m, 2, view.gh, view.gw) if fmt.layout else (m, view.gh, view.gw, 2)
+        if tuple(flow_fw.shape) != want:
+            raise ValueError(f"flow_fw has shape {tuple(flow_fw.shape)}, expected {want}")
+        if flow_bw is not None and (tuple(flow_bw.shape) != want or flow_bw.dtype != flow_fw.dtype or not flow_bw.is_cuda):
+            raise ValueError(f"flow_bw must be a CUDA tensor of flow_fw's dtype and shape {want}")
+        n = points.shape[0]
+        if start is not None and (tuple(start.shape) != (n,) or start.dtype != torch.int32 or not start.is_cuda):
+            raise ValueError(f"start must be an int32 CUDA tensor [{n}]")
+        flow_fw, points = flow_fw.contiguous(), points.contiguous()
+        flow_bw = flow_bw.contiguous() if flow_bw is not None else None
+        start = start.contiguous() if start is not None else None
+        tracks = torch.empty((n, 2) if last_only else (m + 1, n, 2), dtype=torch.float32, device=points.device)
+        status = torch.empty((n,) if last_only else (m + 1, n), dtype=torch.uint8, device=points.device)
+        self.track_points_ptr(flow_fw.data_ptr(), flow_bw.data_ptr() if flow_bw is not None else 0, view, m, w, h,
+                              points.data_ptr(), n, start.data_ptr() if start is not None else 0, alpha, beta,
+                              TRACK_LAST if last_only else 0, tracks.data_ptr(), status.data_ptr(),
+                              torch.cuda.current_stream(points.device).cuda_stream)
+        return tracks, status
+
+    def run_sequence_track_ptr(self, frames_ptr: int, nframes: int, width: int, height: int, p: Params, points_ptr: int,
+                               npts: int, start_ptr: int = 0, fb: bool = True, alpha: float = 0.01, beta: float = 0.5,
+                               flags: int = 0, tracks_ptr: int = 0, status_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_run_sequence_track_u8`` on raw device pointers, asynchronous on `stream`: frames u8
+        [nframes, h, w, noc], the points through its nframes - 1 pairs (0: no start array / that output is not wanted)."""
+        check(lib().ofdis_run_sequence_track_u8(self._h, frames_ptr or None, nframes, width, height, C.byref(p),
+                                                points_ptr or None, start_ptr or None, npts, int(bool(fb)), alpha, beta,
+                                                flags, tracks_ptr or None, status_ptr or None, stream or None),
+              "ofdis_run_sequence_track_u8")
+
+    def run_sequence_track(self, frames, p: Params, points, start=None, fb: bool = True, alpha: float = 0.01,
+                           beta: float = 0.5, last_only: bool = False):
+        """The flows of a video and the tracks through them in one call: torch.uint8 CUDA tensor [T, h, w] or
+        [T, h, w, noc] and float32 points [N, 2] -> (tracks [T, N, 2], status [T, N]) ([N, 2] and [N] with last_only),
+        bit for bit ``track_points`` on ``run_sequence(frames, p, bidir=True)``'s two flows (fb=False: on the forward
+        flow alone) -- but the flows stay on their level grids: no full-resolution flow is written."""
+        import torch
+        f4 = frames.unsqueeze(-1) if frames.dim() == 3 else frames
+        if f4.dim() != 4 or f4.shape[-1] != p.noc or f4.dtype != torch.uint8 or not f4.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor with noc channels")
+        if not points.is_cuda or points.dim() != 2 or points.shape[1] != 2 or points.dtype != torch.float32:
+            raise ValueError("expected a float32 CUDA tensor of points [N, 2]")
+        t, h, w, _ = f4.shape
+        n = points.shape[0]
+        if start is not None and (tuple(start.shape) != (n,) or start.dtype != torch.int32 or not start.is_cuda):
+            raise ValueError(f"start must be an int32 CUDA tensor [{n}]")
+        f4, points = f4.contiguous(), points.contiguous()
+        start = start.contiguous() if start is not None else None
+        tracks = torch.empty((n, 2) if last_only else (t, n, 2), dtype=torch.float32, device=f4.device)
+        status = torch.empty((n,) if last_only else (t, n), dtype=torch.uint8, device=f4.device)
+        self.run_sequence_track_ptr(f4.data_ptr(), t, w, h, p, points.data_ptr(), n,
+                                    start.data_ptr() if start is not None else 0, fb, alpha, beta,
+                                    TRACK_LAST if last_only else 0, tracks.data_ptr(), status.data_ptr(),
+                                    torch.cuda.current_stream(f4.device).cuda_stream)
+        return tracks, status
+
+    def run_sequence_track_host(self, frames: np.ndarray, p: Params, points: np.ndarray, start=None, fb: bool = True,
+                                alpha: float = 0.01, beta: float = 0.5, last_only: bool = False):
+        """run_sequence_track on numpy arrays (frames u8 [T, h, w] or [T, h, w, noc], points [N, 2]); synchronous."""
+        f4 = np.ascontiguousarray(frames[..., None] if frames.ndim == 3 else frames, np.uint8)
+        if f4.ndim != 4 or f4.shape[-1] != p.noc:
+            raise ValueError("expected a uint8 array with noc channels")
+        pts = np.ascontiguousarray(points, _f32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("expected points [N, 2]")
+        t, h, w = f4.shape[:3]
+        n = pts.shape[0]
+        st = None if start is None else np.ascontiguousarray(start, np.int32)
+        if st is not None and st.shape != (n,):
+            raise ValueError(f"start must have shape ({n},)")
+        tracks = np.empty((n, 2) if last_only else (t, n, 2), _f32)
+        status = np.empty((n,) if last_only else (t, n), np.uint8)
+        check(lib().ofdis_run_sequence_track_u8_host(self._h, f4.ctypes.data, t, w, h, C.byref(p),
+                                                     pts.ctypes.data if n else None,
+                                                     None if st is None else st.ctypes.data, n, int(bool(fb)), alpha, beta,
+                                                     TRACK_LAST if last_only else 0, tracks.ctypes.data,
+                                                     status.ctypes.data), "ofdis_run_sequence_track_u8_host")
+        return tracks, status
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
@@ -923,6 +1038,15 @@ def _times(t) -> np.ndarray:
     return np.ascontiguousarray(np.atleast_1d(np.asarray(t, _f32)).reshape(-1))
 
 
+def pixel_grid(width: int, height: int, step: int = 1) -> np.ndarray:
+    """The pixel centres (x, y) of every `step`-th column and row of a width x height frame, row-major: float32 [N, 2],
+    the points a dense tracking call starts from."""
+    if width < 1 or height < 1 or step < 1:
+        raise ValueError("pixel_grid needs a positive size and step")
+    xs, ys = np.arange(0, width, step, dtype=_f32), np.arange(0, height, step, dtype=_f32)
+    return np.ascontiguousarray(np.stack(np.meshgrid(xs, ys), axis=-1).reshape(-1, 2))
+
+
 def write_pnm(path: str, pixels: np.ndarray) -> None:
     """Binary PGM (u8 [h, w] or [h, w, 1]) / PPM (u8 [h, w, 3] in BGR order, written as RGB)."""
     pixels = np.ascontiguousarray(pixels, np.uint8)
@@ -949,5 +1073,5 @@ def algorithmic_bytes(p: Params, width: int, height: int, kernel: str) -> float:
 
 __all__ = ["OFClass", "Context", "Params", "oppoint", "params_from_strings", "validate", "synth_pair", "synth_shift_pair",
            "write_flo", "write_pfm", "write_pnm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
-           "max_frames_per_launch", "out_geometry",
+           "max_frames_per_launch", "out_geometry", "pixel_grid",
            "MODE_OF", "MODE_DE"]
