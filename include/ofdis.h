@@ -571,6 +571,71 @@ int ofdis_run_sequence_track_u8_host(ofdis_context *ctx, const uint8_t *frames, 
                                      const ofdis_params *p, const float *points, const int32_t *start, int npts,
                                      int use_fb, float alpha, float beta, int flags, float *tracks, uint8_t *status);
 
+/* ------------------------------------------------------------------ motion-compensated temporal denoising
+ *
+ * Not in the reference.  Every frame of a video averaged with its two neighbours pulled onto it along the flows, each
+ * neighbour weighted per pixel by how well it agrees with the frame: noise averages out where the motion is known, and a
+ * neighbour that disagrees (a wrong flow, an occlusion, a position outside its frame) drops out.
+ *
+ * ofdis_tfilter_u8: all pointers are device pointers.  frames: u8 [nframes][height][width][noc], T = nframes, m = T - 1.
+ * flow_fw / flow_bw: the m forward / backward fields of ofdis_run_sequence_u8 at stride 1 -- flow_fw field j on frame
+ * j's grid (frame j -> j + 1), flow_bw field j on frame j + 1's grid (frame j + 1 -> j).  Both are described by the one
+ * `view`, with ofdis_track_points's rules: a full view of any dtype and layout, or a level view, float32 interleaved
+ * only (any other valid enum value in a level view returns OFDIS_ERR_UNSUPPORTED).  occ_fw / occ_bw: NULL, or u8
+ * [m][height][width], ofdis_run_sequence_u8's occ_fw / occ_bw (mask j of occ_fw on frame j's grid, of occ_bw on frame
+ * j + 1's); either may be NULL alone.  out: u8 or float32 (out_dtype) [nframes][height][width][noc].  used: u8
+ * [nframes][height][width] or NULL.
+ *
+ * Definition, frame i, pixel (x, y); all arithmetic float32 in this order, every operation rounded on its own (no fused
+ * multiply-add), `/` the correctly rounded division:
+ *   inv = 1.0f / (sigma * (float)noc)             computed once on the host
+ *   C[ch] = (float)frames[i][y][x][ch]
+ *   acc[ch] = C[ch];  wsum = 1;  bits = 0
+ *   neighbours in this order:
+ *     k = 0 (previous, only if i > 0):     G = flow_bw[i-1], O = occ_bw[i-1], N = frames[i-1]
+ *     k = 1 (next,     only if i < T-1):   G = flow_fw[i],   O = occ_fw[i],   N = frames[i+1]
+ *     (u, v) = G at (x, y) as the view defines it (binary16 converted exactly; a level view expanded as ofdis_warp_u8
+ *              defines)
+ *     S[ch], inside = ofdis_warp_u8's val / inside for image N at (x + u, y + v), scale 1
+ *     ok = inside && (O == NULL || O[y][x] == 0)
+ *     d = |S[0] - C[0]|  (+ |S[1] - C[1]| + |S[2] - C[2]| in this order for noc = 3)
+ *     r = d * inv;   w = ok ? fmaxf(1 - r*r, 0) : 0
+ *     acc[ch] = acc[ch] + w * S[ch];   wsum = wsum + w;   if w > 0: bits |= 1 << k
+ *   val[ch] = acc[ch] / wsum
+ *   float32 output: val.    u8 output: (uint8_t)rintf(fminf(val, 255))          (round half to even)
+ *   used = bits            (0 the frame itself alone, 1 previous, 2 next, 3 both)
+ * Consequences: a NaN or infinite flow clears `inside`, so val is always finite; identical frames with zero flows
+ * return the frames exactly, in both output types; a neighbour that differs by sigma grey levels or more per channel
+ * (d >= sigma * noc) contributes nothing; the first and the last frame have one neighbour; the positions and weights of
+ * one neighbour never depend on the other.
+ * Refused before anything is enqueued (OFDIS_ERR_INVALID_ARGUMENT, the context stays usable): whatever ofdis_warp_u8
+ * refuses of a view, a size and noc; NULL frames, flow_fw, flow_bw, view or out; nframes < 2; sigma not finite or
+ * outside [1/1024, 65536]; an unknown out_dtype; out overlapping frames (neighbours are read after a frame is written).
+ * Stream and ordering rules are those of ofdis_fb_check. */
+int ofdis_tfilter_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, const void *flow_fw, const void *flow_bw,
+                     const ofdis_flow_view *view, int width, int height, int noc, float sigma,
+                     const uint8_t *occ_fw, const uint8_t *occ_bw, int out_dtype, void *out, uint8_t *used, void *stream);
+
+/* The flows of a video and its filtered frames from one call.  By definition out / used == ofdis_tfilter_u8 on the
+ * fields of ofdis_run_sequence_u8(frames, stride 1) in both directions, bit for bit; with use_occ the masks are that
+ * call's occ_fw / occ_bw at alpha, beta (alpha and beta are ignored otherwise).  Every pair's two flows leave the
+ * coarse-to-fine loop as float32 level grids, 2 * m * bytes_per_pair bytes in the buffer the context owns; with use_occ
+ * every chunk runs the check on its own grids (ofdis_fb_check_level) into 2 * m * width * height bytes of masks behind
+ * the grids in that buffer, sized per call; and one launch filters all frames from the grids after the last chunk: no upsample runs and no
+ * full-resolution flow exists.
+ * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED, and so does a call while a stage capture is set.  No
+ * initial flow.  verbosity is ignored.  Argument errors are those of ofdis_run_sequence_track_u8 (nframes < 2, ...) and
+ * of ofdis_tfilter_u8 (with use_occ, the threshold rules of ofdis_fb_check); stream, ordering, chunking, round-robin,
+ * graph and workspace rules are those of ofdis_run_batch_u8 (the graph is recorded anew when an output pointer,
+ * out_dtype, sigma, use_occ, alpha or beta changes; a graph of another call kind is never replayed). */
+int ofdis_run_sequence_tfilter_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                  const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
+                                  int out_dtype, void *out, uint8_t *used, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_sequence_tfilter_u8_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                       const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
+                                       int out_dtype, void *out, uint8_t *used);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -689,7 +754,8 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * "warp_level" with a level-grid view; the left-right check as "lr_check" / "lr_check_err" like the forward-backward
  * one; the interpolation as "interp" with full-resolution flow views and as "interp_level" with level-grid views; the
  * forward-backward check on level grids as "fb_check_level", whatever it writes; the point tracker as "track" with
- * full-resolution flow views and as "track_level" with level-grid views. */
+ * full-resolution flow views and as "track_level" with level-grid views; the temporal filter as "tfilter" with
+ * full-resolution flow views and as "tfilter_level" with level-grid views. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
@@ -702,7 +768,10 @@ const char *ofdis_kernel_names(void);
  * times): the two float32 flow views (16 bytes per pixel; the two level grids' 2 * gw * gh * 8 bytes per pair), 2 noc
  * bytes of image read, noc bytes of u8 output and the mask byte per pixel -- W * H * (16 + 3 noc + 1) and
  * 2 * gw * gh * 8 + W * H * (3 noc + 1).  "fb_check_level": both grids once, the mask byte and the 4-byte error per
- * pixel and direction -- 2 * gw * gh * 8 + 2 * W * H * (1 + 4). */
+ * pixel and direction -- 2 * gw * gh * 8 + 2 * W * H * (1 + 4).  "tfilter" / "tfilter_level": per output frame with
+ * both neighbours, in "interp"'s convention (masks not counted): the two float32 flow views (16 bytes per pixel; two
+ * level grids, 2 * gw * gh * 8 bytes), 3 noc bytes of image read (the frame and its two neighbours), noc bytes of u8
+ * output and the `used` byte per pixel -- W * H * (16 + 4 noc + 1) and 2 * gw * gh * 8 + W * H * (4 noc + 1). */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */

@@ -169,6 +169,9 @@ def lib():
         "ofdis_track_points": ([vp, vp, vp, V, i, i, i, vp, vp, i, f, f, i, vp, vp, vp], i),
         "ofdis_run_sequence_track_u8": ([vp, vp, i, i, i, P, vp, vp, i, i, f, f, i, vp, vp, vp], i),
         "ofdis_run_sequence_track_u8_host": ([vp, vp, i, i, i, P, vp, vp, i, i, f, f, i, vp, vp], i),
+        "ofdis_tfilter_u8": ([vp, vp, i, vp, vp, V, i, i, i, f, vp, vp, i, vp, vp, vp], i),
+        "ofdis_run_sequence_tfilter_u8": ([vp, vp, i, i, i, P, f, i, f, f, i, vp, vp, vp], i),
+        "ofdis_run_sequence_tfilter_u8_host": ([vp, vp, i, i, i, P, f, i, f, f, i, vp, vp], i),
         "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),

@@ -252,8 +252,26 @@ struct TrackArgs {
   int gw, gh, log2c, offx, offy;  // as WarpArgs
 };
 
+// Every frame of a video averaged with its two motion-compensated neighbours (include/ofdis.h: ofdis_tfilter_u8).
+// One view describes both chains of m = T - 1 fields.
+struct TfilterArgs {
+  const uint8_t *frames;         // [T][H][W][noc]
+  const void *fw, *bw;           // m fields back to back in the layouts of WarpArgs::flow
+  const uint8_t *occ_fw, *occ_bw;  // [m][H][W] occlusion masks, or NULL
+  void *out;                     // u8 or float [T][H][W][noc]
+  uint8_t *used;                 // [T][H][W] bit 0: the previous frame used, bit 1: the next; or NULL
+  int T, W, H, noc;              // W * H < 2^31
+  int f0, n;                     // the launch's output frames f0 .. f0 + n - 1 (set by launch_tfilter)
+  float inv;                     // 1 / (sigma noc)
+  int out_f32;
+  int f16, planar, level;
+  int gw, gh, log2c, offx, offy;  // as WarpArgs
+  int srows, scols;              // level form: rows and columns of a staged window (set by launch_tfilter)
+};
+
 void launch_warp(const WarpArgs &a, hipStream_t s);
 void launch_track(const TrackArgs &a, hipStream_t s);
+void launch_tfilter(const TfilterArgs &a, hipStream_t s);
 void launch_interp(const InterpArgs &a, hipStream_t s);
 void launch_fb_check(const FbArgs &a, hipStream_t s);
 void launch_fb_check_level(const FbLevelArgs &a, hipStream_t s);

@@ -38,6 +38,8 @@
 //                their two flows, full-resolution fields / level grids (no reference code)
 //   track        k_track<FT, PLANAR>, k_track_level  points followed along a chain of flow fields / level grids, one
 //                thread per point (no reference code)
+//   tfilter      k_tfilter<OT, NOC, FT, PLANAR, PX>, k_tfilter_level<OT, NOC, PX>  every frame of a video averaged with
+//                its two motion-compensated neighbours, full-resolution fields / level grids (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -6698,6 +6700,223 @@ void launch_track(const TrackArgs &a, hipStream_t s) {
   else if (a.f16) k_track<_Float16, false><<<grid, 256, 0, s>>>(a);
   else if (a.planar) k_track<float, true><<<grid, 256, 0, s>>>(a);
   else k_track<float, false><<<grid, 256, 0, s>>>(a);
+}
+
+// ------------------------------------------------------------------------------ temporal filter
+// Every frame of a video averaged with its two neighbours pulled onto it along the flows (include/ofdis.h:
+// ofdis_tfilter_u8): frame i reads frame i - 1 at (x, y) + backward flow i - 1 and frame i + 1 at (x, y) + forward flow i
+// through warp_pixel, weights each sample by its distance to the frame's own pixel, and divides the weighted sum by the
+// sum of weights.  Every operation and its order are fixed by the definition, as for the warp.  Grid z is the output
+// frame; the first and the last frame have one neighbour (a branch uniform over the block).
+//   k_tfilter<OT, NOC, FT, PLANAR, PX>  both chains are full-resolution fields of one format
+//   k_tfilter_level<OT, NOC, PX>        both chains are float32 interleaved level grids of one geometry, expanded as
+//                                       k_warp_level does
+namespace {
+
+// The PX pixels (x .. x + PX - 1, y) of frame i from their flows to the previous frame (pu, pv) and to the next one
+// (nu, nv): the centre pixels, the two samples and weights, the division, the store.
+template <class OT, int NOC, int PX>
+__device__ __forceinline__ void tfilter_emit(const TfilterArgs &a, int i, int x, int y, const float *pu, const float *pv,
+                                             const float *nu, const float *nv) {
+  const long plane = (long)a.W * a.H, op = (long)y * a.W + x, o = (long)i * plane + op;
+  const bool has[2] = {i > 0, i < a.T - 1};
+  // neighbour k: its frame and the mask on frame i's grid (backward mask i - 1 / forward mask i)
+  const uint8_t *N[2] = {a.frames + (long)(has[0] ? i - 1 : i) * plane * NOC,
+                         a.frames + (long)(has[1] ? i + 1 : i) * plane * NOC};
+  const uint8_t *O[2] = {a.occ_bw && has[0] ? a.occ_bw + (long)(i - 1) * plane + op : nullptr,
+                         a.occ_fw && has[1] ? a.occ_fw + (long)i * plane + op : nullptr};
+  // the thread's own bytes of the frame and the masks: PX = 4 as dwords (launch_tfilter's alignment conditions)
+  unsigned cb[PX * NOC], ob[2][PX] = {};
+  const uint8_t *Cp = a.frames + o * NOC;
+  if constexpr (PX == 4) {
+#pragma unroll
+    for (int j = 0; j < NOC; ++j) {
+      const unsigned w = *reinterpret_cast<const unsigned *>(Cp + 4 * j);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) cb[4 * j + b] = (w >> (8 * b)) & 0xffu;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (O[k]) {
+        const unsigned w = *reinterpret_cast<const unsigned *>(O[k]);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) ob[k][b] = (w >> (8 * b)) & 0xffu;
+      }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) cb[c] = Cp[c];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (O[k]) ob[k][0] = O[k][0];
+  }
+  float val[PX * NOC];
+  unsigned m = 0;
+#pragma unroll
+  for (int px = 0; px < PX; ++px) {
+    float C[NOC], acc[NOC], wsum = 1.f;
+    unsigned bits = 0;
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) C[c] = acc[c] = (float)cb[px * NOC + c];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (!has[k]) continue;
+      float S[NOC];
+      bool ok = warp_pixel<NOC>(N[k], a.W, a.H, x + px, y, k ? nu[px] : pu[px], k ? nv[px] : pv[px], 1.f, S) != 0;
+      if (ob[k][px]) ok = false;
+      float d = fabsf(S[0] - C[0]);
+#pragma unroll
+      for (int c = 1; c < NOC; ++c) d = d + fabsf(S[c] - C[c]);
+      const float r = d * a.inv;
+      const float w = ok ? fmaxf(1.f - r * r, 0.f) : 0.f;
+#pragma unroll
+      for (int c = 0; c < NOC; ++c) acc[c] = acc[c] + w * S[c];
+      wsum = wsum + w;
+      if (w > 0.f) bits |= 1u << k;
+    }
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) {
+      const float v = acc[c] / wsum;
+      val[px * NOC + c] = std::is_same<OT, float>::value ? v : fminf(v, 255.f);
+    }
+    m |= bits << (8 * px);
+  }
+  interp_store<OT, NOC, PX>(a.out, a.used, o, val, m);
+}
+
+// Thread layout, vector loads and alignment rules of k_warp; frame i = a.f0 + blockIdx.z.
+template <class OT, int NOC, class FT, bool PLANAR, int PX>
+__global__ __launch_bounds__(256) void k_tfilter(TfilterArgs a) {
+  const int i = a.f0 + (int)blockIdx.z;
+  const unsigned wq = (unsigned)a.W / PX;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= wq * (unsigned)a.H) return;
+  const int y = (int)(q / wq), x = (int)(q - (unsigned)y * wq) * PX;
+  const long plane = (long)a.W * a.H, o = (long)y * a.W + x;
+  float pu[PX] = {}, pv[PX] = {}, nu[PX] = {}, nv[PX] = {};
+  if (i > 0) warp_own_flow<FT, PLANAR, PX>(reinterpret_cast<const FT *>(a.bw) + (long)(i - 1) * 2 * plane, o, plane, pu, pv);
+  if (i < a.T - 1) warp_own_flow<FT, PLANAR, PX>(reinterpret_cast<const FT *>(a.fw) + (long)i * 2 * plane, o, plane, nu, nv);
+  tfilter_emit<OT, NOC, PX>(a, i, x, y, pu, pv, nu, nv);
+}
+
+// Block shape and dynamic-LDS staging of k_interp_level, for two grids of one geometry that belong to different pairs:
+// grid 0 is backward grid i - 1 (frame i -> i - 1), grid 1 forward grid i (frame i -> i + 1), both on frame i's pixel
+// grid.  An end frame stages and expands its one grid.
+extern __shared__ float tfilter_src[];  // [grid][row][comp][col]
+template <class OT, int NOC, int PX>
+__global__ __launch_bounds__(256) void k_tfilter_level(TfilterArgs a) {
+  constexpr int kCols = 256 * PX;
+  auto src = [&](int g, int row, int comp) { return tfilter_src + ((g * a.srows + row) * 2 + comp) * a.scols; };
+  const unsigned ncb = ((unsigned)a.W + kCols - 1) / kCols;
+  const int y0 = (int)(blockIdx.x / ncb) * kWarpRows, f = a.f0 + (int)blockIdx.z;
+  const long xb = (long)(blockIdx.x % ncb) * kCols;
+  const long xl = xb + threadIdx.x * PX;
+  const int x = (int)(xl < a.W ? xl : a.W);
+  const long gplane = (long)a.gw * a.gh;
+  const bool has[2] = {f > 0, f < a.T - 1};
+  // the frame's two grids, [gh][gw][2] float32 (an end frame's missing one is never read)
+  const float *G[2] = {reinterpret_cast<const float *>(a.bw) + (has[0] ? (long)(f - 1) * gplane * 2 : 0),
+                       reinterpret_cast<const float *>(a.fw) + (has[1] ? (long)f * gplane * 2 : 0)};
+  float pu[PX] = {}, pv[PX] = {}, nu[PX] = {}, nv[PX] = {};
+  if (a.log2c == 0) {
+    if (x >= a.W) return;
+    for (int r = 0; r < kWarpRows; ++r) {
+      const int y = y0 + r;
+      if (y >= a.H) break;
+#pragma unroll
+      for (int i = 0; i < PX; ++i) {
+        const long o = (long)(y + a.offy) * a.gw + (x + i + a.offx);
+        if (has[0]) pu[i] = G[0][2 * o], pv[i] = G[0][2 * o + 1];
+        if (has[1]) nu[i] = G[1][2 * o], nv[i] = G[1][2 * o + 1];
+      }
+      tfilter_emit<OT, NOC, PX>(a, f, x, y, pu, pv, nu, nv);
+    }
+    return;
+  }
+  const double scale = 1.0 / (double)(1 << a.log2c);
+  const int ylast = min(y0 + kWarpRows, a.H) - 1;
+  const int r_first = ytap(y0 + a.offy, scale, a.gh).r0;
+  const int nr = min(ytap(ylast + a.offy, scale, a.gh).r1 - r_first + 1, a.srows);
+  const long c_raw = (2 * (xb + a.offx) + 1 - (1 << a.log2c)) >> (a.log2c + 1);  // (as k_warp_level)
+  const int c_lo = (int)(c_raw > 0 ? c_raw : 0);
+  const int ncol = a.scols;  // ceil(kCols / cell) + 2 columns and a spare
+  const int g_lo = has[0] ? 0 : 1, ng = (has[1] ? 2 : 1) - g_lo;
+  for (int k = threadIdx.x; k < ng * nr * 2 * ncol; k += 256) {
+    const int col = k % ncol, rc = k / ncol;  // rc = ((grid - g_lo) * nr + row) * 2 + comp
+    const int g = g_lo + (rc >> 1) / nr, row = (rc >> 1) % nr;
+    const int sc = min(c_lo + col, a.gw - 1);
+    src(g, row, rc & 1)[col] = G[g][2 * ((long)(r_first + row) * a.gw + sc) + (rc & 1)];
+  }
+  __syncthreads();
+  if (x >= a.W) return;
+  XTap xt[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    xt[i] = xtap(x + i + a.offx, scale, a.gw);
+    xt[i].sx = min(max(xt[i].sx - c_lo, 0), ncol - 2);  // (inside the staged window by construction)
+  }
+  for (int r = 0; r < kWarpRows; ++r) {
+    const int y = y0 + r;
+    if (y >= a.H) break;
+    const YTap yt = ytap(y + a.offy, scale, a.gh);
+    const int j0 = min(max(yt.r0 - r_first, 0), nr - 1), j1 = min(max(yt.r1 - r_first, 0), nr - 1);
+    const float b0 = 1.f - yt.fy, b1 = yt.fy;
+    if (has[0]) {
+#pragma unroll
+      for (int i = 0; i < PX; ++i) {
+        pu[i] = up_px_s(src(0, j0, 0), src(0, j1, 0), xt[i], b0, b1);
+        pv[i] = up_px_s(src(0, j0, 1), src(0, j1, 1), xt[i], b0, b1);
+      }
+    }
+    if (has[1]) {
+#pragma unroll
+      for (int i = 0; i < PX; ++i) {
+        nu[i] = up_px_s(src(1, j0, 0), src(1, j1, 0), xt[i], b0, b1);
+        nv[i] = up_px_s(src(1, j0, 1), src(1, j1, 1), xt[i], b0, b1);
+      }
+    }
+    tfilter_emit<OT, NOC, PX>(a, f, x, y, pu, pv, nu, nv);
+  }
+}
+
+}  // namespace
+// ---- launch
+// Output frames go in grid z, 65535 per launch (a.f0: the slice's first frame; the pointers stay the call's, since
+// frame i reads frames and fields i - 1 .. i + 1).  The vector forms under launch_warp's conditions for both chains,
+// and with the frames and masks aligned to the thread's own dword of them.
+void launch_tfilter(const TfilterArgs &a0, hipStream_t s) {
+  const bool vec = a0.W % 4 == 0 && (a0.level || ((uintptr_t)a0.fw % 16 == 0 && (uintptr_t)a0.bw % 16 == 0)) &&
+                   (uintptr_t)a0.out % (a0.out_f32 ? 16 : 4) == 0 && (uintptr_t)a0.used % 4 == 0 &&
+                   (uintptr_t)a0.frames % 4 == 0 && (uintptr_t)a0.occ_fw % 4 == 0 && (uintptr_t)a0.occ_bw % 4 == 0;
+  const long frame = (long)a0.W * a0.H;
+  const int kSlice = 65535;  // grid z
+  for (int f0 = 0; f0 < a0.T; f0 += kSlice) {
+    TfilterArgs a = a0;
+    a.f0 = f0;
+    a.n = std::min(kSlice, a0.T - f0);
+    auto go = [&](auto OT, auto NOC, auto PX) {
+      using O = std::conditional_t<OT != 0, float, uint8_t>;
+      if (a.level) {
+        const dim3 grid(ceil_div(a.H, kWarpRows) * ceil_div(a.W, 256 * PX), 1, a.n);
+        // the staged windows, sized as launch_interp's
+        a.srows = a.log2c ? std::min((kWarpRows >> a.log2c) + 3, kWarpSrcRows) : 0;
+        a.scols = a.log2c ? std::min(((256 * PX) >> a.log2c) + 3, kWarpSrcCols) : 0;
+        const size_t lds = sizeof(float) * 2 * a.srows * 2 * a.scols;
+        k_tfilter_level<O, NOC, PX><<<grid, 256, lds, s>>>(a);
+        return;
+      }
+      const dim3 grid(ceil_div(frame / PX, 256), 1, a.n);
+      if (a.f16 && a.planar) k_tfilter<O, NOC, _Float16, true, PX><<<grid, 256, 0, s>>>(a);
+      else if (a.f16) k_tfilter<O, NOC, _Float16, false, PX><<<grid, 256, 0, s>>>(a);
+      else if (a.planar) k_tfilter<O, NOC, float, true, PX><<<grid, 256, 0, s>>>(a);
+      else k_tfilter<O, NOC, float, false, PX><<<grid, 256, 0, s>>>(a);
+    };
+    pick_noc(a.noc, [&](auto NOC) {
+      pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {
+        if (vec) go(OT, NOC, Int<4>{});
+        else go(OT, NOC, Int<1>{});
+      });
+    });
+  }
 }
 
 // Code-object warm-up: HIP loads a translation unit's code object on the first launch of any of its kernels, which

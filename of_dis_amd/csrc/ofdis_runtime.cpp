@@ -41,7 +41,9 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     // the forward-backward check on two level grids
                                     "fb_check_level",
                                     // the point tracker on full-resolution fields / on level grids
-                                    "track", "track_level"};
+                                    "track", "track_level",
+                                    // the temporal filter on full-resolution fields / on level grids
+                                    "tfilter", "tfilter_level"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -2572,6 +2574,252 @@ int ofdis_run_sequence_track_u8_host(ofdis_context *c, const uint8_t *frames, in
   return rc;
 }
 
+// ------------------------------------------------------------------ temporal filter (include/ofdis.h)
+
+namespace {
+// The parameters and outputs of a filtering call (ofdis_tfilter_u8, ofdis_run_sequence_tfilter_u8).
+struct TfilterIo {
+  float sigma = 0.f;
+  const uint8_t *occ_fw = nullptr, *occ_bw = nullptr;  // the primitive's masks
+  bool use_occ = false;                                // the fused call: masks from the chunks' grids at alpha, beta
+  float alpha = 0.f, beta = 0.f;
+  int f32 = 0;
+  void *out = nullptr;
+  uint8_t *used = nullptr;
+};
+
+// What every filtering call checks of its frames, sigma and outputs.
+bool tfilter_io_ok(const TfilterIo &io, const uint8_t *frames, int nframes, int width, int height, int noc, int out_dtype) {
+  if (!frames || !io.out || nframes < 2 || width <= 0 || height <= 0 || (noc != 1 && noc != 3) ||
+      (long)width * height > 0x7fffffffL || !img_dtype_ok(out_dtype))
+    return false;
+  if (!(io.sigma >= 1.0f / 1024.0f && io.sigma <= 65536.0f)) return false;  // (false for NaN)
+  // neighbours are read after a frame is written: the picture must not overlap the frames
+  const size_t in = (size_t)nframes * width * height * noc, outb = in * (out_dtype == OFDIS_IMG_F32 ? 4 : 1);
+  const uintptr_t f = (uintptr_t)frames, o = (uintptr_t)io.out;
+  return f + in <= o || o + outb <= f;
+}
+
+// The T frames filtered along the two chains of view v (timer "tfilter_level" for a level-grid view, else "tfilter").
+int run_tfilter(ofdis_context *c, const uint8_t *frames, int nframes, const void *fw, const void *bw,
+                const ofdis_flow_view &v, int width, int height, int noc, const TfilterIo &io, hipStream_t s) {
+  TfilterArgs ta{};
+  ta.frames = frames;
+  ta.fw = fw;
+  ta.bw = bw;
+  ta.occ_fw = io.occ_fw;
+  ta.occ_bw = io.occ_bw;
+  ta.out = io.out;
+  ta.used = io.used;
+  ta.T = nframes;
+  ta.W = width;
+  ta.H = height;
+  ta.noc = noc;
+  ta.inv = 1.0f / (io.sigma * (float)noc);
+  ta.out_f32 = io.f32;
+  ta.f16 = v.dtype == OFDIS_OUT_F16;
+  ta.planar = v.layout == OFDIS_OUT_PLANAR;
+  ta.level = v.grid == OFDIS_OUT_LEVEL;
+  if (ta.level) {
+    ta.gw = v.gw;
+    ta.gh = v.gh;
+    ta.offx = v.off_x;
+    ta.offy = v.off_y;
+    while ((1 << ta.log2c) < v.cell) ++ta.log2c;
+  }
+  timed(c, ta.level ? 28 : 27, s, [&] { launch_tfilter(ta, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// One chunk of ofdis_run_sequence_tfilter_u8 (P a bidirectional sequence plan of stride 1): run_chunk_track's pipeline
+// and level grids, then with masks the check on the chunk's own grids into its share of the call's masks.
+int run_chunk_tfilter(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *frames,
+                      void *grid_fw, void *grid_bw, uint8_t *occ_fw, uint8_t *occ_bw, const TfilterIo &io, hipStream_t s) {
+  int rc = run_chunk_track(c, ws, P, p, frames, grid_fw, grid_bw, s);
+  if (rc || !io.use_occ) return rc;
+  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
+  BidirOut bo;
+  bo.occ_fw = occ_fw;
+  bo.occ_bw = occ_bw;
+  bo.alpha = io.alpha;
+  bo.beta = io.beta;
+  return run_fb_check_level(c, (const float *)grid_fw, (const float *)grid_bw, v, P.n, P.W0, P.H0, bo, s);
+}
+
+// The call's issue in run_batch's two kinds, as issue_track, and after the join the one filter launch on s over all
+// frames.  grids: the context's buffer, the m forward grids and then the m backward ones; masks likewise (use_occ).
+int issue_tfilter(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *frames,
+                  char *grids, uint8_t *masks, const TfilterIo &io) {
+  const size_t px = (size_t)cp.width * cp.height;
+  char *grids_bw = grids + (size_t)cp.n * cp.out_pair;
+  uint8_t *masks_bw = masks ? masks + (size_t)cp.n * px : nullptr;
+  if (cp.kind == CallPlan::kSingle) {
+    int rc = run_chunk_tfilter(c, c->ws, cp.whole, p, frames, grids, grids_bw, masks, masks_bw, io, s);
+    if (rc) return rc;
+  } else {
+    const int k = cp.lanes;
+    HIP_OK(hipEventRecord(c->entry, s));
+    for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
+    const size_t in_frame = px * p->noc;
+    for (int ch = 0; ch < cp.nchunks; ++ch) {
+      const size_t f0 = (size_t)ch * cp.chunk;
+      auto &L = c->lanes[ch % k];
+      int rc = run_chunk_tfilter(c, L.ws, cp.parts[ch], p, frames + f0 * in_frame, grids + f0 * cp.out_pair,
+                                 grids_bw + f0 * cp.out_pair, masks ? masks + f0 * px : nullptr,
+                                 masks ? masks_bw + f0 * px : nullptr, io, L.s);
+      if (rc) return rc;
+    }
+    for (int i = 0; i < k; ++i) {
+      HIP_OK(hipEventRecord(c->lanes[i].done, c->lanes[i].s));
+      HIP_OK(hipStreamWaitEvent(s, c->lanes[i].done, 0));
+    }
+  }
+  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
+  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P1.lv[0].w, P1.lv[0].h, 1 << p->sc_l, P1.padl, P1.padt};
+  TfilterIo fio = io;
+  fio.occ_fw = masks;
+  fio.occ_bw = masks_bw;
+  return run_tfilter(c, frames, cp.n + 1, grids, grids_bw, v, cp.width, cp.height, p->noc, fio, s);
+}
+
+// ofdis_run_sequence_tfilter_u8 on stream s (no stage capture is set): run_batch_track's plan, the 2 m level grids in
+// the context's buffer, with masks the 2 m masks (u8 [2][m][H][W], the forward ones first) behind them in the same
+// buffer, and run_batch's chunk, lane and graph rules.  The graph key is run_batch_interp's in its own fields: warp = 4,
+// warp_out / warp_valid / warp_f32 the picture, `used` and dtype, warp_scale sigma, occ_fw the masks (NULL without
+// use_occ), alpha and beta with use_occ.
+int run_batch_tfilter(ofdis_context *c, hipStream_t s, const uint8_t *frames, int m, int width, int height,
+                      const ofdis_params *p, const TfilterIo &io) {
+  CallPlan cp;
+  int rc = prepare(c, p, m, width, height, false, false, cp, 1, 1);
+  if (rc) return rc;
+  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
+  cp.out_pair = (size_t)P1.lv[0].w * P1.lv[0].h * P1.nop * 4;  // a pair's float32 level grid
+  const size_t grid_bytes = align_up(2 * (size_t)m * cp.out_pair);
+  const size_t mask_bytes = io.use_occ ? 2 * (size_t)m * width * height : 0;  // sized per call
+  if ((rc = ensure_warp_buf(c, grid_bytes + mask_bytes))) return rc;  // (drops the graph before it grows)
+  uint8_t *masks = io.use_occ ? (uint8_t *)c->warp_buf + grid_bytes : nullptr;
+  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
+  if (!graph || c->timing) return issue_tfilter(c, cp, s, p, frames, c->warp_buf, masks, io);
+  ofdis_context::GraphKey key;
+  std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
+  key.a = frames; key.out = c->warp_buf; key.ws = c->ws;
+  key.n = m; key.w = width; key.h = height; key.p = *p;
+  key.out_level = 1; key.seq = 1; key.stride = 1; key.bidir = 1;
+  key.warp = 4; key.warp_buf = c->warp_buf;
+  key.warp_out = io.out; key.warp_valid = io.used; key.warp_f32 = io.f32; key.warp_scale = io.sigma;
+  key.occ_fw = masks;
+  if (io.use_occ) {
+    key.alpha = io.alpha; key.beta = io.beta;
+  }
+  if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0) {
+    if ((rc = drop_graph(c))) return rc;
+    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    rc = issue_tfilter(c, cp, c->stream, p, frames, c->warp_buf, masks, io);
+    hipGraph_t graph = nullptr;
+    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
+    if (rc) {
+      if (graph) hipGraphDestroy(graph);
+      return rc;
+    }
+    if (ce != hipSuccess || !graph) return OFDIS_ERR_DEVICE;
+    const hipError_t ie = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    if (ie != hipSuccess) {
+      c->gexec = nullptr;
+      return OFDIS_ERR_DEVICE;
+    }
+    std::memcpy(&c->gkey, &key, sizeof(key));
+  }
+  HIP_OK(hipGraphLaunch(c->gexec, s));
+  return OFDIS_OK;
+}
+}  // namespace
+
+int ofdis_tfilter_u8(ofdis_context *c, const uint8_t *frames, int nframes, const void *flow_fw, const void *flow_bw,
+                     const ofdis_flow_view *v, int width, int height, int noc, float sigma, const uint8_t *occ_fw,
+                     const uint8_t *occ_bw, int out_dtype, void *out, uint8_t *used, void *stream) {
+  TfilterIo io;
+  io.sigma = sigma;
+  io.occ_fw = occ_fw;
+  io.occ_bw = occ_bw;
+  io.f32 = out_dtype == OFDIS_IMG_F32;
+  io.out = out;
+  io.used = used;
+  if (!c || !flow_fw || !flow_bw || !v || !tfilter_io_ok(io, frames, nframes, width, height, noc, out_dtype))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->grid == OFDIS_OUT_LEVEL && (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED))
+    return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_track_points)
+  if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
+  if (rc) return rc;
+  rc = run_tfilter(c, frames, nframes, flow_fw, flow_bw, *v, width, height, noc, io, s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_sequence_tfilter_u8(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                  const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
+                                  int out_dtype, void *out, uint8_t *used, void *stream) {
+  TfilterIo io;
+  io.sigma = sigma;
+  io.use_occ = use_occ != 0;
+  io.alpha = alpha;
+  io.beta = beta;
+  io.f32 = out_dtype == OFDIS_IMG_F32;
+  io.out = out;
+  io.used = used;
+  if (!c || !p || !tfilter_io_ok(io, frames, nframes, width, height, p->noc, out_dtype) ||
+      (io.use_occ && !fb_thresholds_ok(alpha, beta)))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  if ((rc = call_begin(c, stream, s))) return rc;
+  rc = run_batch_tfilter(c, s, frames, nframes - 1, width, height, p, io);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+int ofdis_run_sequence_tfilter_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                       const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
+                                       int out_dtype, void *out, uint8_t *used) {
+  if (!c || !frames || !p || !out || nframes < 2 || width <= 0 || height <= 0 || !img_dtype_ok(out_dtype) ||
+      (p->noc != 1 && p->noc != 3))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)nframes * width * height, in = px * p->noc, outb = in * (out_dtype == OFDIS_IMG_F32 ? 4 : 1);
+  // one device block: the frames, the picture, the `used` bytes (each at a multiple of 256 bytes)
+  const size_t off_out = align_up(in), off_used = off_out + align_up(outb);
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_used + (used ? px : 0)));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  if (step(hipMemcpyAsync(d, frames, in, hipMemcpyHostToDevice, c->stream))) {
+    rc = ofdis_run_sequence_tfilter_u8(c, (const uint8_t *)d, nframes, width, height, p, sigma, use_occ, alpha, beta,
+                                       out_dtype, d + off_out, used ? (uint8_t *)(d + off_used) : nullptr, c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      step(hipMemcpy(out, d + off_out, outb, hipMemcpyDeviceToHost));
+      if (used) step(hipMemcpy(used, d + off_used, px, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -2759,6 +3007,11 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   if (k == "interp_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * (3.0 * noc + 1.0);
   // the check on level grids: both grids once, the mask byte and the 4-byte error per pixel and direction
   if (k == "fb_check_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + 2.0 * width * height * (1.0 + 4.0);
+  // the temporal filter per output frame with both neighbours, in the interpolation's convention (masks not counted):
+  // the frame and the taps of its two neighbours (3 noc), the u8 picture (noc) and the `used` byte per pixel, and the
+  // two float32 flow views -- 16 bytes per pixel, or the two level grids
+  if (k == "tfilter") b = (double)width * height * (16.0 + 4.0 * noc + 1.0);
+  if (k == "tfilter_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * (4.0 * noc + 1.0);
   *bytes = b;
   return OFDIS_OK;
 }

@@ -971,6 +971,120 @@ class Context:
                                                      status.ctypes.data), "ofdis_run_sequence_track_u8_host")
         return tracks, status
 
+    def tfilter_ptr(self, frames_ptr: int, nframes: int, fw_ptr: int, bw_ptr: int, view: FlowView, width: int,
+                    height: int, noc: int, sigma: float, out_dtype: int, out_ptr: int, used_ptr: int = 0,
+                    occ_fw_ptr: int = 0, occ_bw_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_tfilter_u8`` on raw device pointers (0: no `used` output / no occlusion mask); out_dtype IMG_U8 /
+        IMG_F32."""
+        check(lib().ofdis_tfilter_u8(self._h, frames_ptr or None, nframes, fw_ptr or None, bw_ptr or None,
+                                     None if view is None else C.byref(view), width, height, noc, sigma,
+                                     occ_fw_ptr or None, occ_bw_ptr or None, out_dtype, out_ptr or None,
+                                     used_ptr or None, stream or None), "ofdis_tfilter_u8")
+
+    def tfilter(self, frames, flow_fw, flow_bw, sigma: float, occ_fw=None, occ_bw=None, out_dtype=None,
+                want_used: bool = False, grid: str = "full", p: Optional[Params] = None, size=None,
+                layout: str = "nhwc"):
+        """Motion-compensated temporal denoising (the definition is in ofdis.h): every frame of a video averaged with
+        its two neighbours pulled onto it along the flows, each neighbour weighted per pixel by 1 - (d / (sigma noc))^2
+        of its distance d to the frame's own pixel.  frames: torch.uint8 CUDA tensor [T, h, w] or [T, h, w, 3];
+        flow_fw / flow_bw: the T - 1 forward / backward fields of ``run_sequence(frames, p, bidir=True)`` in one
+        format, described as for ``track_points`` (dtype from the tensors, layout, grid; grid "level" takes float32
+        "nhwc" grids and needs `p`; size defaults to the frames' (width, height)).  occ_fw / occ_bw: that call's masks
+        ([T - 1, h, w] uint8), either or both; a marked pixel does not take that neighbour.  Returns the filtered
+        frames in the frames' shape, torch.uint8 (the default) or torch.float32; with want_used the tuple (frames, used
+        uint8 [T, h, w]: bit 0 the previous frame contributed, bit 1 the next)."""
+        import torch
+        _tfilter_checks("tfilter", sigma, out_dtype, (None, torch.uint8, torch.float32))
+        gray = frames.dim() == 3
+        f4 = frames.unsqueeze(-1) if gray else frames
+        if (f4.dim() != 4 or f4.shape[-1] not in (1, 3) or f4.dtype != torch.uint8
+                or not (f4.is_cuda and flow_fw.is_cuda and flow_bw.is_cuda)):
+            raise ValueError("expected a uint8 CUDA tensor [T, h, w] or [T, h, w, 3] and two CUDA flow tensors")
+        t, h, w, noc = f4.shape
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "tfilter: a video needs two frames or more")
+        if size is not None and (int(size[0]), int(size[1])) != (w, h):
+            raise ValueError(f"size {tuple(size)} is not the frames' {(w, h)}")
+        if flow_fw.dtype != flow_bw.dtype:
+            raise ValueError("the two flows must have one dtype")
+        fmt = out_format(flow_fw.dtype, layout, grid)
+        view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        if grid == "level":
+            if p is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'tfilter: grid="level" needs the parameters the flows were computed with')
+            g = out_geometry(p, w, h, False, flow_fw.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        want = (t - 1, 2, view.gh, view.gw) if fmt.layout else (t - 1, view.gh, view.gw, 2)
+        if tuple(flow_fw.shape) != want or tuple(flow_bw.shape) != want:
+            raise ValueError(f"flows have shapes {tuple(flow_fw.shape)} and {tuple(flow_bw.shape)}, expected {want}")
+        for occ in (occ_fw, occ_bw):
+            if occ is not None and (tuple(occ.shape) != (t - 1, h, w) or occ.dtype != torch.uint8 or not occ.is_cuda):
+                raise ValueError(f"expected uint8 CUDA occlusion masks of shape {(t - 1, h, w)}")
+        f32 = out_dtype == torch.float32
+        f4, flow_fw, flow_bw = f4.contiguous(), flow_fw.contiguous(), flow_bw.contiguous()
+        occ_fw = occ_fw.contiguous() if occ_fw is not None else None
+        occ_bw = occ_bw.contiguous() if occ_bw is not None else None
+        out = torch.empty(frames.shape, dtype=torch.float32 if f32 else torch.uint8, device=f4.device)
+        used = torch.empty((t, h, w), dtype=torch.uint8, device=f4.device) if want_used else None
+        self.tfilter_ptr(f4.data_ptr(), t, flow_fw.data_ptr(), flow_bw.data_ptr(), view, w, h, noc, float(sigma),
+                         IMG_F32 if f32 else IMG_U8, out.data_ptr(), used.data_ptr() if want_used else 0,
+                         occ_fw.data_ptr() if occ_fw is not None else 0, occ_bw.data_ptr() if occ_bw is not None else 0,
+                         torch.cuda.current_stream(f4.device).cuda_stream)
+        return (out, used) if want_used else out
+
+    def run_sequence_tfilter_ptr(self, frames_ptr: int, nframes: int, width: int, height: int, p: Params, sigma: float,
+                                 out_dtype: int, out_ptr: int, used_ptr: int = 0, occ: bool = False,
+                                 alpha: float = 0.01, beta: float = 0.5, stream: int = 0) -> None:
+        """``ofdis_run_sequence_tfilter_u8`` on raw device pointers, asynchronous on `stream`: frames u8
+        [nframes, h, w, noc] -> the filtered frames (used_ptr 0: no `used` output); out_dtype IMG_U8 / IMG_F32."""
+        check(lib().ofdis_run_sequence_tfilter_u8(self._h, frames_ptr or None, nframes, width, height, C.byref(p), sigma,
+                                                  int(bool(occ)), alpha, beta, out_dtype, out_ptr or None,
+                                                  used_ptr or None, stream or None), "ofdis_run_sequence_tfilter_u8")
+
+    def run_sequence_tfilter(self, frames, p: Params, sigma: float, occ: bool = False, alpha: float = 0.01,
+                             beta: float = 0.5, out_dtype=None, want_used: bool = False):
+        """The flows of a video and its filtered frames in one call: torch.uint8 CUDA tensor [T, h, w] or
+        [T, h, w, noc] -> the filtered frames in that shape (torch.uint8, or torch.float32), with want_used the tuple
+        (frames, used [T, h, w]).  Bit for bit ``tfilter(frames, *run_sequence(frames, p, bidir=True)[:2], sigma)`` --
+        with occ, also given that call's two masks at alpha, beta -- but the flows stay on their level grids: no
+        full-resolution flow is written."""
+        import torch
+        _tfilter_checks("run_sequence_tfilter", sigma, out_dtype, (None, torch.uint8, torch.float32))
+        f4 = frames.unsqueeze(-1) if frames.dim() == 3 else frames
+        if f4.dim() != 4 or f4.shape[-1] != p.noc or f4.dtype != torch.uint8 or not f4.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor with noc channels")
+        t, h, w, _ = f4.shape
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_tfilter: a video needs two frames or more")
+        f32 = out_dtype == torch.float32
+        f4 = f4.contiguous()
+        out = torch.empty(frames.shape, dtype=torch.float32 if f32 else torch.uint8, device=f4.device)
+        used = torch.empty((t, h, w), dtype=torch.uint8, device=f4.device) if want_used else None
+        self.run_sequence_tfilter_ptr(f4.data_ptr(), t, w, h, p, float(sigma), IMG_F32 if f32 else IMG_U8,
+                                      out.data_ptr(), used.data_ptr() if want_used else 0, occ, alpha, beta,
+                                      torch.cuda.current_stream(f4.device).cuda_stream)
+        return (out, used) if want_used else out
+
+    def run_sequence_tfilter_host(self, frames: np.ndarray, p: Params, sigma: float, occ: bool = False,
+                                  alpha: float = 0.01, beta: float = 0.5, out_dtype=np.uint8, want_used: bool = False):
+        """run_sequence_tfilter on a numpy u8 array [T, h, w] or [T, h, w, noc]; synchronous."""
+        _tfilter_checks("run_sequence_tfilter_host", sigma, np.dtype(np.uint8 if out_dtype is None else out_dtype),
+                        (np.dtype(np.uint8), np.dtype(_f32)))
+        f4 = np.ascontiguousarray(frames[..., None] if frames.ndim == 3 else frames, np.uint8)
+        if f4.ndim != 4 or f4.shape[-1] != p.noc:
+            raise ValueError("expected a uint8 array with noc channels")
+        t, h, w = f4.shape[:3]
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_tfilter_host: a video needs two frames or more")
+        f32 = out_dtype is not None and np.dtype(out_dtype) == _f32
+        out = np.empty(frames.shape, _f32 if f32 else np.uint8)
+        used = np.empty((t, h, w), np.uint8) if want_used else None
+        check(lib().ofdis_run_sequence_tfilter_u8_host(self._h, f4.ctypes.data, t, w, h, C.byref(p), float(sigma),
+                                                       int(bool(occ)), alpha, beta, IMG_F32 if f32 else IMG_U8,
+                                                       out.ctypes.data, used.ctypes.data if want_used else None),
+              "ofdis_run_sequence_tfilter_u8_host")
+        return (out, used) if want_used else out
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
@@ -1036,6 +1150,15 @@ def _out_shape(p: Params, width: int, height: int, n: int, with_init: bool, fmt:
 def _times(t) -> np.ndarray:
     """The times of an interpolation call, a scalar or a sequence, as the float32 array the library copies."""
     return np.ascontiguousarray(np.atleast_1d(np.asarray(t, _f32)).reshape(-1))
+
+
+def _tfilter_checks(what: str, sigma, out_dtype, dtypes) -> None:
+    """What the filtering calls refuse of sigma and out_dtype, before any library call (ofdis_tfilter_u8's rules)."""
+    s = float(sigma)
+    if not (np.isfinite(s) and 1.0 / 1024.0 <= s <= 65536.0):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: sigma {sigma!r} is not in [1/1024, 65536]")
+    if out_dtype not in dtypes:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: out_dtype {out_dtype!r}")
 
 
 def pixel_grid(width: int, height: int, step: int = 1) -> np.ndarray:
