@@ -17,6 +17,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ofdis.h"
@@ -110,33 +111,56 @@ struct ofdis_context {
   int opt_sor_generic = 0;
   int opt_sor_pipe = 0;  // 1: force the single-wave-per-row-group register pipeline (A/B)
   int opt_graph = 1;           // replay the whole batch as one HIP graph (captured once per shape / pointers)
+  // What the one recorded graph bakes in.  The part every call has comes first (graph_key() fills all of it), then the
+  // payload of the call's family alone; the whole key is zeroed before it is filled and compared bytewise, padding
+  // included, and the family tag keeps the keys of two families apart whatever their payloads hold.
   struct GraphKey {
-    const void *a = nullptr, *b = nullptr, *out = nullptr, *ws = nullptr, *init = nullptr;
-    const void *flow_bw = nullptr, *occ_fw = nullptr, *occ_bw = nullptr, *err_fw = nullptr, *err_bw = nullptr;
-    float alpha = 0.f, beta = 0.f;  // the bidirectional call's extra outputs and thresholds
-    int bidir = 0;
-    int stereo = 0;           // ofdis_run_stereo_u8: a / b the left / right images, flow_bw .. beta its outputs
-    int seq = 0, stride = 0;  // ofdis_run_sequence_u8: `a` is one array of n + stride frames, b is NULL
-    int out_f16 = 0, out_planar = 0, out_level = 0;  // output format: a formatted call on a plain call's buffers
-                                                     // records anew, and the other way round
-    // ofdis_run_warp_u8: the picture, its mask and the level-grid buffer the flow passes through
-    const void *warp_out = nullptr, *warp_valid = nullptr, *warp_buf = nullptr;
-    float warp_scale = 0.f;
-    int warp = 0, warp_f32 = 0;
-    // ofdis_run_sequence_track_u8 (warp = 3; warp_buf the level grids, bidir / alpha / beta its use_fb and thresholds)
-    const void *trk_points = nullptr, *trk_start = nullptr, *trk_tracks = nullptr, *trk_status = nullptr;
-    int trk_npts = 0, trk_flags = 0;
-    int n = 0, w = 0, h = 0;
-    ofdis_params p{};
-  } gkey;
+    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter };
+    // run_batch: ofdis_run_batch_u8*, bidir, stereo, sequence, the formatted calls and ofdis_run_warp_u8
+    struct Batch {
+      const void *flow_bw, *occ_fw, *occ_bw, *err_fw, *err_bw;  // the bidirectional / stereo call's extra outputs,
+      float alpha, beta;                                        // its thresholds
+      int bidir, stereo;                                        // and which of the two it is
+      int out_f16, out_planar, out_level;  // output format: a formatted call on a plain call's buffers records anew
+      int warp, warp_f32;                  // ofdis_run_warp_u8: the picture's dtype, the picture, its mask, the scale
+      const void *warp_out, *warp_valid;   // (`out` and `buf` of the common part are then the level-grid buffer)
+      float warp_scale;
+    };
+    // run_batch_interp: the pictures, their dtype and mask, the times; with masks the mask arrays and thresholds
+    struct Interp {
+      const void *pictures, *valid, *occ_fw, *occ_bw;
+      int f32, use_occ;
+      float alpha, beta;
+      int nt;
+      float t[kInterpMaxT];
+    };
+    // run_batch_track: the points, their first frames and the outputs; with use_fb the thresholds
+    struct Track {
+      const void *points, *start, *tracks, *status;
+      int npts, flags, use_fb;
+      float alpha, beta;
+    };
+    // run_batch_tfilter: the picture, its dtype and `used` bytes, sigma; with masks their place in the context's
+    // buffer (else NULL) and the thresholds
+    struct Tfilter {
+      const void *picture, *used, *masks;
+      int f32;
+      float sigma, alpha, beta;
+    };
+    int family;
+    int n, w, h;
+    int seq, stride;  // a sequence call: `a` is one array of n + stride frames
+    const void *a, *b, *init, *out, *ws;
+    const void *buf;  // the context's level-grid buffer, in the calls whose flow passes through it
+    ofdis_params p;
+    union {
+      Batch batch;
+      Interp interp;
+      Track track;
+      Tfilter tfilter;
+    } u;
+  } gkey{};
   hipGraphExec_t gexec = nullptr;
-  // ofdis_run_interp_u8 records gkey with warp = 2 (warp_out / warp_valid / warp_buf / warp_f32 its picture, mask,
-  // buffer and dtype) and its times here; the graph of such a call is replayed only while both agree.  With masks
-  // (ofdis_run_interp_occ_u8) gkey.bidir, occ_fw, occ_bw, alpha and beta say so; the sequence form sets seq / stride
-  struct InterpKey {
-    int nt = 0;
-    float t[kInterpMaxT] = {};
-  } ikey;
   int opt_nt_store = 0;        // upsample output with non-temporal stores (A/B)
   // flow upsample: 0 per-output-row horizontal taps (k_upsample_rows), 1 / 2 once per staged source row (k_upsample_h,
   // 4 / 8 rows), 3 auto: 1 when the frame spans a whole 1024-column block and the call runs on two or more lanes or
@@ -199,6 +223,10 @@ struct ofdis_context {
   bool ws_pending = false;
   std::mutex mu;
 };
+
+static_assert(std::is_trivially_copyable<ofdis_context::GraphKey>::value && std::is_standard_layout<ofdis_context::GraphKey>::value,
+              "the graph key is zeroed, copied and compared as bytes");
+static_assert(sizeof(ofdis_context::GraphKey) <= 512, "the graph key is built on the stack by every replayed call");
 
 namespace {
 
@@ -879,7 +907,37 @@ void ofdis_context_destroy(ofdis_context *c) {
   delete c;
 }
 
+extern "C++" {  // (templates among them)
 namespace {
+
+// The level grid of a plan (ofdis_out_geometry's OFDIS_OUT_LEVEL): the finest level's plane x 2^sc_l.  One pair's
+// float32 grid in bytes, and the view that the warp, interpolation, check, tracker and filter read it through.
+size_t level_grid_bytes(const Plan &P) { return (size_t)P.lv[0].w * P.lv[0].h * P.nop * 4; }
+
+ofdis_flow_view level_view(const Plan &P) {
+  return ofdis_flow_view{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << P.sc_l, P.padl, P.padt};
+}
+
+// The forward flows of the chunk in workspace ws as level grids into grid_fw, and (grid_bw not NULL) the backward
+// flows into grid_bw; fmt: their dtype and layout, float32 interleaved by default (timer "level_out").
+int run_level_out(ofdis_context *c, char *ws, const Plan &P, void *grid_fw, void *grid_bw, hipStream_t s,
+                  const OutFmt &fmt = OutFmt()) {
+  for (int dir = 0; dir < (grid_bw ? 2 : 1); ++dir) {
+    LevelOutArgs lo{};
+    lo.flow = (const float *)(ws + (dir ? P.off_flow_bw[0] : P.off_flow[0]));
+    lo.out = dir ? grid_bw : grid_fw;
+    lo.n = P.n;
+    lo.nop = P.nop;
+    lo.wl = P.lv[0].w;
+    lo.hl = P.lv[0].h;
+    lo.log2s = P.sc_l;
+    lo.f16 = fmt.f16;
+    lo.planar = fmt.planar;
+    timed(c, 17, s, [&] { launch_level_out(lo, s); });
+    if (hipGetLastError() != hipSuccess) return OFDIS_ERR_DEVICE;
+  }
+  return OFDIS_OK;
+}
 
 // x 2^sc_l + INTER_LINEAR upsample + crop of the finest level's flow in workspace ws (run_dense.cpp:407-415).
 // A format other than the plain one (never with `backward`): the formatted store forms, or for the level grid no
@@ -887,20 +945,7 @@ namespace {
 // disp_r (a stereo plan): the mirrored pairs' half of the batch goes there, mirrored back and negated by the store.
 int run_upsample(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, void *flow_out, hipStream_t s,
                  bool backward = false, const OutFmt &fmt = OutFmt(), float *disp_r = nullptr) {
-  if (fmt.level) {
-    LevelOutArgs lo{};
-    lo.flow = (const float *)(ws + P.off_flow[0]);
-    lo.out = flow_out;
-    lo.n = P.n;
-    lo.nop = P.nop;
-    lo.wl = P.lv[0].w;
-    lo.hl = P.lv[0].h;
-    lo.log2s = p->sc_l;
-    lo.f16 = fmt.f16;
-    lo.planar = fmt.planar;
-    timed(c, 17, s, [&] { launch_level_out(lo, s); });
-    return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
-  }
+  if (fmt.level) return run_level_out(c, ws, P, flow_out, nullptr, s, fmt);
   UpArgs up{};
   up.flow = (const float *)(ws + (backward ? P.off_flow_bw[0] : P.off_flow[0]));
   up.out = (float *)flow_out;
@@ -1143,39 +1188,34 @@ int run_chunk(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, 
     return bd->checks() ? run_lr_check(c, (const float *)flow_out, disp_r, P.n / 2, P.W0, P.H0, *bd, s) : OFDIS_OK;
   }
   rc = run_upsample(c, ws, P, p, flow_out, s, false, fmt);
-  if (!rc && wo) {  // ofdis_run_warp_u8: flow_out is the chunk's float32 level grid (fmt), img_b warped by it
-    ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
-    return run_warp(c, img_b, flow_out, v, P.n, P.W0, P.H0, P.noc, *wo, s);
-  }
+  // ofdis_run_warp_u8: flow_out is the chunk's float32 level grid (fmt), img_b warped by it
+  if (!rc && wo) return run_warp(c, img_b, flow_out, level_view(P), P.n, P.W0, P.H0, P.noc, *wo, s);
   if (rc || !bd) return rc;  // (bd: the plain format, float32 fields)
   float *flow_bw = bd->flow_bw ? bd->flow_bw : (float *)(ws + P.off_up_bw);
   if ((rc = run_upsample(c, ws, P, p, flow_bw, s, true))) return rc;
   return bd->checks() ? run_fb_check(c, (const float *)flow_out, flow_bw, P.n, P.W0, P.H0, *bd, s) : OFDIS_OK;
 }
 
-// One chunk of ofdis_run_interp_u8 (P a bidirectional plan, no initial flow): the pipeline of run_chunk, then both
-// flows of the finest level x 2^sc_l as float32 interleaved level grids (grid_fw, grid_bw: the chunk's share of the
-// context's buffer) and the pictures from them.  No upsample runs.  io.use_occ: the check on the two grids in between,
-// its masks read by the interpolation.  A sequence plan: img_a is the chunk's first frame and the pyramid reads its
-// n + stride frames from there; img_b, frame b of the chunk's first pair, is read by the interpolation alone.
-int run_chunk_interp(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
-                     const uint8_t *img_b, void *grid_fw, void *grid_bw, const InterpOut &io, hipStream_t s) {
+// One chunk of a fused call that reads level grids (the interpolation, the tracker, the temporal filter; P without an
+// initial flow, bidirectional when grid_bw is given): the pipeline of run_chunk, then the finest level's flows x 2^sc_l
+// as float32 interleaved level grids into grid_fw and grid_bw, the chunk's share of the context's buffer (grid_bw NULL:
+// the forward grids alone).  No upsample runs.  A sequence plan reads its n + stride frames from img_a, and not img_b.
+int run_chunk_grids(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
+                    const uint8_t *img_b, void *grid_fw, void *grid_bw, hipStream_t s) {
   int rc = run_pyramid(c, ws, P, img_a, P.seq ? nullptr : img_b, s);
   if (rc) return rc;
   if ((rc = run_levels(c, ws, P, p, s, nullptr, nullptr))) return rc;
-  for (int dir = 0; dir < 2; ++dir) {
-    LevelOutArgs lo{};
-    lo.flow = (const float *)(ws + (dir ? P.off_flow_bw[0] : P.off_flow[0]));
-    lo.out = dir ? grid_bw : grid_fw;
-    lo.n = P.n;
-    lo.nop = P.nop;
-    lo.wl = P.lv[0].w;
-    lo.hl = P.lv[0].h;
-    lo.log2s = p->sc_l;
-    timed(c, 17, s, [&] { launch_level_out(lo, s); });
-    if (hipGetLastError() != hipSuccess) return OFDIS_ERR_DEVICE;
-  }
-  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
+  return run_level_out(c, ws, P, grid_fw, grid_bw, s);
+}
+
+// One chunk of ofdis_run_interp_u8: its two level grids and the pictures from them.  io.use_occ: the check on the two
+// grids in between, its masks read by the interpolation.  A sequence plan: img_a is the chunk's first frame; img_b,
+// frame b of the chunk's first pair, is read by the interpolation alone.
+int run_chunk_interp(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *img_a,
+                     const uint8_t *img_b, void *grid_fw, void *grid_bw, const InterpOut &io, hipStream_t s) {
+  int rc = run_chunk_grids(c, ws, P, p, img_a, img_b, grid_fw, grid_bw, s);
+  if (rc) return rc;
+  const ofdis_flow_view v = level_view(P);
   if (!io.use_occ) return run_interp(c, img_a, img_b, grid_fw, grid_bw, v, P.n, P.W0, P.H0, P.noc, io, s);
   const size_t px = (size_t)P.n * P.W0 * P.H0;
   BidirOut bo;
@@ -1239,6 +1279,9 @@ struct CallPlan {
   std::vector<Plan> parts;  // kRoundRobin: one plan per chunk
 };
 
+// The plan of the first chunk: the geometry (levels, padding, components) that every chunk of the call shares.
+const Plan &first_plan(const CallPlan &cp) { return cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0]; }
+
 int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int height, bool init, bool capturing,
             CallPlan &cp, int bidir = 0, int stride = 0, int stereo = 0) {
   cp.n = n;
@@ -1270,58 +1313,20 @@ int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int heigh
   return ensure_lanes(c, cp.lanes, cp.parts[0].total);
 }
 
-// Chunks round-robin over the lanes, each chunk's whole pipeline on one lane (fork from s, join into s).
-// A sequence call (img_b NULL): the chunk of m pairs from pair f0 reads frames [f0, f0 + m + stride) of the caller's
-// array, so neighbouring chunks rebuild the `stride` frames they share; the outputs are per pair as ever.
-int issue_round_robin(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p,
-                      const uint8_t *img_a, const uint8_t *img_b, const float *init, void *flow_out,
-                      const BidirOut *bd, const OutFmt &fmt, const WarpOut *wo) {
+// The chunks of a call, each through fn(f0, ws, P, stream) -- the chunk's first pair, workspace, plan and stream.
+// Single: the whole batch in the context's workspace on s.  Round robin: the chunks over the lanes, each chunk's whole
+// pipeline on one lane (fork from s, join into s; inside a capture the events are recorded into the graph).
+// A sequence call: the chunk of m pairs from pair f0 reads frames [f0, f0 + m + stride) of the caller's array, so
+// neighbouring chunks rebuild the `stride` frames they share; the outputs are per pair as ever.
+template <class Fn>
+int for_each_chunk(ofdis_context *c, const CallPlan &cp, hipStream_t s, Fn &&fn) {
+  if (cp.kind == CallPlan::kSingle) return fn((size_t)0, c->ws, cp.whole, s);
   const int k = cp.lanes;
   HIP_OK(hipEventRecord(c->entry, s));
   for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
-  const size_t in_frame = (size_t)cp.width * cp.height * p->noc;
-  const size_t out_frame = (size_t)cp.width * cp.height * cp.parts[0].nop;
   for (int ch = 0; ch < cp.nchunks; ++ch) {
-    const size_t f0 = (size_t)ch * cp.chunk;
     auto &L = c->lanes[ch % k];
-    const BidirOut part = bd ? bd->at(f0, (size_t)cp.width * cp.height) : BidirOut();
-    const WarpOut wpart = wo ? wo->at(f0, (size_t)cp.width * cp.height, p->noc) : WarpOut();
-    int rc = run_chunk(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b ? img_b + f0 * in_frame : nullptr,
-                       init ? init + f0 * out_frame : nullptr, (char *)flow_out + f0 * cp.out_pair,
-                       bd ? &part : nullptr, L.s, fmt, wo ? &wpart : nullptr);
-    if (rc) return rc;
-  }
-  for (int i = 0; i < k; ++i) {
-    HIP_OK(hipEventRecord(c->lanes[i].done, c->lanes[i].s));
-    HIP_OK(hipStreamWaitEvent(s, c->lanes[i].done, 0));
-  }
-  return OFDIS_OK;
-}
-
-int issue(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *img_a,
-          const uint8_t *img_b, const float *init, void *flow_out, const BidirOut *bd, const OutFmt &fmt,
-          const WarpOut *wo) {
-  switch (cp.kind) {
-    case CallPlan::kRoundRobin: return issue_round_robin(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt, wo);
-    default: return run_chunk(c, c->ws, cp.whole, p, img_a, img_b, init, flow_out, bd, s, fmt, wo);
-  }
-}
-
-// ofdis_run_interp_u8's issue, in the same two kinds: the whole batch on stream s, or chunks round-robin over the
-// lanes (fork from s, join into s).  grids: the context's buffer, the n forward grids and then the n backward ones.
-int issue_interp(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *img_a,
-                 const uint8_t *img_b, char *grids, const InterpOut &io) {
-  char *grids_bw = grids + (size_t)cp.n * cp.out_pair;
-  if (cp.kind == CallPlan::kSingle) return run_chunk_interp(c, c->ws, cp.whole, p, img_a, img_b, grids, grids_bw, io, s);
-  const int k = cp.lanes;
-  HIP_OK(hipEventRecord(c->entry, s));
-  for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
-  const size_t px = (size_t)cp.width * cp.height, in_frame = px * p->noc;
-  for (int ch = 0; ch < cp.nchunks; ++ch) {
-    const size_t f0 = (size_t)ch * cp.chunk;
-    auto &L = c->lanes[ch % k];
-    int rc = run_chunk_interp(c, L.ws, cp.parts[ch], p, img_a + f0 * in_frame, img_b + f0 * in_frame,
-                              grids + f0 * cp.out_pair, grids_bw + f0 * cp.out_pair, io.at(f0, px, p->noc), L.s);
+    const int rc = fn((size_t)ch * cp.chunk, L.ws, cp.parts[ch], L.s);
     if (rc) return rc;
   }
   for (int i = 0; i < k; ++i) {
@@ -1364,53 +1369,54 @@ int validate_call(const ofdis_params *p, int width, int height, bool init) {
   return tv_frame_cap(p, width, height) >= 1 ? OFDIS_OK : OFDIS_ERR_INVALID_ARGUMENT;
 }
 
-// The whole-batch device path on stream s (call ordering done by the caller).  stride > 0: img_a is a sequence of
-// n + stride frames and pair i is (frame i, frame i + stride); img_b is NULL.
-int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
-              int width, int height, const ofdis_params *p, void *flow_out, const BidirOut *bd = nullptr,
-              int stride = 0, const OutFmt &fmt = OutFmt(), const WarpOut *wo = nullptr) {
-  const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
-  CallPlan cp;
-  const int keep = bd ? (bd->flow_bw ? 1 : 2) : 0;  // 2: the second field stays in the workspace
-  const bool stereo = bd && bd->stereo;
-  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, stereo ? 0 : keep, stride, stereo ? keep : 0);
+// A device entry point's frame around body(s), after its arguments are checked: the context's lock, the refusal of a
+// set stage capture for the calls that cannot honour one, the device, the call's ordering on `stream` and the merged
+// status.  nothing_asked: the call has no output to write -- OFDIS_OK once it is known to be allowed.
+template <class Body>
+int device_call(ofdis_context *c, void *stream, bool refuse_capture, Body &&body, bool nothing_asked = false) {
+  std::lock_guard<std::mutex> lock(c->mu);
+  if (refuse_capture && (!c->cap_dis.empty() || !c->cap_tv.empty())) return OFDIS_ERR_UNSUPPORTED;
+  if (nothing_asked) return OFDIS_OK;
+  HIP_OK(hipSetDevice(c->device));
+  hipStream_t s;
+  int rc = call_begin(c, stream, s);
   if (rc) return rc;
-  {  // a chunk of m pairs from pair f0 writes the bytes [f0, f0 + m) * out_pair of flow_out
-    const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
-    const size_t cells = fmt.level ? (size_t)P1.lv[0].w * P1.lv[0].h : (size_t)width * height;
-    cp.out_pair = cells * P1.nop * (fmt.f16 ? 2 : 4);
-  }
-  if (wo) {  // ofdis_run_warp_u8 (flow_out NULL, fmt the float32 level grid): the flow goes through the context's buffer
-    if ((rc = ensure_warp_buf(c, (size_t)n * cp.out_pair))) return rc;
-    flow_out = c->warp_buf;
-  }
-  OFDIS_TRACE("run_batch: kind %d, %d chunks of %d, %d lanes", (int)cp.kind, cp.nchunks, cp.chunk, cp.lanes);
-  // graph 1: capture single-stream batches; graph 2: also the multi-lane (fork / join) issues
-  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
-  if (!graph || capturing || c->timing) return issue(c, cp, s, p, img_a, img_b, init, flow_out, bd, fmt, wo);
-  // ~80 dependent launches per chunk: record them once as a HIP graph (on the context's own stream -- the
-  // caller's may be the legacy NULL stream, which cannot capture) and replay it on the caller's stream while
-  // the pointers, sizes, parameters and options stay the same (set_option drops the graph).  Multi-lane
-  // issues fork from and join into the capturing stream through events recorded inside the capture.
-  ofdis_context::GraphKey key;
+  rc = body(s);
+  const int rc2 = call_end(c, stream, s);
+  return rc ? rc : rc2;
+}
+
+// A graph key with the common part filled: the family, the images (a sequence call: stride > 0, b NULL or the
+// interpolation's frame `stride`), the initial flow, where the flow goes, the workspace, the sizes and parameters, and
+// `buf`, the context's level-grid buffer when the call's flow passes through it.  The family's payload is all zero.
+using GraphKey = ofdis_context::GraphKey;
+GraphKey graph_key(GraphKey::Family family, const ofdis_context *c, const void *a, const void *b, const void *init,
+                   const void *out, const void *buf, int n, int width, int height, int stride, const ofdis_params *p) {
+  GraphKey key;
   std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
-  key.a = img_a; key.b = img_b; key.out = flow_out; key.ws = c->ws; key.init = init;
+  key.family = family;
+  key.a = a; key.b = b; key.init = init; key.out = out; key.ws = c->ws; key.buf = buf;
   key.n = n; key.w = width; key.h = height; key.p = *p;
   key.seq = stride > 0; key.stride = stride;  // a sequence call on a plain call's buffers records anew
-  key.out_f16 = fmt.f16; key.out_planar = fmt.planar; key.out_level = fmt.level;
-  if (bd) {  // a plain call after a bidirectional one on the same buffers records anew, and the other way round
-    key.bidir = !bd->stereo; key.stereo = bd->stereo; key.flow_bw = bd->flow_bw; key.occ_fw = bd->occ_fw; key.occ_bw = bd->occ_bw;
-    key.err_fw = bd->err_fw; key.err_bw = bd->err_bw; key.alpha = bd->alpha; key.beta = bd->beta;
-  }
-  if (wo) {  // (key.out is then the level-grid buffer)
-    key.warp = 1; key.warp_out = wo->out; key.warp_valid = wo->valid; key.warp_buf = c->warp_buf;
-    key.warp_scale = wo->scale; key.warp_f32 = wo->f32;
-  }
+  return key;
+}
+
+// issue(stream) enqueues the whole call.  Eagerly on s: with graph 0, for the multi-lane issues with graph 1 (graph 2
+// captures their fork and join too), under the kernel timers or a stage capture.  Else ~80 dependent launches per
+// chunk are recorded once as a HIP graph (on the context's own stream -- the caller's may be the legacy NULL stream,
+// which cannot capture) and replayed on the caller's stream while the key -- pointers, sizes, parameters, the family's
+// own values -- stays the same; set_option and every reallocation drop the graph.  One graph per context: a call with
+// another key records anew.
+template <class Issue>
+int replay_or_record(ofdis_context *c, hipStream_t s, const CallPlan &cp, const GraphKey &key, Issue &&issue) {
+  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
+  if (!graph || !c->cap_dis.empty() || !c->cap_tv.empty() || c->timing) return issue(s);
   if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0) {
-    if ((rc = drop_graph(c))) return rc;
+    int rc = drop_graph(c);
+    if (rc) return rc;
     OFDIS_TRACE("graph: capture (kind %d, %d chunks of %d)", (int)cp.kind, cp.nchunks, cp.chunk);
     HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = issue(c, cp, c->stream, p, img_a, img_b, init, flow_out, bd, fmt, wo);
+    rc = issue(c->stream);
     OFDIS_TRACE("graph: issued rc %d", rc);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
@@ -1434,8 +1440,50 @@ int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8
   return OFDIS_OK;
 }
 
+// The whole-batch device path on stream s (call ordering done by the caller).  stride > 0: img_a is a sequence of
+// n + stride frames and pair i is (frame i, frame i + stride); img_b is NULL.
+int run_batch(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
+              int width, int height, const ofdis_params *p, void *flow_out, const BidirOut *bd = nullptr,
+              int stride = 0, const OutFmt &fmt = OutFmt(), const WarpOut *wo = nullptr) {
+  const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
+  CallPlan cp;
+  const int keep = bd ? (bd->flow_bw ? 1 : 2) : 0;  // 2: the second field stays in the workspace
+  const bool stereo = bd && bd->stereo;
+  int rc = prepare(c, p, n, width, height, init != nullptr, capturing, cp, stereo ? 0 : keep, stride, stereo ? keep : 0);
+  if (rc) return rc;
+  const Plan &P1 = first_plan(cp);
+  const size_t px = (size_t)width * height, in_frame = px * p->noc, out_frame = px * P1.nop;
+  // a chunk of m pairs from pair f0 writes the bytes [f0, f0 + m) * out_pair of flow_out
+  cp.out_pair = (fmt.level ? level_grid_bytes(P1) : out_frame * 4) / (fmt.f16 ? 2 : 1);
+  if (wo) {  // ofdis_run_warp_u8 (flow_out NULL, fmt the float32 level grid): the flow goes through the context's buffer
+    if ((rc = ensure_warp_buf(c, (size_t)n * cp.out_pair))) return rc;
+    flow_out = c->warp_buf;
+  }
+  OFDIS_TRACE("run_batch: kind %d, %d chunks of %d, %d lanes", (int)cp.kind, cp.nchunks, cp.chunk, cp.lanes);
+  GraphKey key = graph_key(GraphKey::kBatch, c, img_a, img_b, init, flow_out, wo ? c->warp_buf : nullptr, n, width,
+                           height, stride, p);
+  GraphKey::Batch &kb = key.u.batch;
+  kb.out_f16 = fmt.f16; kb.out_planar = fmt.planar; kb.out_level = fmt.level;
+  if (bd) {  // a plain call after a bidirectional one on the same buffers records anew, and the other way round
+    kb.bidir = !bd->stereo; kb.stereo = bd->stereo; kb.flow_bw = bd->flow_bw; kb.occ_fw = bd->occ_fw; kb.occ_bw = bd->occ_bw;
+    kb.err_fw = bd->err_fw; kb.err_bw = bd->err_bw; kb.alpha = bd->alpha; kb.beta = bd->beta;
+  }
+  if (wo) {
+    kb.warp = 1; kb.warp_out = wo->out; kb.warp_valid = wo->valid; kb.warp_scale = wo->scale; kb.warp_f32 = wo->f32;
+  }
+  return replay_or_record(c, s, cp, key, [&](hipStream_t q) {
+    return for_each_chunk(c, cp, q, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      const BidirOut part = bd ? bd->at(f0, px) : BidirOut();
+      const WarpOut wpart = wo ? wo->at(f0, px, p->noc) : WarpOut();
+      return run_chunk(c, ws, P, p, img_a + f0 * in_frame, img_b ? img_b + f0 * in_frame : nullptr,
+                       init ? init + f0 * out_frame : nullptr, (char *)flow_out + f0 * cp.out_pair, bd ? &part : nullptr,
+                       ls, fmt, wo ? &wpart : nullptr);
+    });
+  });
+}
+
 // ofdis_run_interp_u8 on stream s (no stage capture is set): the bidirectional plan with nothing kept at full
-// resolution, the 2 n level grids in the context's buffer, and run_batch's chunk, lane and graph rules.
+// resolution and the 2 n level grids in the context's buffer, the n forward grids and then the n backward ones.
 // stride > 0: img_a is a sequence of n + stride frames (the sequence plan) and img_b its frame `stride`.
 int run_batch_interp(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
                      int height, const ofdis_params *p, const InterpOut &io, int stride = 0) {
@@ -1443,47 +1491,24 @@ int run_batch_interp(ofdis_context *c, hipStream_t s, const uint8_t *img_a, cons
   // (masks the caller does not take live in the chunk's workspace)
   int rc = prepare(c, p, n, width, height, false, false, cp, io.use_occ && !(io.occ_fw && io.occ_bw) ? 3 : 1, stride);
   if (rc) return rc;
-  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
-  cp.out_pair = (size_t)P1.lv[0].w * P1.lv[0].h * P1.nop * 4;  // a pair's float32 level grid
+  cp.out_pair = level_grid_bytes(first_plan(cp));
   if ((rc = ensure_warp_buf(c, 2 * (size_t)n * cp.out_pair))) return rc;  // (drops the graph before it grows)
-  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
-  if (!graph || c->timing) return issue_interp(c, cp, s, p, img_a, img_b, c->warp_buf, io);
-  ofdis_context::GraphKey key;
-  std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
-  key.a = img_a; key.b = img_b; key.out = c->warp_buf; key.ws = c->ws;
-  key.n = n; key.w = width; key.h = height; key.p = *p;
-  key.out_level = 1;
-  key.warp = 2; key.warp_out = io.out; key.warp_valid = io.valid; key.warp_buf = c->warp_buf; key.warp_f32 = io.f32;
-  key.seq = stride > 0; key.stride = stride;  // a sequence call on a pair call's buffers records anew
-  if (io.use_occ) {  // and so does a call with masks after one without, or with other thresholds or mask arrays
-    key.bidir = 1; key.occ_fw = io.occ_fw; key.occ_bw = io.occ_bw; key.alpha = io.alpha; key.beta = io.beta;
+  char *grids = c->warp_buf, *grids_bw = grids + (size_t)n * cp.out_pair;
+  GraphKey key = graph_key(GraphKey::kInterp, c, img_a, img_b, nullptr, grids, grids, n, width, height, stride, p);
+  GraphKey::Interp &ki = key.u.interp;
+  ki.pictures = io.out; ki.valid = io.valid; ki.f32 = io.f32;
+  if (io.use_occ) {  // a call with masks after one without, or with other thresholds or mask arrays, records anew
+    ki.use_occ = 1; ki.occ_fw = io.occ_fw; ki.occ_bw = io.occ_bw; ki.alpha = io.alpha; ki.beta = io.beta;
   }
-  ofdis_context::InterpKey ikey;
-  std::memset(&ikey, 0, sizeof(ikey));
-  ikey.nt = io.nt;
-  std::memcpy(ikey.t, io.t, sizeof(float) * io.nt);
-  if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0 || std::memcmp(&ikey, &c->ikey, sizeof(ikey)) != 0) {
-    if ((rc = drop_graph(c))) return rc;
-    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = issue_interp(c, cp, c->stream, p, img_a, img_b, c->warp_buf, io);
-    hipGraph_t graph = nullptr;
-    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-    if (rc) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    if (ce != hipSuccess || !graph) return OFDIS_ERR_DEVICE;
-    const hipError_t ie = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (ie != hipSuccess) {
-      c->gexec = nullptr;
-      return OFDIS_ERR_DEVICE;
-    }
-    std::memcpy(&c->gkey, &key, sizeof(key));
-    std::memcpy(&c->ikey, &ikey, sizeof(ikey));
-  }
-  HIP_OK(hipGraphLaunch(c->gexec, s));
-  return OFDIS_OK;
+  ki.nt = io.nt;  // and so does the same call with other times
+  std::memcpy(ki.t, io.t, sizeof(float) * io.nt);
+  const size_t px = (size_t)width * height, in_frame = px * p->noc;
+  return replay_or_record(c, s, cp, key, [&](hipStream_t q) {
+    return for_each_chunk(c, cp, q, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      return run_chunk_interp(c, ws, P, p, img_a + f0 * in_frame, img_b + f0 * in_frame, grids + f0 * cp.out_pair,
+                              grids_bw + f0 * cp.out_pair, io.at(f0, px, p->noc), ls);
+    });
+  });
 }
 
 // verbosity 2, one pair (the CLI): the reference's stdout timers -- pyramid (run_dense.cpp:352), grid
@@ -1524,6 +1549,7 @@ int run_verbose(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, co
 }
 
 }  // namespace
+}  // extern "C++"
 
 int ofdis_run_batch_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
                        const ofdis_params *p, float *flow_out, void *stream) {
@@ -1533,15 +1559,11 @@ int ofdis_run_batch_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *im
 int ofdis_run_batch_u8_init(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, const float *init, int n,
                             int width, int height, const ofdis_params *p, float *flow_out, void *stream) {
   if (!c || !img_a || !img_b || !flow_out || n <= 0 || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
-  int rc = validate_call(p, width, height, init != nullptr);
+  const int rc = validate_call(p, width, height, init != nullptr);
   if (rc) return rc;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch(c, s, img_a, img_b, init, n, width, height, p, flow_out);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_batch(c, s, img_a, img_b, init, n, width, height, p, flow_out);
+  });
 }
 
 int ofdis_run_batch_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
@@ -1615,14 +1637,8 @@ int ofdis_fb_check(ofdis_context *c, const float *flow_fw, const float *flow_bw,
   o.alpha = alpha;
   o.beta = beta;
   if (!o.checks()) return OFDIS_OK;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  int rc = call_begin(c, stream, s);
-  if (rc) return rc;
-  rc = run_fb_check(c, flow_fw, flow_bw, n, width, height, o, s);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false,
+                     [&](hipStream_t s) { return run_fb_check(c, flow_fw, flow_bw, n, width, height, o, s); });
 }
 
 int ofdis_run_bidir_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
@@ -1642,15 +1658,10 @@ int ofdis_run_bidir_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *im
   o.err_bw = err_bw;
   o.alpha = alpha;
   o.beta = beta;
-  std::lock_guard<std::mutex> lock(c->mu);
-  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  // nothing but the forward flow asked for: the plain call
-  rc = run_batch(c, s, img_a, img_b, nullptr, n, width, height, p, flow_fw, flow_bw || o.checks() ? &o : nullptr);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, true, [&](hipStream_t s) {
+    // nothing but the forward flow asked for: the plain call
+    return run_batch(c, s, img_a, img_b, nullptr, n, width, height, p, flow_fw, flow_bw || o.checks() ? &o : nullptr);
+  });
 }
 
 extern "C++" {  // (a template)
@@ -1729,14 +1740,8 @@ int ofdis_lr_check(ofdis_context *c, const float *disp_l, const float *disp_r, i
   o.alpha = alpha;
   o.beta = beta;
   if (!o.checks()) return OFDIS_OK;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  int rc = call_begin(c, stream, s);
-  if (rc) return rc;
-  rc = run_lr_check(c, disp_l, disp_r, n, width, height, o, s);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false,
+                     [&](hipStream_t s) { return run_lr_check(c, disp_l, disp_r, n, width, height, o, s); });
 }
 
 int ofdis_run_stereo_u8(ofdis_context *c, const uint8_t *img_l, const uint8_t *img_r, int n, int width, int height,
@@ -1757,15 +1762,10 @@ int ofdis_run_stereo_u8(ofdis_context *c, const uint8_t *img_l, const uint8_t *i
   o.err_bw = err_r;
   o.alpha = alpha;
   o.beta = beta;
-  std::lock_guard<std::mutex> lock(c->mu);
-  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  // nothing but the left view's disparity asked for: the plain call
-  rc = run_batch(c, s, img_l, img_r, nullptr, n, width, height, p, disp_l, disp_r || o.checks() ? &o : nullptr);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, true, [&](hipStream_t s) {
+    // nothing but the left view's disparity asked for: the plain call
+    return run_batch(c, s, img_l, img_r, nullptr, n, width, height, p, disp_l, disp_r || o.checks() ? &o : nullptr);
+  });
 }
 
 int ofdis_run_stereo_u8_host(ofdis_context *c, const uint8_t *img_l, const uint8_t *img_r, int n, int width, int height,
@@ -1802,14 +1802,9 @@ int ofdis_run_sequence_u8(ofdis_context *c, const uint8_t *frames, int nframes, 
   if (rc) return rc;
   if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
   if (init && bidir) return OFDIS_ERR_UNSUPPORTED;              // no pinned initial backward flow
-  std::lock_guard<std::mutex> lock(c->mu);
-  if (bidir && (!c->cap_dis.empty() || !c->cap_tv.empty())) return OFDIS_ERR_UNSUPPORTED;
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch(c, s, frames, nullptr, init, nframes - stride, width, height, p, flow_fw, bidir ? &o : nullptr, stride);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, bidir, [&](hipStream_t s) {
+    return run_batch(c, s, frames, nullptr, init, nframes - stride, width, height, p, flow_fw, bidir ? &o : nullptr, stride);
+  });
 }
 
 int ofdis_run_sequence_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int stride, const float *init,
@@ -1892,13 +1887,9 @@ int ofdis_run_batch_u8_fmt(ofdis_context *c, const uint8_t *img_a, const uint8_t
   if (of.plain())  // the existing path and kernel instantiations
     return ofdis_run_batch_u8_init(c, img_a, img_b, init, n, width, height, p, (float *)flow_out, stream);
   if ((rc = validate_call(p, width, height, init != nullptr))) return rc;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch(c, s, img_a, img_b, init, n, width, height, p, flow_out, nullptr, 0, of);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_batch(c, s, img_a, img_b, init, n, width, height, p, flow_out, nullptr, 0, of);
+  });
 }
 
 int ofdis_run_sequence_u8_fmt(ofdis_context *c, const uint8_t *frames, int nframes, int stride, const float *init,
@@ -1915,13 +1906,9 @@ int ofdis_run_sequence_u8_fmt(ofdis_context *c, const uint8_t *frames, int nfram
                                  nullptr, nullptr, nullptr, nullptr, nullptr, stream);
   if ((rc = validate_call(p, width, height, init != nullptr))) return rc;
   if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch(c, s, frames, nullptr, init, nframes - stride, width, height, p, flow_fw, nullptr, stride, of);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_batch(c, s, frames, nullptr, init, nframes - stride, width, height, p, flow_fw, nullptr, stride, of);
+  });
 }
 
 namespace {
@@ -2009,14 +1996,8 @@ int ofdis_warp_u8(ofdis_context *c, const uint8_t *img, const void *flow, const 
   o.valid = valid;
   o.scale = scale;
   o.f32 = out_dtype == OFDIS_IMG_F32;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  int rc = call_begin(c, stream, s);
-  if (rc) return rc;
-  rc = run_warp(c, img, flow, *v, n, width, height, noc, o, s);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false,
+                     [&](hipStream_t s) { return run_warp(c, img, flow, *v, n, width, height, noc, o, s); });
 }
 
 int ofdis_run_warp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
@@ -2034,13 +2015,9 @@ int ofdis_run_warp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img
   o.f32 = out_dtype == OFDIS_IMG_F32;
   OutFmt of;
   of.level = 1;  // float32, interleaved
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch(c, s, img_a, img_b, nullptr, n, width, height, p, nullptr, nullptr, 0, of, &o);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_batch(c, s, img_a, img_b, nullptr, n, width, height, p, nullptr, nullptr, 0, of, &o);
+  });
 }
 
 int ofdis_run_warp_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
@@ -2116,39 +2093,9 @@ int ofdis_interp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b
   o.f32 = out_dtype == OFDIS_IMG_F32;
   o.nt = nt;
   std::memcpy(o.t, t, sizeof(float) * nt);
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  int rc = call_begin(c, stream, s);
-  if (rc) return rc;
-  rc = run_interp(c, img_a, img_b, flow_fw, flow_bw, *v, n, width, height, noc, o, s);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
-}
-
-int ofdis_run_interp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
-                        const ofdis_params *p, const float *t, int nt, int out_dtype, void *out, uint8_t *valid,
-                        void *stream) {
-  if (!c || !img_a || !img_b || !out || n <= 0 || width <= 0 || height <= 0 || !p || !img_dtype_ok(out_dtype) ||
-      (long)width * height > 0x7fffffffL || !interp_times_ok(t, nt))
-    return OFDIS_ERR_INVALID_ARGUMENT;
-  int rc = validate_call(p, width, height, false);
-  if (rc) return rc;
-  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // (as ofdis_run_bidir_u8)
-  InterpOut o;
-  o.out = out;
-  o.valid = valid;
-  o.f32 = out_dtype == OFDIS_IMG_F32;
-  o.nt = nt;
-  std::memcpy(o.t, t, sizeof(float) * nt);
-  std::lock_guard<std::mutex> lock(c->mu);
-  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch_interp(c, s, img_a, img_b, n, width, height, p, o);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_interp(c, img_a, img_b, flow_fw, flow_bw, *v, n, width, height, noc, o, s);
+  });
 }
 
 int ofdis_run_interp_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
@@ -2203,19 +2150,14 @@ int ofdis_fb_check_level(ofdis_context *c, const float *grid_fw, const float *gr
   o.alpha = alpha;
   o.beta = beta;
   if (!o.checks()) return OFDIS_OK;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  int rc = call_begin(c, stream, s);
-  if (rc) return rc;
-  rc = run_fb_check_level(c, grid_fw, grid_bw, *v, n, width, height, o, s);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_fb_check_level(c, grid_fw, grid_bw, *v, n, width, height, o, s);
+  });
 }
 
 namespace {
-// The fused interpolation calls beyond ofdis_run_interp_u8: masks (use_occ) and the sequence plan (stride > 0: img_a is
-// the array of n + stride frames).  Arguments checked as ofdis_run_interp_u8 checks them, plus the thresholds.
+// The fused interpolation calls: ofdis_run_interp_u8, with masks (use_occ: their thresholds checked too) and on the
+// sequence plan (stride > 0: img_a is the array of n + stride frames).
 int run_interp_call(ofdis_context *c, const uint8_t *img_a, int n, int stride, const uint8_t *img_b, int width,
                     int height, const ofdis_params *p, const float *t, int nt, bool use_occ, float alpha, float beta,
                     int out_dtype, void *out, uint8_t *valid, uint8_t *occ_fw, uint8_t *occ_bw, void *stream) {
@@ -2239,14 +2181,9 @@ int run_interp_call(ofdis_context *c, const uint8_t *img_a, int n, int stride, c
     o.beta = beta;
   }
   if (stride > 0) img_b = img_a + (size_t)stride * width * height * p->noc;
-  std::lock_guard<std::mutex> lock(c->mu);
-  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch_interp(c, s, img_a, img_b, n, width, height, p, o, stride);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, true, [&](hipStream_t s) {
+    return run_batch_interp(c, s, img_a, img_b, n, width, height, p, o, stride);
+  });
 }
 
 // Host form of run_interp_call (synchronous): one device block -- the in_a bytes of img_a, the in_b bytes of img_b (a
@@ -2287,6 +2224,14 @@ int run_interp_call_host(ofdis_context *c, const uint8_t *img_a, size_t in_a, co
   return rc;
 }
 }  // namespace
+
+int ofdis_run_interp_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
+                        const ofdis_params *p, const float *t, int nt, int out_dtype, void *out, uint8_t *valid,
+                        void *stream) {
+  if (!img_b) return OFDIS_ERR_INVALID_ARGUMENT;
+  return run_interp_call(c, img_a, n, 0, img_b, width, height, p, t, nt, false, 0.f, 0.f, out_dtype, out, valid, nullptr,
+                         nullptr, stream);
+}
 
 int ofdis_run_interp_occ_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, int n, int width, int height,
                             const ofdis_params *p, const float *t, int nt, float alpha, float beta, int out_dtype,
@@ -2378,104 +2323,33 @@ int run_track(ofdis_context *c, const void *fw, const void *bw, const ofdis_flow
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
-// One chunk of ofdis_run_sequence_track_u8 (P a sequence plan of stride 1, bidirectional when the backward grids are
-// wanted): the pipeline of run_chunk, then the finest level's flows x 2^sc_l as float32 interleaved level grids into the
-// chunk's share of the context's buffer (grid_bw NULL: the forward grids alone).  No upsample runs.
-int run_chunk_track(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *frames,
-                    void *grid_fw, void *grid_bw, hipStream_t s) {
-  int rc = run_pyramid(c, ws, P, frames, nullptr, s);
-  if (rc) return rc;
-  if ((rc = run_levels(c, ws, P, p, s, nullptr, nullptr))) return rc;
-  for (int dir = 0; dir < (grid_bw ? 2 : 1); ++dir) {
-    LevelOutArgs lo{};
-    lo.flow = (const float *)(ws + (dir ? P.off_flow_bw[0] : P.off_flow[0]));
-    lo.out = dir ? grid_bw : grid_fw;
-    lo.n = P.n;
-    lo.nop = P.nop;
-    lo.wl = P.lv[0].w;
-    lo.hl = P.lv[0].h;
-    lo.log2s = p->sc_l;
-    timed(c, 17, s, [&] { launch_level_out(lo, s); });
-    if (hipGetLastError() != hipSuccess) return OFDIS_ERR_DEVICE;
-  }
-  return OFDIS_OK;
-}
-
-// The call's issue in run_batch's two kinds -- the whole video on stream s, or chunks round-robin over the lanes (fork
-// from s, join into s) -- and after the join the one track launch on s over all grids.  grids: the context's buffer,
-// the m forward grids and then the m backward ones.
-int issue_track(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *frames,
-                char *grids, const TrackIo &io) {
-  char *grids_bw = io.use_fb ? grids + (size_t)cp.n * cp.out_pair : nullptr;
-  if (cp.kind == CallPlan::kSingle) {
-    int rc = run_chunk_track(c, c->ws, cp.whole, p, frames, grids, grids_bw, s);
-    if (rc) return rc;
-  } else {
-    const int k = cp.lanes;
-    HIP_OK(hipEventRecord(c->entry, s));
-    for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
-    const size_t in_frame = (size_t)cp.width * cp.height * p->noc;
-    for (int ch = 0; ch < cp.nchunks; ++ch) {
-      const size_t f0 = (size_t)ch * cp.chunk;
-      auto &L = c->lanes[ch % k];
-      int rc = run_chunk_track(c, L.ws, cp.parts[ch], p, frames + f0 * in_frame, grids + f0 * cp.out_pair,
-                               grids_bw ? grids_bw + f0 * cp.out_pair : nullptr, L.s);
-      if (rc) return rc;
-    }
-    for (int i = 0; i < k; ++i) {
-      HIP_OK(hipEventRecord(c->lanes[i].done, c->lanes[i].s));
-      HIP_OK(hipStreamWaitEvent(s, c->lanes[i].done, 0));
-    }
-  }
-  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
-  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P1.lv[0].w, P1.lv[0].h, 1 << p->sc_l, P1.padl, P1.padt};
-  return run_track(c, grids, grids_bw, v, cp.n, cp.width, cp.height, io, s);
-}
-
-// ofdis_run_sequence_track_u8 on stream s (no stage capture is set): the sequence plan of stride 1, the m or 2 m level
-// grids in the context's buffer, and run_batch's chunk, lane and graph rules.
+// ofdis_run_sequence_track_u8 on stream s (no stage capture is set): the sequence plan of stride 1, bidirectional with
+// use_fb; the m forward level grids in the context's buffer and then, with use_fb, the m backward ones, every chunk
+// writing its share; after the chunks one track launch on s over all grids.
 int run_batch_track(ofdis_context *c, hipStream_t s, const uint8_t *frames, int m, int width, int height,
                     const ofdis_params *p, const TrackIo &io) {
   CallPlan cp;
   int rc = prepare(c, p, m, width, height, false, false, cp, io.use_fb ? 1 : 0, 1);
   if (rc) return rc;
-  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
-  cp.out_pair = (size_t)P1.lv[0].w * P1.lv[0].h * P1.nop * 4;  // a pair's float32 level grid
+  const ofdis_flow_view v = level_view(first_plan(cp));
+  cp.out_pair = level_grid_bytes(first_plan(cp));
   if ((rc = ensure_warp_buf(c, (io.use_fb ? 2 : 1) * (size_t)m * cp.out_pair))) return rc;  // (drops the graph before it grows)
-  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
-  if (!graph || c->timing) return issue_track(c, cp, s, p, frames, c->warp_buf, io);
-  ofdis_context::GraphKey key;
-  std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
-  key.a = frames; key.out = c->warp_buf; key.ws = c->ws;
-  key.n = m; key.w = width; key.h = height; key.p = *p;
-  key.out_level = 1; key.seq = 1; key.stride = 1;
-  key.warp = 3; key.warp_buf = c->warp_buf;
-  key.trk_points = io.points; key.trk_start = io.start; key.trk_tracks = io.tracks; key.trk_status = io.status;
-  key.trk_npts = io.npts; key.trk_flags = io.flags;
+  char *grids = c->warp_buf, *grids_bw = io.use_fb ? grids + (size_t)m * cp.out_pair : nullptr;
+  GraphKey key = graph_key(GraphKey::kTrack, c, frames, nullptr, nullptr, grids, grids, m, width, height, 1, p);
+  GraphKey::Track &kt = key.u.track;
+  kt.points = io.points; kt.start = io.start; kt.tracks = io.tracks; kt.status = io.status;
+  kt.npts = io.npts; kt.flags = io.flags;
   if (io.use_fb) {
-    key.bidir = 1; key.alpha = io.alpha; key.beta = io.beta;
+    kt.use_fb = 1; kt.alpha = io.alpha; kt.beta = io.beta;
   }
-  if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0) {
-    if ((rc = drop_graph(c))) return rc;
-    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = issue_track(c, cp, c->stream, p, frames, c->warp_buf, io);
-    hipGraph_t graph = nullptr;
-    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-    if (rc) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    if (ce != hipSuccess || !graph) return OFDIS_ERR_DEVICE;
-    const hipError_t ie = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (ie != hipSuccess) {
-      c->gexec = nullptr;
-      return OFDIS_ERR_DEVICE;
-    }
-    std::memcpy(&c->gkey, &key, sizeof(key));
-  }
-  HIP_OK(hipGraphLaunch(c->gexec, s));
-  return OFDIS_OK;
+  const size_t in_frame = (size_t)width * height * p->noc;
+  return replay_or_record(c, s, cp, key, [&](hipStream_t q) {
+    const int err = for_each_chunk(c, cp, q, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      return run_chunk_grids(c, ws, P, p, frames + f0 * in_frame, nullptr, grids + f0 * cp.out_pair,
+                             grids_bw ? grids_bw + f0 * cp.out_pair : nullptr, ls);
+    });
+    return err ? err : run_track(c, grids, grids_bw, v, m, width, height, io, q);
+  });
 }
 }  // namespace
 
@@ -2501,14 +2375,8 @@ int ofdis_track_points(ofdis_context *c, const void *flow_fw, const void *flow_b
     return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_fb_check_level)
   if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
   if (!tracks && !status) return OFDIS_OK;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  int rc = call_begin(c, stream, s);
-  if (rc) return rc;
-  rc = run_track(c, flow_fw, flow_bw, *v, m, width, height, io, s);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false,
+                     [&](hipStream_t s) { return run_track(c, flow_fw, flow_bw, *v, m, width, height, io, s); });
 }
 
 int ofdis_run_sequence_track_u8(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
@@ -2528,15 +2396,9 @@ int ofdis_run_sequence_track_u8(ofdis_context *c, const uint8_t *frames, int nfr
   int rc = validate_call(p, width, height, false);
   if (rc) return rc;
   if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
-  std::lock_guard<std::mutex> lock(c->mu);
-  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
-  if (!tracks && !status) return OFDIS_OK;
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch_track(c, s, frames, nframes - 1, width, height, p, io);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(
+      c, stream, true, [&](hipStream_t s) { return run_batch_track(c, s, frames, nframes - 1, width, height, p, io); },
+      !tracks && !status);
 }
 
 int ofdis_run_sequence_track_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
@@ -2631,107 +2493,47 @@ int run_tfilter(ofdis_context *c, const uint8_t *frames, int nframes, const void
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
-// One chunk of ofdis_run_sequence_tfilter_u8 (P a bidirectional sequence plan of stride 1): run_chunk_track's pipeline
-// and level grids, then with masks the check on the chunk's own grids into its share of the call's masks.
-int run_chunk_tfilter(ofdis_context *c, char *ws, const Plan &P, const ofdis_params *p, const uint8_t *frames,
-                      void *grid_fw, void *grid_bw, uint8_t *occ_fw, uint8_t *occ_bw, const TfilterIo &io, hipStream_t s) {
-  int rc = run_chunk_track(c, ws, P, p, frames, grid_fw, grid_bw, s);
-  if (rc || !io.use_occ) return rc;
-  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P.lv[0].w, P.lv[0].h, 1 << p->sc_l, P.padl, P.padt};
-  BidirOut bo;
-  bo.occ_fw = occ_fw;
-  bo.occ_bw = occ_bw;
-  bo.alpha = io.alpha;
-  bo.beta = io.beta;
-  return run_fb_check_level(c, (const float *)grid_fw, (const float *)grid_bw, v, P.n, P.W0, P.H0, bo, s);
-}
-
-// The call's issue in run_batch's two kinds, as issue_track, and after the join the one filter launch on s over all
-// frames.  grids: the context's buffer, the m forward grids and then the m backward ones; masks likewise (use_occ).
-int issue_tfilter(ofdis_context *c, const CallPlan &cp, hipStream_t s, const ofdis_params *p, const uint8_t *frames,
-                  char *grids, uint8_t *masks, const TfilterIo &io) {
-  const size_t px = (size_t)cp.width * cp.height;
-  char *grids_bw = grids + (size_t)cp.n * cp.out_pair;
-  uint8_t *masks_bw = masks ? masks + (size_t)cp.n * px : nullptr;
-  if (cp.kind == CallPlan::kSingle) {
-    int rc = run_chunk_tfilter(c, c->ws, cp.whole, p, frames, grids, grids_bw, masks, masks_bw, io, s);
-    if (rc) return rc;
-  } else {
-    const int k = cp.lanes;
-    HIP_OK(hipEventRecord(c->entry, s));
-    for (int i = 0; i < k; ++i) HIP_OK(hipStreamWaitEvent(c->lanes[i].s, c->entry, 0));
-    const size_t in_frame = px * p->noc;
-    for (int ch = 0; ch < cp.nchunks; ++ch) {
-      const size_t f0 = (size_t)ch * cp.chunk;
-      auto &L = c->lanes[ch % k];
-      int rc = run_chunk_tfilter(c, L.ws, cp.parts[ch], p, frames + f0 * in_frame, grids + f0 * cp.out_pair,
-                                 grids_bw + f0 * cp.out_pair, masks ? masks + f0 * px : nullptr,
-                                 masks ? masks_bw + f0 * px : nullptr, io, L.s);
-      if (rc) return rc;
-    }
-    for (int i = 0; i < k; ++i) {
-      HIP_OK(hipEventRecord(c->lanes[i].done, c->lanes[i].s));
-      HIP_OK(hipStreamWaitEvent(s, c->lanes[i].done, 0));
-    }
-  }
-  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
-  ofdis_flow_view v{OFDIS_OUT_F32, OFDIS_OUT_INTERLEAVED, OFDIS_OUT_LEVEL, P1.lv[0].w, P1.lv[0].h, 1 << p->sc_l, P1.padl, P1.padt};
-  TfilterIo fio = io;
-  fio.occ_fw = masks;
-  fio.occ_bw = masks_bw;
-  return run_tfilter(c, frames, cp.n + 1, grids, grids_bw, v, cp.width, cp.height, p->noc, fio, s);
-}
-
-// ofdis_run_sequence_tfilter_u8 on stream s (no stage capture is set): run_batch_track's plan, the 2 m level grids in
-// the context's buffer, with masks the 2 m masks (u8 [2][m][H][W], the forward ones first) behind them in the same
-// buffer, and run_batch's chunk, lane and graph rules.  The graph key is run_batch_interp's in its own fields: warp = 4,
-// warp_out / warp_valid / warp_f32 the picture, `used` and dtype, warp_scale sigma, occ_fw the masks (NULL without
-// use_occ), alpha and beta with use_occ.
+// ofdis_run_sequence_tfilter_u8 on stream s (no stage capture is set): run_batch_track's plan, always bidirectional;
+// the 2 m level grids in the context's buffer and, with masks, the 2 m masks (u8 [2][m][H][W], the forward ones first)
+// behind them in the same buffer.  Every chunk writes its share of the grids and, with masks, runs the check on its own
+// grids into its share of the masks; after the chunks one filter launch on s over all frames.
 int run_batch_tfilter(ofdis_context *c, hipStream_t s, const uint8_t *frames, int m, int width, int height,
                       const ofdis_params *p, const TfilterIo &io) {
   CallPlan cp;
   int rc = prepare(c, p, m, width, height, false, false, cp, 1, 1);
   if (rc) return rc;
-  const Plan &P1 = cp.kind == CallPlan::kSingle ? cp.whole : cp.parts[0];
-  cp.out_pair = (size_t)P1.lv[0].w * P1.lv[0].h * P1.nop * 4;  // a pair's float32 level grid
+  const ofdis_flow_view v = level_view(first_plan(cp));
+  cp.out_pair = level_grid_bytes(first_plan(cp));
+  const size_t px = (size_t)width * height, in_frame = px * p->noc;
   const size_t grid_bytes = align_up(2 * (size_t)m * cp.out_pair);
-  const size_t mask_bytes = io.use_occ ? 2 * (size_t)m * width * height : 0;  // sized per call
+  const size_t mask_bytes = io.use_occ ? 2 * (size_t)m * px : 0;  // sized per call
   if ((rc = ensure_warp_buf(c, grid_bytes + mask_bytes))) return rc;  // (drops the graph before it grows)
-  uint8_t *masks = io.use_occ ? (uint8_t *)c->warp_buf + grid_bytes : nullptr;
-  const bool graph = c->opt_graph == 2 || (c->opt_graph == 1 && cp.kind == CallPlan::kSingle);
-  if (!graph || c->timing) return issue_tfilter(c, cp, s, p, frames, c->warp_buf, masks, io);
-  ofdis_context::GraphKey key;
-  std::memset(&key, 0, sizeof(key));  // padding included: the key is compared bytewise
-  key.a = frames; key.out = c->warp_buf; key.ws = c->ws;
-  key.n = m; key.w = width; key.h = height; key.p = *p;
-  key.out_level = 1; key.seq = 1; key.stride = 1; key.bidir = 1;
-  key.warp = 4; key.warp_buf = c->warp_buf;
-  key.warp_out = io.out; key.warp_valid = io.used; key.warp_f32 = io.f32; key.warp_scale = io.sigma;
-  key.occ_fw = masks;
+  char *grids = c->warp_buf, *grids_bw = grids + (size_t)m * cp.out_pair;
+  uint8_t *masks = io.use_occ ? (uint8_t *)c->warp_buf + grid_bytes : nullptr, *masks_bw = masks ? masks + (size_t)m * px : nullptr;
+  GraphKey key = graph_key(GraphKey::kTfilter, c, frames, nullptr, nullptr, grids, grids, m, width, height, 1, p);
+  GraphKey::Tfilter &kf = key.u.tfilter;
+  kf.picture = io.out; kf.used = io.used; kf.f32 = io.f32; kf.sigma = io.sigma; kf.masks = masks;
   if (io.use_occ) {
-    key.alpha = io.alpha; key.beta = io.beta;
+    kf.alpha = io.alpha; kf.beta = io.beta;
   }
-  if (!c->gexec || std::memcmp(&key, &c->gkey, sizeof(key)) != 0) {
-    if ((rc = drop_graph(c))) return rc;
-    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = issue_tfilter(c, cp, c->stream, p, frames, c->warp_buf, masks, io);
-    hipGraph_t graph = nullptr;
-    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-    if (rc) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    if (ce != hipSuccess || !graph) return OFDIS_ERR_DEVICE;
-    const hipError_t ie = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (ie != hipSuccess) {
-      c->gexec = nullptr;
-      return OFDIS_ERR_DEVICE;
-    }
-    std::memcpy(&c->gkey, &key, sizeof(key));
-  }
-  HIP_OK(hipGraphLaunch(c->gexec, s));
-  return OFDIS_OK;
+  return replay_or_record(c, s, cp, key, [&](hipStream_t q) {
+    const int err = for_each_chunk(c, cp, q, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      char *gfw = grids + f0 * cp.out_pair, *gbw = grids_bw + f0 * cp.out_pair;
+      const int err = run_chunk_grids(c, ws, P, p, frames + f0 * in_frame, nullptr, gfw, gbw, ls);
+      if (err || !io.use_occ) return err;
+      BidirOut bo;
+      bo.occ_fw = masks + f0 * px;
+      bo.occ_bw = masks_bw + f0 * px;
+      bo.alpha = io.alpha;
+      bo.beta = io.beta;
+      return run_fb_check_level(c, (const float *)gfw, (const float *)gbw, level_view(P), P.n, P.W0, P.H0, bo, ls);
+    });
+    if (err) return err;
+    TfilterIo fio = io;  // the filter reads the call's own masks
+    fio.occ_fw = masks;
+    fio.occ_bw = masks_bw;
+    return run_tfilter(c, frames, m + 1, grids, grids_bw, v, width, height, p->noc, fio, q);
+  });
 }
 }  // namespace
 
@@ -2754,14 +2556,9 @@ int ofdis_tfilter_u8(ofdis_context *c, const uint8_t *frames, int nframes, const
   if (v->grid == OFDIS_OUT_LEVEL && (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED))
     return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_track_points)
   if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  int rc = call_begin(c, stream, s);
-  if (rc) return rc;
-  rc = run_tfilter(c, frames, nframes, flow_fw, flow_bw, *v, width, height, noc, io, s);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_tfilter(c, frames, nframes, flow_fw, flow_bw, *v, width, height, noc, io, s);
+  });
 }
 
 int ofdis_run_sequence_tfilter_u8(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
@@ -2781,14 +2578,9 @@ int ofdis_run_sequence_tfilter_u8(ofdis_context *c, const uint8_t *frames, int n
   int rc = validate_call(p, width, height, false);
   if (rc) return rc;
   if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
-  std::lock_guard<std::mutex> lock(c->mu);
-  if (!c->cap_dis.empty() || !c->cap_tv.empty()) return OFDIS_ERR_UNSUPPORTED;
-  HIP_OK(hipSetDevice(c->device));
-  hipStream_t s;
-  if ((rc = call_begin(c, stream, s))) return rc;
-  rc = run_batch_tfilter(c, s, frames, nframes - 1, width, height, p, io);
-  const int rc2 = call_end(c, stream, s);
-  return rc ? rc : rc2;
+  return device_call(c, stream, true, [&](hipStream_t s) {
+    return run_batch_tfilter(c, s, frames, nframes - 1, width, height, p, io);
+  });
 }
 
 int ofdis_run_sequence_tfilter_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
