@@ -636,6 +636,112 @@ int ofdis_run_sequence_tfilter_u8_host(ofdis_context *ctx, const uint8_t *frames
                                        const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
                                        int out_dtype, void *out, uint8_t *used);
 
+/* ------------------------------------------------------------------ global motion and video stabilisation
+ *
+ * Not in the reference.  The camera's motion between the frames of a video as one 2 x 3 transform per frame pair, fitted
+ * robustly to the flow at a sparse lattice of samples, and the stabilised video built from those transforms: the
+ * cumulative camera path, smoothed, and every frame pulled through the difference.  Three device primitives and one
+ * fused call.  All transform arithmetic is float64 (normal equations over coordinates up to 4096 px are ill-conditioned
+ * in float32); every operation below is rounded on its own (no fused multiply-add), `/` is the correctly rounded
+ * division, and there is no square root and no transcendental function, so numpy restates every bit
+ * (tests/test_stabilize.py).  A transform is six doubles (m00, m01, m02, m10, m11, m12) in pixel coordinates.
+ *
+ * ofdis_fit_motion: a robust similarity (or translation) per field of a chain of m fields.  All pointers are device
+ * pointers.  flow_fw / flow_bw / view: ofdis_track_points's rules -- a full view of any dtype and layout, or a level
+ * view, float32 interleaved only (any other valid enum value in a level view returns OFDIS_ERR_UNSUPPORTED), which gives
+ * the bits of the full float32 field.  flow_bw NULL: no consistency check (alpha, beta ignored).
+ * xform: double [m][6]; support: int32 [m] or NULL; weights: float [m][ns] or NULL.
+ *
+ * Definition for pair j, h = step / 2 (integer division):
+ *   lattice   columns x_i = h + i*step for i < sx = (W-1-h)/step + 1, rows y_r likewise with sy; ns = sx*sy, sample
+ *             s = r*sx + i (row-major).  cx = (double)(W-1) / 2, cy = (double)(H-1) / 2 (exact);
+ *             xc = (double)x - cx, yc = (double)y - cy.
+ *   value     (u, v) = the field at the integer pixel as the view defines it (binary16 converted exactly; a level view
+ *             expanded as ofdis_warp_u8 defines), converted to double.  ok = isfinite(u) && isfinite(v); with flow_bw
+ *             also: ofdis_fb_check(alpha, beta)'s occ_fw code at that pixel is 0 (for a level view
+ *             ofdis_fb_check_level's), evaluated at the samples alone -- no mask is written.  A sample that is not ok
+ *             has u = v = 0 before any arithmetic (a select, so a NaN flow never reaches a sum).
+ *   weights   solve 0: w = ok ? 1 : 0.  Solve it = 1 .. iters, with (p0 .. p3) of the solve before:
+ *               t_it = tau * 2^(iters - it);  inv = 1.0 / (t_it * t_it)        (the power exact; inv computed on the host)
+ *               ru = u - ((p0*xc - p1*yc) + p2);  rv = v - ((p1*xc + p0*yc) + p3);  r2 = ru*ru + rv*rv
+ *               w  = ok ? fmax(1 - r2*inv, 0) : 0
+ *   sums      Sw, Sx, Sy, Sr, Su, Sv, Sa, Sb of the per-sample terms w, w*xc, w*yc, w*((xc*xc)+(yc*yc)), w*u, w*v,
+ *             w*((xc*u)+(yc*v)), w*((xc*v)-(yc*u)), and cnt = #{w > 0}.
+ *   order     part[t] = ((0 + term[t]) + term[t + 256]) + ... for t in 0 .. OFDIS_FIT_LANES - 1 (no sample: +0.0);
+ *             then for stride = 128, 64, ..., 1: part[i] = part[i] + part[i + stride] for i < stride; the sum is part[0].
+ *   solve     D  = Sw*Sr - (Sx*Sx + Sy*Sy)
+ *             p0 = (Sw*Sa - (Sx*Su + Sy*Sv)) / D;   p1 = (Sw*Sb - (Sx*Sv - Sy*Su)) / D
+ *             p2 = (Su - (p0*Sx - p1*Sy)) / Sw;     p3 = (Sv - (p1*Sx + p0*Sy)) / Sw
+ *             OFDIS_MOTION_TRANSLATION: p0 = p1 = 0.  The solve fails when cnt < 3 or !(D > 0) (translation: cnt < 1 or
+ *             !(Sw > 0)).  Any failed solve ends the pair: the identity (1, 0, 0, 0, 1, 0), support 0, all weights 0.
+ *   output    position in frame j + 1 = M * position in frame j:
+ *             M = (1+p0, -p1, p2 - (p0*cx - p1*cy),   p1, 1+p0, p3 - (p1*cx + p0*cy)) of the last solve; support = its
+ *             cnt; weights = its w as float32.
+ * Consequences: zero fields give the identity; a NaN or infinite sample changes nothing but the support; the result never
+ * depends on how the work is spread over the device.  Breakdown: the annealed fit is a redescending M-estimator started
+ * from least squares, so it needs the dominant motion to hold a clear majority -- on an exact similarity field with 25 %
+ * of the columns displaced by (10, -6), iters >= 2 at tau = 2 recovers every parameter to 5e-9 where iters = 0 misses
+ * by 2; with 40 % displaced it locks on to nothing useful (error about 4).  Use the check (flow_bw) or a coarser model
+ * when the foreground is that large.
+ * Refused before anything is enqueued (OFDIS_ERR_INVALID_ARGUMENT, the context stays usable): whatever
+ * ofdis_track_points refuses of a view and a size; NULL flow_fw, view or xform; m < 1; an unknown model; step < 1;
+ * step / 2 > min(W, H) - 1; ns > OFDIS_FIT_MAX_SAMPLES; tau not finite or outside [1/1024, 65536]; iters outside 0 .. 16;
+ * with flow_bw, the threshold rules of ofdis_fb_check.  Stream and ordering rules are those of ofdis_fb_check. */
+enum { OFDIS_MOTION_TRANSLATION = 0, OFDIS_MOTION_SIMILARITY = 1 };
+#define OFDIS_FIT_MAX_SAMPLES 65536
+#define OFDIS_FIT_LANES 256 /* part of the definition: the summation order above */
+int ofdis_fit_motion(ofdis_context *ctx, const void *flow_fw, const void *flow_bw, const ofdis_flow_view *view, int m,
+                     int width, int height, int model, int step, double tau, int iters, float alpha, float beta,
+                     double *xform, int32_t *support, float *weights, void *stream);
+
+/* ofdis_smooth_path: the m pair transforms to m + 1 per-frame corrections, on the device.  xform: double [m][6];
+ * corr: double [m + 1][6]; corr_i maps a pixel of stabilised frame i to the position in input frame i that it shows.
+ *   compose(P, C):  r00 = P00*C00 + P01*C10;  r01 = P00*C01 + P01*C11;  r02 = (P00*C02 + P01*C12) + P02;  row 1 likewise
+ *   path      C_0 = I;  C_{j+1} = compose(P_j, C_j)
+ *   smoothing S_i, entry by entry: (sum over k = -R .. R, ascending, starting from 0.0, of g_k * C_clamp(i+k, 0, m)) / G
+ *             with g_k = (double)(R+1-|k|), G = (double)((R+1)*(R+1)) -- a triangular window with integer weights
+ *   inverse   det = S00*S11 - S01*S10; det zero or not finite: corr_i = I.  Else i00 = S11/det, i01 = -S01/det,
+ *             i10 = -S10/det, i11 = S00/det, i02 = -(i00*S02 + i01*S12), i12 = -(i10*S02 + i11*S12)
+ *   result    corr_i = compose(compose(C_i, Sinv_i), Z),  z = 1.0 / zoom,  Z = (z, 0, cx - z*cx, 0, z, cy - z*cy)
+ * Refused (OFDIS_ERR_INVALID_ARGUMENT): NULL pointers, m < 1, radius outside 0 .. 256, zoom not finite or outside
+ * [1, 16], a non-positive size.  The chain C lives in the context's workspace.  Stream and ordering rules are those of
+ * ofdis_fb_check. */
+int ofdis_smooth_path(ofdis_context *ctx, const double *xform, int m, int radius, double zoom, int width, int height,
+                      double *corr, void *stream);
+
+/* ofdis_warp_affine_u8: each of n u8 frames pulled through its own transform.  img: u8 [n][height][width][noc]; xf:
+ * device double [n][6]; out: u8 or float32 (out_dtype) of img's shape; valid: u8 [n][height][width] or NULL.  Per pixel
+ *   px = (float)((M00*(double)x + M01*(double)y) + M02);   py = (float)((M10*(double)x + M11*(double)y) + M12)
+ * then ofdis_warp_u8's inside, clamp, taps, val, rounding and valid, verbatim, at (px, py): a replicated border, and
+ * valid = 0 outside.  The identity returns the frame.
+ * Refused (OFDIS_ERR_INVALID_ARGUMENT): what ofdis_warp_u8 refuses of a size, noc and out_dtype; NULL img, xf or out;
+ * n < 1; out overlapping img.  Stream and ordering rules are those of ofdis_fb_check. */
+int ofdis_warp_affine_u8(ofdis_context *ctx, const uint8_t *img, int n, int width, int height, int noc, const double *xf,
+                         int out_dtype, void *out, uint8_t *valid, void *stream);
+
+/* The flows of a video, its camera path and the stabilised frames from one call: frames u8 [nframes][height][width][noc],
+ * m = nframes - 1.  By definition out / valid / xform / corr / support == ofdis_warp_affine_u8(frames,
+ * ofdis_smooth_path(ofdis_fit_motion(F, use_fb ? B : NULL))) bit for bit, with F, B the fields of
+ * ofdis_run_sequence_u8(frames, stride 1) -- but every pair's flows leave the coarse-to-fine loop as float32 level
+ * grids in the buffer the context owns, and after the last chunk come three launches: the fit over all m pairs (which
+ * evaluates the check at its own samples), the path, and the affine warp over all nframes frames.  No upsample runs, no
+ * full-resolution field and no mask exists, and every frame's pyramid is built once.  xform [m][6], corr [nframes][6]
+ * and support [m] are optional outputs; those not asked for live behind the grids in that buffer.
+ * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED, and so does a call while a stage capture is set.  No
+ * initial flow.  verbosity is ignored.  Argument errors are those of ofdis_run_sequence_track_u8 (nframes < 2, ...), of
+ * the three primitives and, with use_fb, the threshold rules of ofdis_fb_check; stream, ordering, chunking, round-robin,
+ * graph and workspace rules are those of ofdis_run_batch_u8 (the graph is recorded anew when an output pointer or any
+ * scalar of the call changes; a graph of another call kind is never replayed). */
+int ofdis_run_sequence_stabilize_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                    const ofdis_params *p, int model, int step, double tau, int iters, int use_fb,
+                                    float alpha, float beta, int radius, double zoom, int out_dtype, void *out,
+                                    uint8_t *valid, double *xform, double *corr, int32_t *support, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_sequence_stabilize_u8_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                         const ofdis_params *p, int model, int step, double tau, int iters, int use_fb,
+                                         float alpha, float beta, int radius, double zoom, int out_dtype, void *out,
+                                         uint8_t *valid, double *xform, double *corr, int32_t *support);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -755,7 +861,9 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * one; the interpolation as "interp" with full-resolution flow views and as "interp_level" with level-grid views; the
  * forward-backward check on level grids as "fb_check_level", whatever it writes; the point tracker as "track" with
  * full-resolution flow views and as "track_level" with level-grid views; the temporal filter as "tfilter" with
- * full-resolution flow views and as "tfilter_level" with level-grid views. */
+ * full-resolution flow views and as "tfilter_level" with level-grid views; the motion fit as "fit_motion" with
+ * full-resolution flow views and as "fit_motion_level" with level-grid views, the path kernel as "smooth_path" and the
+ * affine warp as "warp_affine". */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
@@ -771,7 +879,12 @@ const char *ofdis_kernel_names(void);
  * pixel and direction -- 2 * gw * gh * 8 + 2 * W * H * (1 + 4).  "tfilter" / "tfilter_level": per output frame with
  * both neighbours, in "interp"'s convention (masks not counted): the two float32 flow views (16 bytes per pixel; two
  * level grids, 2 * gw * gh * 8 bytes), 3 noc bytes of image read (the frame and its two neighbours), noc bytes of u8
- * output and the `used` byte per pixel -- W * H * (16 + 4 noc + 1) and 2 * gw * gh * 8 + W * H * (4 noc + 1). */
+ * output and the `used` byte per pixel -- W * H * (16 + 4 noc + 1) and 2 * gw * gh * 8 + W * H * (4 noc + 1).
+ * "fit_motion" / "fit_motion_level": per pair at the default lattice (step 16, ns samples; the check's gather not
+ * counted): the 8-byte value of a float32 view per sample, ns * 8; of a level grid the up to nine 8-byte cells a
+ * sample's expansion reads, ns * 72.  "smooth_path": six doubles per pair in and per frame out, 96.  "warp_affine": per
+ * frame, noc bytes of image read, noc bytes of u8 output and the mask byte per pixel and the six doubles --
+ * W * H * (2 noc + 1) + 48. */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */

@@ -3,8 +3,9 @@
 Drop-in for lordnn/OF_DIS's OFClass / run_dense pipeline.  The compute lives in libofdis.so
 (hand-written HIP kernels + C-ABI, include/ofdis.h); this package is a thin host-side mirror.
 """
-from ._lib import IMG_F32, IMG_U8, INTERP_MAX_T, MODE_DE, MODE_OF, TRACK_LAST, FlowView, OfdisError, OutFormat, Params, build, lib, out_format  # noqa: F401
-from .ofclass import (Context, OFClass, algorithmic_bytes, auto_first_scale, kernel_names,  # noqa: F401
+from ._lib import (FIT_LANES, FIT_MAX_SAMPLES, IMG_F32, IMG_U8, INTERP_MAX_T, MODE_DE, MODE_OF, MOTION_SIMILARITY,  # noqa: F401
+                   MOTION_TRANSLATION, TRACK_LAST, FlowView, OfdisError, OutFormat, Params, build, lib, out_format)
+from .ofclass import (Context, OFClass, algorithmic_bytes, auto_first_scale, fit_lattice, kernel_names,  # noqa: F401
                       max_frames_per_launch, oppoint, out_geometry, params_from_strings, pixel_grid, read_flo, read_image, synth_pair, synth_shift_pair, validate,
                       write_flo, write_pfm, write_pnm)
 

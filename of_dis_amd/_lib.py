@@ -35,6 +35,10 @@ IMG_U8, IMG_F32 = 0, 1
 INTERP_MAX_T = 16
 # OFDIS_TRACK_LAST: a tracking call writes only the last frame's entry
 TRACK_LAST = 1
+# the models of ofdis_fit_motion, and its limits (OFDIS_FIT_MAX_SAMPLES, OFDIS_FIT_LANES)
+MOTION_TRANSLATION, MOTION_SIMILARITY = 0, 1
+FIT_MAX_SAMPLES = 65536
+FIT_LANES = 256
 
 
 class OfdisError(RuntimeError):
@@ -124,7 +128,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "or `make -C of_dis_amd/csrc` (hipcc, gfx950)")
     L = C.CDLL(LIB_PATH)
-    vp, i, f = C.c_void_p, C.c_int, C.c_float
+    vp, i, f, d = C.c_void_p, C.c_int, C.c_float, C.c_double
     P = C.POINTER(Params)
     F = C.POINTER(OutFormat)
     V = C.POINTER(FlowView)
@@ -172,6 +176,11 @@ def lib():
         "ofdis_tfilter_u8": ([vp, vp, i, vp, vp, V, i, i, i, f, vp, vp, i, vp, vp, vp], i),
         "ofdis_run_sequence_tfilter_u8": ([vp, vp, i, i, i, P, f, i, f, f, i, vp, vp, vp], i),
         "ofdis_run_sequence_tfilter_u8_host": ([vp, vp, i, i, i, P, f, i, f, f, i, vp, vp], i),
+        "ofdis_fit_motion": ([vp, vp, vp, V, i, i, i, i, i, d, i, f, f, vp, vp, vp, vp], i),
+        "ofdis_smooth_path": ([vp, vp, i, i, d, i, i, vp, vp], i),
+        "ofdis_warp_affine_u8": ([vp, vp, i, i, i, i, vp, i, vp, vp, vp], i),
+        "ofdis_run_sequence_stabilize_u8": ([vp, vp, i, i, i, P, i, i, d, i, i, f, f, i, d, i, vp, vp, vp, vp, vp, vp], i),
+        "ofdis_run_sequence_stabilize_u8_host": ([vp, vp, i, i, i, P, i, i, d, i, i, f, f, i, d, i, vp, vp, vp, vp, vp], i),
         "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),

@@ -269,7 +269,49 @@ struct TfilterArgs {
   int srows, scols;              // level form: rows and columns of a staged window (set by launch_tfilter)
 };
 
+// A robust similarity or translation fitted to each of m flow fields (include/ofdis.h: ofdis_fit_motion).  One view
+// describes both chains.
+constexpr int kFitLanes = 256;         // OFDIS_FIT_LANES: one workgroup per pair, the pinned summation order
+constexpr int kFitMaxSamples = 65536;  // OFDIS_FIT_MAX_SAMPLES
+constexpr int kFitMaxIters = 16;
+struct FitArgs {
+  const void *fw, *bw;   // m fields back to back in the layouts of WarpArgs::flow; bw NULL: no consistency check
+  double *xform;         // [m][6]
+  int32_t *support;      // [m] or NULL
+  float *weights;        // [m][ns] or NULL
+  int m, W, H;           // W * H < 2^31
+  int similarity;        // OFDIS_MOTION_SIMILARITY (else a translation)
+  int step, half, sx, sy, ns;  // the lattice: columns half + i * step, i < sx; rows likewise; ns = sx * sy
+  int iters;
+  double inv[kFitMaxIters + 1];  // inv[it] = 1 / t_it^2 of solve it = 1 .. iters (the host's divisions)
+  float alpha, beta;
+  int f16, planar, level;
+  int gw, gh, log2c, offx, offy;  // as WarpArgs
+};
+
+// Pair transforms to per-frame corrections (include/ofdis.h: ofdis_smooth_path).
+struct PathArgs {
+  const double *xform;  // [m][6]
+  double *corr;         // [m + 1][6]
+  double *chain;        // [m + 1][6] scratch: the cumulative transforms C_i
+  int m, radius, W, H;
+  double z;             // 1 / zoom (the host's division)
+};
+
+// Each of n u8 frames pulled through its own 2 x 3 transform (include/ofdis.h: ofdis_warp_affine_u8).
+struct WarpAffineArgs {
+  const uint8_t *img;  // [n][H][W][noc]
+  const double *xf;    // [n][6], device
+  void *out;           // u8 or float [n][H][W][noc]
+  uint8_t *valid;      // [n][H][W] 1 / 0, or NULL
+  int n, W, H, noc;    // W * H < 2^31
+  int out_f32;
+};
+
 void launch_warp(const WarpArgs &a, hipStream_t s);
+void launch_fit_motion(const FitArgs &a, hipStream_t s);
+void launch_smooth_path(const PathArgs &a, hipStream_t s);
+void launch_warp_affine(const WarpAffineArgs &a, hipStream_t s);
 void launch_track(const TrackArgs &a, hipStream_t s);
 void launch_tfilter(const TfilterArgs &a, hipStream_t s);
 void launch_interp(const InterpArgs &a, hipStream_t s);

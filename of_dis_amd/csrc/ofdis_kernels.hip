@@ -40,6 +40,9 @@
 //                thread per point (no reference code)
 //   tfilter      k_tfilter<OT, NOC, FT, PLANAR, PX>, k_tfilter_level<OT, NOC, PX>  every frame of a video averaged with
 //                its two motion-compensated neighbours, full-resolution fields / level grids (no reference code)
+//   motion       k_fit_motion<FT, PLANAR, CACHE>, k_fit_motion_level<CACHE>  a robust similarity per flow field, float64,
+//                one workgroup per pair; k_smooth_path  pair transforms to per-frame corrections;
+//                k_warp_affine<OT, NOC, PX>  every frame through its own 2 x 3 transform (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -6914,6 +6917,349 @@ void launch_tfilter(const TfilterArgs &a0, hipStream_t s) {
       pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {
         if (vec) go(OT, NOC, Int<4>{});
         else go(OT, NOC, Int<1>{});
+      });
+    });
+  }
+}
+
+// ------------------------------------------------------------------------------ global motion, stabilisation
+// The camera's motion per frame pair and the stabilised video built from it (include/ofdis.h: ofdis_fit_motion,
+// ofdis_smooth_path, ofdis_warp_affine_u8).  The fit is float64: the definition fixes every operation, the order of
+// every sum and the shape of the reduction tree (one 256-thread workgroup per pair), so the six numbers of a pair are
+// a pure function of the field's values at the lattice.
+//   k_fit_motion<FT, PLANAR, CACHE>  (CACHE: LDS sample slots, 0 / 2,048 / 16,384) the fields are full-resolution (float32 / binary16, interleaved / planar)
+//   k_fit_motion_level<CACHE>        the fields are float32 interleaved level grids: a sample's own value and, with a
+//                                    backward chain, the four taps of the check come from level_taps -- the check is
+//                                    evaluated at the samples alone and no mask is written
+//   k_smooth_path                    one workgroup: lane 0 chains the pair transforms, then one lane per frame
+//   k_warp_affine<OT, NOC, PX>       k_warp's layout and stores, the position from the frame's 2 x 3 transform
+namespace {
+
+// The field's value at an integer pixel, on top of the tracker's bilinear gather (the check's other field).
+template <class FT, bool PLANAR>
+struct FitFull : TrackFull<FT, PLANAR> {
+  __device__ __forceinline__ void value(const void *base, int j, int x, int y, float &u, float &v) const {
+    const FT *F = reinterpret_cast<const FT *>(base) + (long)j * this->field;
+    const long o = (long)y * this->W + x, plane = this->field >> 1;
+    u = (float)(PLANAR ? F[o] : F[2 * o]);
+    v = (float)(PLANAR ? F[plane + o] : F[2 * o + 1]);
+  }
+};
+struct FitLevel : TrackLevel {
+  __device__ __forceinline__ void value(const void *base, int j, int x, int y, float &u, float &v) const {
+    const float *G = reinterpret_cast<const float *>(base) + (long)j * field;
+    float bx[4], by[4];  // the four taps of a gather whose taps coincide: tap 0 is the expansion at (x, y)
+    level_taps(G, g, scale, x, x, y, y, bx, by);
+    u = bx[0], v = by[0];
+  }
+};
+
+// Samples of a pair kept in LDS across the solves: 2,048 (16 KiB: several pairs per CU) where that holds the lattice,
+// else 16,384 (128 KiB of the CU's 160: one pair per CU), else none -- every solve reads the fields again.
+constexpr int kFitCacheSmall = 2048, kFitCache = 16384;
+
+struct FitSample {
+  float u, v;  // u is NaN for a sample that is not ok (an ok sample is finite)
+};
+
+// Sample s of pair j: the field at its lattice pixel and whether it counts -- finite and, with a backward chain,
+// code 0 of the forward-backward check there (fb_pixel's arithmetic through the tracker's gather).
+template <class S>
+__device__ __forceinline__ FitSample fit_sample(const FitArgs &a, const S &field, int j, int s, int &x, int &y) {
+  const int r = s / a.sx, i = s - r * a.sx;
+  x = a.half + i * a.step, y = a.half + r * a.step;
+  float u, v;
+  field.value(a.fw, j, x, y, u, v);
+  bool ok = __builtin_isfinite(u) && __builtin_isfinite(v);
+  if (a.bw) {
+    const float px = (float)x + u, py = (float)y + v;
+    const bool inside = px >= 0.f && px <= (float)(a.W - 1) && py >= 0.f && py <= (float)(a.H - 1);  // false for NaN
+    float bu, bv;
+    field(a.bw, j, inside ? px : 0.f, inside ? py : 0.f, bu, bv);
+    const float du = u + bu, dv = v + bv;
+    const float e = du * du + dv * dv;
+    const float mag = (u * u + v * v) + (bu * bu + bv * bv);
+    const float thr = a.alpha * mag + a.beta;
+    ok = ok && inside && e <= thr;  // (a NaN error fails)
+  }
+  return FitSample{ok ? u : __builtin_nanf(""), v};
+}
+
+// Pair j = blockIdx.x.  Lane t owns samples t, t + 256, ...; with CACHE > 0 (the slots, at least ns) they are read once
+// and live in the lane's own LDS slots across the iters + 1 solves, else every solve reads them again.  The nine
+// sums -- the eight of the definition and the count, exact in float64 -- go down the pinned tree: strides 128 and 64
+// through LDS, 32 .. 1 by shuffles inside wave 0; lane 0 solves and broadcasts.
+template <class S, int CACHE>
+__device__ __forceinline__ void fit_pair(const FitArgs &a, const S &field) {
+  __shared__ FitSample cache[CACHE ? CACHE : 1];
+  __shared__ double red[9][kFitLanes / 2];
+  __shared__ double sol[5];  // p0 .. p3, failed
+  const int j = blockIdx.x, t = threadIdx.x;
+  const double cx = (double)(a.W - 1) / 2.0, cy = (double)(a.H - 1) / 2.0;
+  if constexpr (CACHE != 0) {
+    for (int s = t; s < a.ns; s += kFitLanes) {
+      int x, y;
+      cache[s] = fit_sample(a, field, j, s, x, y);
+    }
+  }
+  double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0, cnt = 0.0;
+  bool failed = false;
+  float *wout = a.weights ? a.weights + (long)j * a.ns : nullptr;
+  for (int it = 0; it <= a.iters && !failed; ++it) {
+    const double inv = a.inv[it];
+    double acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    for (int s = t; s < a.ns; s += kFitLanes) {
+      int x, y;
+      FitSample q;
+      if constexpr (CACHE != 0) {
+        const int r = s / a.sx, i = s - r * a.sx;
+        x = a.half + i * a.step, y = a.half + r * a.step;
+        q = cache[s];
+      } else {
+        q = fit_sample(a, field, j, s, x, y);
+      }
+      const bool ok = q.u == q.u;
+      const double u = ok ? (double)q.u : 0.0, v = ok ? (double)q.v : 0.0;  // a select: no NaN reaches a sum
+      const double xc = (double)x - cx, yc = (double)y - cy;
+      double w;
+      if (it == 0) {
+        w = ok ? 1.0 : 0.0;
+      } else {
+        const double ru = u - ((p0 * xc - p1 * yc) + p2), rv = v - ((p1 * xc + p0 * yc) + p3);
+        const double r2 = ru * ru + rv * rv;
+        w = ok ? fmax(1.0 - r2 * inv, 0.0) : 0.0;
+      }
+      acc[0] = acc[0] + w;
+      acc[1] = acc[1] + w * xc;
+      acc[2] = acc[2] + w * yc;
+      acc[3] = acc[3] + w * ((xc * xc) + (yc * yc));
+      acc[4] = acc[4] + w * u;
+      acc[5] = acc[5] + w * v;
+      acc[6] = acc[6] + w * ((xc * u) + (yc * v));
+      acc[7] = acc[7] + w * ((xc * v) - (yc * u));
+      acc[8] = acc[8] + (w > 0.0 ? 1.0 : 0.0);
+      if (wout && it == a.iters) wout[s] = (float)w;
+    }
+#pragma unroll
+    for (int half = kFitLanes / 2; half >= 64; half >>= 1) {
+      if (t >= half && t < 2 * half) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) red[k][t - half] = acc[k];
+      }
+      __syncthreads();
+      if (t < half) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) acc[k] = acc[k] + red[k][t];
+      }
+      __syncthreads();
+    }
+    if (t < 64) {
+#pragma unroll
+      for (int stride = 32; stride >= 1; stride >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) acc[k] = acc[k] + __shfl_down(acc[k], stride, 64);
+      }
+    }
+    if (t == 0) {
+      const double Sw = acc[0], Sx = acc[1], Sy = acc[2], Sr = acc[3], Su = acc[4], Sv = acc[5], Sa = acc[6], Sb = acc[7];
+      double q0 = 0.0, q1 = 0.0;
+      bool bad;
+      if (a.similarity) {
+        const double D = Sw * Sr - (Sx * Sx + Sy * Sy);
+        bad = acc[8] < 3.0 || !(D > 0.0);
+        q0 = (Sw * Sa - (Sx * Su + Sy * Sv)) / D;
+        q1 = (Sw * Sb - (Sx * Sv - Sy * Su)) / D;
+      } else {
+        bad = acc[8] < 1.0 || !(Sw > 0.0);
+      }
+      sol[0] = q0, sol[1] = q1;
+      sol[2] = (Su - (q0 * Sx - q1 * Sy)) / Sw;
+      sol[3] = (Sv - (q1 * Sx + q0 * Sy)) / Sw;
+      sol[4] = bad ? 1.0 : 0.0;
+      red[8][0] = acc[8];
+    }
+    __syncthreads();
+    p0 = sol[0], p1 = sol[1], p2 = sol[2], p3 = sol[3], cnt = red[8][0];
+    failed = sol[4] != 0.0;
+    __syncthreads();  // (lane 0 writes sol and red again in the next solve)
+  }
+  if (failed) {  // the identity, support 0 and every weight 0
+    p0 = p1 = p2 = p3 = cnt = 0.0;
+    if (wout)
+      for (int s = t; s < a.ns; s += kFitLanes) wout[s] = 0.f;
+  }
+  if (t == 0) {
+    double *M = a.xform + 6 * (long)j;
+    M[0] = 1.0 + p0, M[1] = failed ? 0.0 : -p1, M[2] = p2 - (p0 * cx - p1 * cy);
+    M[3] = p1, M[4] = 1.0 + p0, M[5] = p3 - (p1 * cx + p0 * cy);
+    if (a.support) a.support[j] = (int32_t)cnt;
+  }
+}
+
+template <class FT, bool PLANAR, int CACHE>
+__global__ __launch_bounds__(kFitLanes) void k_fit_motion(FitArgs a) {
+  fit_pair<FitFull<FT, PLANAR>, CACHE>(a, FitFull<FT, PLANAR>{{a.W, a.H, 2 * (long)a.W * a.H}});
+}
+
+template <int CACHE>
+__global__ __launch_bounds__(kFitLanes) void k_fit_motion_level(FitArgs a) {
+  FitLevel f;
+  f.W = a.W, f.H = a.H, f.field = 2 * (long)a.gw * a.gh;
+  f.g = LevelGeo{a.gw, a.gh, a.log2c, a.offx, a.offy};
+  f.scale = 1.0 / (double)(1 << a.log2c);
+  fit_pair<FitLevel, CACHE>(a, f);
+}
+
+struct Xf {
+  double m[6];  // (m00, m01, m02, m10, m11, m12)
+};
+// compose(P, C) of include/ofdis.h: C first, then P.
+__device__ __forceinline__ Xf xf_compose(const Xf &P, const Xf &C) {
+  Xf r;
+  r.m[0] = P.m[0] * C.m[0] + P.m[1] * C.m[3];
+  r.m[1] = P.m[0] * C.m[1] + P.m[1] * C.m[4];
+  r.m[2] = (P.m[0] * C.m[2] + P.m[1] * C.m[5]) + P.m[2];
+  r.m[3] = P.m[3] * C.m[0] + P.m[4] * C.m[3];
+  r.m[4] = P.m[3] * C.m[1] + P.m[4] * C.m[4];
+  r.m[5] = (P.m[3] * C.m[2] + P.m[4] * C.m[5]) + P.m[5];
+  return r;
+}
+__device__ __forceinline__ Xf xf_load(const double *p) { return Xf{{p[0], p[1], p[2], p[3], p[4], p[5]}}; }
+
+// Lane 0 chains the m pair transforms into a.chain (m dependent 2 x 3 products: microseconds for a video's worth);
+// then lane i smooths, inverts and composes frame i, i + 256, ...
+__global__ __launch_bounds__(256) void k_smooth_path(PathArgs a) {
+  const Xf I{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};
+  if (threadIdx.x == 0) {
+    Xf C = I;
+    for (int e = 0; e < 6; ++e) a.chain[e] = C.m[e];
+    for (int j = 0; j < a.m; ++j) {
+      C = xf_compose(xf_load(a.xform + 6 * (long)j), C);
+      for (int e = 0; e < 6; ++e) a.chain[6 * (long)(j + 1) + e] = C.m[e];
+    }
+  }
+  __syncthreads();  // (the chain is read back by the block that wrote it)
+  const double cx = (double)(a.W - 1) / 2.0, cy = (double)(a.H - 1) / 2.0;
+  const Xf Z{{a.z, 0.0, cx - a.z * cx, 0.0, a.z, cy - a.z * cy}};
+  const int R = a.radius;
+  const double G = (double)((R + 1) * (R + 1));
+  for (int i = threadIdx.x; i <= a.m; i += 256) {
+    Xf S;
+    for (int e = 0; e < 6; ++e) S.m[e] = 0.0;
+    for (int k = -R; k <= R; ++k) {
+      const long c = min(max(i + k, 0), a.m);
+      const double g = (double)(R + 1 - (k < 0 ? -k : k));
+      for (int e = 0; e < 6; ++e) S.m[e] = S.m[e] + g * a.chain[6 * c + e];
+    }
+    for (int e = 0; e < 6; ++e) S.m[e] = S.m[e] / G;
+    const double det = S.m[0] * S.m[4] - S.m[1] * S.m[3];
+    Xf out = I;
+    if (det != 0.0 && __builtin_isfinite(det)) {
+      Xf V;
+      V.m[0] = S.m[4] / det;
+      V.m[1] = -S.m[1] / det;
+      V.m[3] = -S.m[3] / det;
+      V.m[4] = S.m[0] / det;
+      V.m[2] = -(V.m[0] * S.m[2] + V.m[1] * S.m[5]);
+      V.m[5] = -(V.m[3] * S.m[2] + V.m[4] * S.m[5]);
+      out = xf_compose(xf_compose(xf_load(a.chain + 6 * (long)i), V), Z);
+    }
+    for (int e = 0; e < 6; ++e) a.corr[6 * (long)i + e] = out.m[e];
+  }
+}
+
+// k_warp's thread layout (PX = 4: four consecutive pixels of a row per thread, launch_warp_affine's conditions).  The
+// position is two float64 products and two sums per coordinate; the gather follows the transform, not the bytes: at a
+// small rotation a wave's taps stay within a few rows, as k_warp's do along a smooth flow.
+template <class OT, int NOC, int PX>
+__global__ __launch_bounds__(256) void k_warp_affine(WarpAffineArgs a) {
+  const int f = blockIdx.z;
+  const unsigned wq = (unsigned)a.W / PX;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= wq * (unsigned)a.H) return;
+  const int y = (int)(q / wq), x = (int)(q - (unsigned)y * wq) * PX;
+  const long plane = (long)a.W * a.H, o = (long)f * plane + (long)y * a.W + x;
+  const uint8_t *I = a.img + (long)f * plane * NOC;
+  const double *M = a.xf + 6 * (long)f;
+  const double m00 = M[0], m01 = M[1], m02 = M[2], m10 = M[3], m11 = M[4], m12 = M[5];
+  float val[PX * NOC];
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    const float px = (float)((m00 * (double)(x + i) + m01 * (double)y) + m02);
+    const float py = (float)((m10 * (double)(x + i) + m11 * (double)y) + m12);
+    // warp_pixel from pixel (0, 0) along the "flow" (px, py) at scale 1: 1 * px and 0 + px are px (a -0 becomes +0,
+    // which is inside, clamps and taps alike), so the sample is the definition's at (px, py)
+    m |= warp_pixel<NOC>(I, a.W, a.H, 0, 0, px, py, 1.f, val + i * NOC) << (8 * i);
+  }
+  // warp_emit's stores
+  OT *out = reinterpret_cast<OT *>(a.out) + o * NOC;
+  if constexpr (std::is_same<OT, float>::value) {
+    if constexpr (PX == 4) {
+#pragma unroll
+      for (int j = 0; j < NOC; ++j)
+        *reinterpret_cast<float4_v *>(out + 4 * j) = float4_v{val[4 * j], val[4 * j + 1], val[4 * j + 2], val[4 * j + 3]};
+    } else {
+#pragma unroll
+      for (int c = 0; c < NOC; ++c) out[c] = val[c];
+    }
+  } else {  // u8: round half to even, no clamp (warp_emit)
+    unsigned b[PX * NOC];
+#pragma unroll
+    for (int k = 0; k < PX * NOC; ++k) b[k] = (unsigned)(int)rintf(val[k]);
+    if constexpr (PX == 4) {
+#pragma unroll
+      for (int j = 0; j < NOC; ++j)
+        *reinterpret_cast<unsigned *>(out + 4 * j) = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
+    } else {
+#pragma unroll
+      for (int c = 0; c < NOC; ++c) out[c] = (uint8_t)b[c];
+    }
+  }
+  if (a.valid) {
+    if constexpr (PX == 4)
+      *reinterpret_cast<unsigned *>(a.valid + o) = m;
+    else
+      a.valid[o] = (uint8_t)m;
+  }
+}
+
+}  // namespace
+// ---- launch
+// One workgroup per pair; the samples stay in LDS while they fit, in the smallest array that holds them.
+void launch_fit_motion(const FitArgs &a, hipStream_t s) {
+  const dim3 grid(a.m);
+  pick<0, kFitCacheSmall, kFitCache>(a.ns <= kFitCacheSmall ? kFitCacheSmall : a.ns <= kFitCache ? kFitCache : 0, [&](auto CACHE) {
+    if (a.level) k_fit_motion_level<CACHE><<<grid, kFitLanes, 0, s>>>(a);
+    else if (a.f16 && a.planar) k_fit_motion<_Float16, true, CACHE><<<grid, kFitLanes, 0, s>>>(a);
+    else if (a.f16) k_fit_motion<_Float16, false, CACHE><<<grid, kFitLanes, 0, s>>>(a);
+    else if (a.planar) k_fit_motion<float, true, CACHE><<<grid, kFitLanes, 0, s>>>(a);
+    else k_fit_motion<float, false, CACHE><<<grid, kFitLanes, 0, s>>>(a);
+  });
+}
+
+void launch_smooth_path(const PathArgs &a, hipStream_t s) { k_smooth_path<<<1, 256, 0, s>>>(a); }
+
+// Frames go in grid z, 65535 per launch.  The vector stores need W % 4 == 0, the output aligned to its store (4 bytes
+// u8, 16 float32) and the mask to 4.
+void launch_warp_affine(const WarpAffineArgs &a0, hipStream_t s) {
+  const bool vec = a0.W % 4 == 0 && (uintptr_t)a0.out % (a0.out_f32 ? 16 : 4) == 0 && (uintptr_t)a0.valid % 4 == 0;
+  const long frame = (long)a0.W * a0.H;
+  const int kSlice = 65535;  // grid z
+  for (int f0 = 0; f0 < a0.n; f0 += kSlice) {
+    WarpAffineArgs a = a0;
+    a.n = std::min(kSlice, a0.n - f0);
+    a.img += f0 * frame * a0.noc;
+    a.xf += 6 * (long)f0;
+    a.out = (char *)a0.out + f0 * frame * a0.noc * (a0.out_f32 ? 4 : 1);
+    if (a.valid) a.valid += f0 * frame;
+    pick_noc(a.noc, [&](auto NOC) {
+      pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {
+        using O = std::conditional_t<OT != 0, float, uint8_t>;
+        if (vec) k_warp_affine<O, NOC, 4><<<dim3(ceil_div(frame / 4, 256), 1, a.n), 256, 0, s>>>(a);
+        else k_warp_affine<O, NOC, 1><<<dim3(ceil_div(frame, 256), 1, a.n), 256, 0, s>>>(a);
       });
     });
   }

@@ -22,6 +22,7 @@
 
 #include "../../include/ofdis.h"
 #include "ofdis_internal.h"
+#include "ofdis_motion_host.h"
 
 using namespace ofdis;
 
@@ -44,7 +45,10 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     // the point tracker on full-resolution fields / on level grids
                                     "track", "track_level",
                                     // the temporal filter on full-resolution fields / on level grids
-                                    "tfilter", "tfilter_level"};
+                                    "tfilter", "tfilter_level",
+                                    // the motion fit on full-resolution fields / on level grids, the path kernel
+                                    // and the affine warp
+                                    "fit_motion", "fit_motion_level", "smooth_path", "warp_affine"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -115,7 +119,7 @@ struct ofdis_context {
   // payload of the call's family alone; the whole key is zeroed before it is filled and compared bytewise, padding
   // included, and the family tag keeps the keys of two families apart whatever their payloads hold.
   struct GraphKey {
-    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter };
+    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter, kStab };
     // run_batch: ofdis_run_batch_u8*, bidir, stereo, sequence, the formatted calls and ofdis_run_warp_u8
     struct Batch {
       const void *flow_bw, *occ_fw, *occ_bw, *err_fw, *err_bw;  // the bidirectional / stereo call's extra outputs,
@@ -147,6 +151,14 @@ struct ofdis_context {
       int f32;
       float sigma, alpha, beta;
     };
+    // run_batch_stabilize: the picture, its dtype and mask, where the transforms and supports go (the caller's arrays
+    // or their place in the context's buffer), the fit's and the path's scalars; with use_fb the thresholds
+    struct Stab {
+      const void *picture, *valid, *xform, *corr, *support;
+      int f32, model, step, iters, use_fb, radius;
+      float alpha, beta;
+      double tau, zoom;
+    };
     int family;
     int n, w, h;
     int seq, stride;  // a sequence call: `a` is one array of n + stride frames
@@ -158,6 +170,7 @@ struct ofdis_context {
       Interp interp;
       Track track;
       Tfilter tfilter;
+      Stab stab;
     } u;
   } gkey{};
   hipGraphExec_t gexec = nullptr;
@@ -2612,6 +2625,279 @@ int ofdis_run_sequence_tfilter_u8_host(ofdis_context *c, const uint8_t *frames, 
   return rc;
 }
 
+// ------------------------------------------------------------------ global motion and stabilisation (include/ofdis.h)
+
+static_assert(OFDIS_FIT_MAX_SAMPLES == kFitMaxSamples && OFDIS_FIT_MAX_SAMPLES == kMotionMaxSamples &&
+                  OFDIS_FIT_LANES == kFitLanes && kFitMaxIters == kMotionMaxIters,
+              "the header's limits are the kernel's and the host helpers'");
+static_assert(OFDIS_MOTION_TRANSLATION == 0 && OFDIS_MOTION_SIMILARITY == 1, "fit_scalars_ok takes the enum's values");
+
+namespace {
+// The scalars and outputs of a fit (ofdis_fit_motion, ofdis_run_sequence_stabilize_u8).
+struct FitIo {
+  int model = 0, step = 0, iters = 0;
+  double tau = 0.0;
+  bool use_fb = false;
+  float alpha = 0.f, beta = 0.f;
+  double *xform = nullptr;
+  int32_t *support = nullptr;
+  float *weights = nullptr;
+};
+
+// What every fitting call checks of its size, scalars and thresholds; L: the lattice.
+bool fit_io_ok(const FitIo &io, int width, int height, FitLattice &L) {
+  return width > 0 && height > 0 && (long)width * height <= 0x7fffffffL && fit_scalars_ok(io.model, io.tau, io.iters) &&
+         fit_lattice(width, height, io.step, L) && (!io.use_fb || fb_thresholds_ok(io.alpha, io.beta));
+}
+
+// The m fields of view v fitted (timer "fit_motion_level" for a level-grid view, else "fit_motion").
+int run_fit(ofdis_context *c, const void *fw, const void *bw, const ofdis_flow_view &v, int m, int width, int height,
+            const FitIo &io, const FitLattice &L, hipStream_t s) {
+  FitArgs fa{};
+  fa.fw = fw;
+  fa.bw = bw;
+  fa.xform = io.xform;
+  fa.support = io.support;
+  fa.weights = io.weights;
+  fa.m = m;
+  fa.W = width;
+  fa.H = height;
+  fa.similarity = io.model == OFDIS_MOTION_SIMILARITY;
+  fa.step = io.step;
+  fa.half = L.half;
+  fa.sx = L.sx;
+  fa.sy = L.sy;
+  fa.ns = L.ns;
+  fa.iters = io.iters;
+  fit_inv_table(io.tau, io.iters, fa.inv);
+  fa.alpha = io.alpha;
+  fa.beta = io.beta;
+  fa.f16 = v.dtype == OFDIS_OUT_F16;
+  fa.planar = v.layout == OFDIS_OUT_PLANAR;
+  fa.level = v.grid == OFDIS_OUT_LEVEL;
+  if (fa.level) {
+    fa.gw = v.gw;
+    fa.gh = v.gh;
+    fa.offx = v.off_x;
+    fa.offy = v.off_y;
+    while ((1 << fa.log2c) < v.cell) ++fa.log2c;
+  }
+  timed(c, fa.level ? 30 : 29, s, [&] { launch_fit_motion(fa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// The m pair transforms to m + 1 corrections; chain: (m + 1) * 6 doubles of scratch.
+int run_path(ofdis_context *c, const double *xform, int m, int radius, double zoom, int width, int height, double *corr,
+             double *chain, hipStream_t s) {
+  PathArgs pa{};
+  pa.xform = xform;
+  pa.corr = corr;
+  pa.chain = chain;
+  pa.m = m;
+  pa.radius = radius;
+  pa.W = width;
+  pa.H = height;
+  pa.z = 1.0 / zoom;
+  timed(c, 31, s, [&] { launch_smooth_path(pa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// What the affine warp checks of its frames and picture: ofdis_warp_u8's rules, and no overlap (a frame's taps are read
+// while other pixels of it are written).
+bool warp_affine_ok(const uint8_t *img, int n, int width, int height, int noc, int out_dtype, const void *out) {
+  if (!img || !out || n < 1 || width <= 0 || height <= 0 || (noc != 1 && noc != 3) || !img_dtype_ok(out_dtype) ||
+      (long)width * height > 0x7fffffffL)
+    return false;
+  const size_t in = (size_t)n * width * height * noc, outb = in * (out_dtype == OFDIS_IMG_F32 ? 4 : 1);
+  const uintptr_t f = (uintptr_t)img, o = (uintptr_t)out;
+  return f + in <= o || o + outb <= f;
+}
+
+int run_warp_affine(ofdis_context *c, const uint8_t *img, int n, int width, int height, int noc, const double *xf,
+                    int f32, void *out, uint8_t *valid, hipStream_t s) {
+  WarpAffineArgs wa{};
+  wa.img = img;
+  wa.xf = xf;
+  wa.out = out;
+  wa.valid = valid;
+  wa.n = n;
+  wa.W = width;
+  wa.H = height;
+  wa.noc = noc;
+  wa.out_f32 = f32;
+  timed(c, 32, s, [&] { launch_warp_affine(wa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// The path's and the picture's side of a stabilising call.
+struct StabIo {
+  FitIo fit;
+  int radius = 0;
+  double zoom = 1.0;
+  int f32 = 0;
+  void *out = nullptr;
+  uint8_t *valid = nullptr;
+  double *corr = nullptr;
+};
+
+// ofdis_run_sequence_stabilize_u8 on stream s (no stage capture is set): run_batch_track's plan; the m forward level
+// grids in the context's buffer, with use_fb the m backward ones, and behind them the transforms the caller did not ask
+// for (pair transforms, corrections, supports) and the path's chain.  Every chunk writes its share of the grids; after
+// the chunks three launches on s: the fit over all pairs, the path, the affine warp over all frames.
+int run_batch_stabilize(ofdis_context *c, hipStream_t s, const uint8_t *frames, int m, int width, int height,
+                        const ofdis_params *p, const StabIo &io, const FitLattice &L) {
+  CallPlan cp;
+  int rc = prepare(c, p, m, width, height, false, false, cp, io.fit.use_fb ? 1 : 0, 1);
+  if (rc) return rc;
+  const ofdis_flow_view v = level_view(first_plan(cp));
+  cp.out_pair = level_grid_bytes(first_plan(cp));
+  const size_t grid_bytes = align_up((io.fit.use_fb ? 2 : 1) * (size_t)m * cp.out_pair);
+  const size_t xf_bytes = align_up((size_t)m * 48), corr_bytes = align_up((size_t)(m + 1) * 48);
+  if ((rc = ensure_warp_buf(c, grid_bytes + xf_bytes + 2 * corr_bytes + align_up((size_t)m * 4)))) return rc;  // (drops the graph before it grows)
+  char *grids = c->warp_buf, *grids_bw = io.fit.use_fb ? grids + (size_t)m * cp.out_pair : nullptr;
+  char *tail = c->warp_buf + grid_bytes;
+  StabIo q = io;  // the call's own arrays where the caller gives none
+  if (!q.fit.xform) q.fit.xform = (double *)tail;
+  if (!q.corr) q.corr = (double *)(tail + xf_bytes);
+  double *chain = (double *)(tail + xf_bytes + corr_bytes);
+  if (!q.fit.support) q.fit.support = (int32_t *)(tail + xf_bytes + 2 * corr_bytes);
+  GraphKey key = graph_key(GraphKey::kStab, c, frames, nullptr, nullptr, grids, grids, m, width, height, 1, p);
+  GraphKey::Stab &ks = key.u.stab;
+  ks.picture = q.out; ks.valid = q.valid; ks.xform = q.fit.xform; ks.corr = q.corr; ks.support = q.fit.support;
+  ks.f32 = q.f32; ks.model = q.fit.model; ks.step = q.fit.step; ks.iters = q.fit.iters; ks.radius = q.radius;
+  ks.tau = q.fit.tau; ks.zoom = q.zoom;
+  if (q.fit.use_fb) {
+    ks.use_fb = 1; ks.alpha = q.fit.alpha; ks.beta = q.fit.beta;
+  }
+  const size_t in_frame = (size_t)width * height * p->noc;
+  return replay_or_record(c, s, cp, key, [&](hipStream_t g) {
+    int err = for_each_chunk(c, cp, g, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      return run_chunk_grids(c, ws, P, p, frames + f0 * in_frame, nullptr, grids + f0 * cp.out_pair,
+                             grids_bw ? grids_bw + f0 * cp.out_pair : nullptr, ls);
+    });
+    if (err) return err;
+    if ((err = run_fit(c, grids, grids_bw, v, m, width, height, q.fit, L, g))) return err;
+    if ((err = run_path(c, q.fit.xform, m, q.radius, q.zoom, width, height, q.corr, chain, g))) return err;
+    return run_warp_affine(c, frames, m + 1, width, height, p->noc, q.corr, q.f32, q.out, q.valid, g);
+  });
+}
+}  // namespace
+
+int ofdis_fit_motion(ofdis_context *c, const void *flow_fw, const void *flow_bw, const ofdis_flow_view *v, int m,
+                     int width, int height, int model, int step, double tau, int iters, float alpha, float beta,
+                     double *xform, int32_t *support, float *weights, void *stream) {
+  FitIo io;
+  io.model = model;
+  io.step = step;
+  io.tau = tau;
+  io.iters = iters;
+  io.use_fb = flow_bw != nullptr;
+  io.alpha = alpha;
+  io.beta = beta;
+  io.xform = xform;
+  io.support = support;
+  io.weights = weights;
+  FitLattice L;
+  if (!c || !flow_fw || !v || !xform || m < 1 || !fit_io_ok(io, width, height, L)) return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->grid == OFDIS_OUT_LEVEL && (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED))
+    return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_track_points)
+  if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  return device_call(c, stream, false,
+                     [&](hipStream_t s) { return run_fit(c, flow_fw, flow_bw, *v, m, width, height, io, L, s); });
+}
+
+int ofdis_smooth_path(ofdis_context *c, const double *xform, int m, int radius, double zoom, int width, int height,
+                      double *corr, void *stream) {
+  if (!c || !xform || !corr || !path_scalars_ok(m, radius, zoom, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    const int rc = ensure_ws(c, (size_t)(m + 1) * 48);  // the chain (the workspace is this call's until call_end)
+    return rc ? rc : run_path(c, xform, m, radius, zoom, width, height, corr, (double *)c->ws, s);
+  });
+}
+
+int ofdis_warp_affine_u8(ofdis_context *c, const uint8_t *img, int n, int width, int height, int noc, const double *xf,
+                         int out_dtype, void *out, uint8_t *valid, void *stream) {
+  if (!c || !xf || !warp_affine_ok(img, n, width, height, noc, out_dtype, out)) return OFDIS_ERR_INVALID_ARGUMENT;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_warp_affine(c, img, n, width, height, noc, xf, out_dtype == OFDIS_IMG_F32, out, valid, s);
+  });
+}
+
+int ofdis_run_sequence_stabilize_u8(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                    const ofdis_params *p, int model, int step, double tau, int iters, int use_fb,
+                                    float alpha, float beta, int radius, double zoom, int out_dtype, void *out,
+                                    uint8_t *valid, double *xform, double *corr, int32_t *support, void *stream) {
+  StabIo io;
+  io.fit.model = model;
+  io.fit.step = step;
+  io.fit.tau = tau;
+  io.fit.iters = iters;
+  io.fit.use_fb = use_fb != 0;
+  io.fit.alpha = alpha;
+  io.fit.beta = beta;
+  io.fit.xform = xform;
+  io.fit.support = support;
+  io.radius = radius;
+  io.zoom = zoom;
+  io.f32 = out_dtype == OFDIS_IMG_F32;
+  io.out = out;
+  io.valid = valid;
+  io.corr = corr;
+  FitLattice L;
+  if (!c || !p || nframes < 2 || !warp_affine_ok(frames, nframes, width, height, p->noc, out_dtype, out) ||
+      !fit_io_ok(io.fit, width, height, L) || !path_scalars_ok(nframes - 1, radius, zoom, width, height))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
+  return device_call(c, stream, true, [&](hipStream_t s) {
+    return run_batch_stabilize(c, s, frames, nframes - 1, width, height, p, io, L);
+  });
+}
+
+int ofdis_run_sequence_stabilize_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                         const ofdis_params *p, int model, int step, double tau, int iters, int use_fb,
+                                         float alpha, float beta, int radius, double zoom, int out_dtype, void *out,
+                                         uint8_t *valid, double *xform, double *corr, int32_t *support) {
+  if (!c || !frames || !p || !out || nframes < 2 || width <= 0 || height <= 0 || !img_dtype_ok(out_dtype) ||
+      (p->noc != 1 && p->noc != 3))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)nframes * width * height, in = px * p->noc, outb = in * (out_dtype == OFDIS_IMG_F32 ? 4 : 1);
+  const size_t m = (size_t)nframes - 1;
+  // one device block: the frames, the picture, the mask, the transforms, the corrections, the supports (each at a
+  // multiple of 256 bytes)
+  const size_t off_out = align_up(in), off_valid = off_out + align_up(outb), off_xf = off_valid + align_up(px);
+  const size_t off_corr = off_xf + align_up(m * 48), off_sup = off_corr + align_up((m + 1) * 48);
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_sup + align_up(m * 4)));
+  int rc = OFDIS_OK;
+  auto step_ok = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  if (step_ok(hipMemcpyAsync(d, frames, in, hipMemcpyHostToDevice, c->stream))) {
+    rc = ofdis_run_sequence_stabilize_u8(c, (const uint8_t *)d, nframes, width, height, p, model, step, tau, iters, use_fb,
+                                         alpha, beta, radius, zoom, out_dtype, d + off_out,
+                                         valid ? (uint8_t *)(d + off_valid) : nullptr,
+                                         xform ? (double *)(d + off_xf) : nullptr, corr ? (double *)(d + off_corr) : nullptr,
+                                         support ? (int32_t *)(d + off_sup) : nullptr, c->stream);
+    if (rc == OFDIS_OK && step_ok(hipStreamSynchronize(c->stream))) {
+      step_ok(hipMemcpy(out, d + off_out, outb, hipMemcpyDeviceToHost));
+      if (valid) step_ok(hipMemcpy(valid, d + off_valid, px, hipMemcpyDeviceToHost));
+      if (xform) step_ok(hipMemcpy(xform, d + off_xf, m * 48, hipMemcpyDeviceToHost));
+      if (corr) step_ok(hipMemcpy(corr, d + off_corr, (m + 1) * 48, hipMemcpyDeviceToHost));
+      if (support) step_ok(hipMemcpy(support, d + off_sup, m * 4, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -2804,6 +3090,18 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   // two float32 flow views -- 16 bytes per pixel, or the two level grids
   if (k == "tfilter") b = (double)width * height * (16.0 + 4.0 * noc + 1.0);
   if (k == "tfilter_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * (4.0 * noc + 1.0);
+  // the motion fit per pair at the default lattice (step 16), in "track"'s convention (the check's gather not
+  // counted): 8 bytes per sample of a full-resolution float32 view; of a level grid the up to nine 8-byte cells a
+  // sample's expansion reads.  The path kernel moves 6 doubles per pair in and per frame out (charged per pair)
+  {
+    FitLattice L;
+    const double ns = fit_lattice(width, height, 16, L) ? (double)L.ns : 0.0;
+    if (k == "fit_motion") b = ns * 8.0;
+    if (k == "fit_motion_level") b = ns * 9.0 * 8.0;
+  }
+  if (k == "smooth_path") b = 2.0 * 48.0;
+  // the affine warp per frame: image taps and u8 picture (noc each) and the mask byte per pixel, and its six doubles
+  if (k == "warp_affine") b = (double)width * height * (2.0 * noc + 1.0) + 48.0;
   *bytes = b;
   return OFDIS_OK;
 }

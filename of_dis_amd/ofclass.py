@@ -14,8 +14,9 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, IMG_F32, IMG_U8, MODE_DE, MODE_OF, TRACK_LAST, FlowView,
-                   OfdisError, OutFormat, Params, check, lib, out_format)
+from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, FIT_MAX_SAMPLES, IMG_F32, IMG_U8, MODE_DE, MODE_OF,
+                   MOTION_SIMILARITY, MOTION_TRANSLATION, TRACK_LAST, FlowView, OfdisError, OutFormat, Params, check, lib,
+                   out_format)
 
 _f32 = np.float32
 
@@ -1085,6 +1086,190 @@ class Context:
               "ofdis_run_sequence_tfilter_u8_host")
         return (out, used) if want_used else out
 
+    def fit_motion_ptr(self, fw_ptr: int, bw_ptr: int, view: FlowView, m: int, width: int, height: int, model: int,
+                       step: int, tau: float, iters: int, xform_ptr: int, support_ptr: int = 0, weights_ptr: int = 0,
+                       alpha: float = 0.01, beta: float = 0.5, stream: int = 0) -> None:
+        """``ofdis_fit_motion`` on raw device pointers (0: no backward chain / that output is not wanted)."""
+        check(lib().ofdis_fit_motion(self._h, fw_ptr or None, bw_ptr or None, None if view is None else C.byref(view),
+                                     m, width, height, model, step, tau, iters, alpha, beta, xform_ptr or None,
+                                     support_ptr or None, weights_ptr or None, stream or None), "ofdis_fit_motion")
+
+    def fit_motion(self, flow_fw, flow_bw=None, model: int = MOTION_SIMILARITY, step: int = 16, tau: float = 2.0,
+                   iters: int = 4, alpha: float = 0.01, beta: float = 0.5, layout: str = "nhwc", grid: str = "full",
+                   p: Optional[Params] = None, size=None, want_support: bool = False, want_weights: bool = False):
+        """The camera's motion per frame pair (the definition is in ofdis.h): a robust similarity (or translation)
+        fitted to each of the m fields of flow_fw at the lattice ``fit_lattice(width, height, step)``, with Tukey-like
+        weights 1 - r^2 / t^2 annealed over `iters` re-solves down to the threshold tau (pixels).  flow_fw / flow_bw:
+        described as for ``track_points`` (grid "level" takes float32 "nhwc" grids and needs `p` and size = (width,
+        height)); with flow_bw a sample also has to pass the forward-backward check at alpha, beta.  Returns the
+        transforms, torch.float64 [m, 6] = (m00, m01, m02, m10, m11, m12) with position in frame j + 1 = M position in
+        frame j; with want_support also int32 [m], the samples with a positive weight; with want_weights also float32
+        [m, ns]."""
+        import torch
+        if not flow_fw.is_cuda or flow_fw.dim() != 4:
+            raise ValueError("expected the m fields of a chain as one CUDA tensor of four dimensions")
+        fmt = out_format(flow_fw.dtype, layout, grid)
+        m = flow_fw.shape[0]
+        if grid == "level":
+            if p is None or size is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'fit_motion: grid="level" needs the parameters the flows were '
+                                 "computed with and the frame size")
+            w, h = int(size[0]), int(size[1])
+        else:
+            h, w = (flow_fw.shape[2], flow_fw.shape[3]) if fmt.layout else (flow_fw.shape[1], flow_fw.shape[2])
+        ns = _motion_checks("fit_motion", w, h, model, step, tau, iters)
+        if grid == "level":
+            g = out_geometry(p, w, h, False, flow_fw.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        else:
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        want = (m, 2, view.gh, view.gw) if fmt.layout else (m, view.gh, view.gw, 2)
+        if tuple(flow_fw.shape) != want:
+            raise ValueError(f"flow_fw has shape {tuple(flow_fw.shape)}, expected {want}")
+        if flow_bw is not None and (tuple(flow_bw.shape) != want or flow_bw.dtype != flow_fw.dtype or not flow_bw.is_cuda):
+            raise ValueError(f"flow_bw must be a CUDA tensor of flow_fw's dtype and shape {want}")
+        flow_fw = flow_fw.contiguous()
+        flow_bw = flow_bw.contiguous() if flow_bw is not None else None
+        xform = torch.empty((m, 6), dtype=torch.float64, device=flow_fw.device)
+        support = torch.empty((m,), dtype=torch.int32, device=flow_fw.device) if want_support else None
+        weights = torch.empty((m, ns), dtype=torch.float32, device=flow_fw.device) if want_weights else None
+        self.fit_motion_ptr(flow_fw.data_ptr(), flow_bw.data_ptr() if flow_bw is not None else 0, view, m, w, h,
+                            int(model), int(step), float(tau), int(iters), xform.data_ptr(),
+                            support.data_ptr() if want_support else 0, weights.data_ptr() if want_weights else 0,
+                            alpha, beta, torch.cuda.current_stream(flow_fw.device).cuda_stream)
+        res = [xform] + ([support] if want_support else []) + ([weights] if want_weights else [])
+        return tuple(res) if len(res) > 1 else xform
+
+    def smooth_path_ptr(self, xform_ptr: int, m: int, radius: int, zoom: float, width: int, height: int, corr_ptr: int,
+                        stream: int = 0) -> None:
+        """``ofdis_smooth_path`` on raw device pointers."""
+        check(lib().ofdis_smooth_path(self._h, xform_ptr or None, m, radius, zoom, width, height, corr_ptr or None,
+                                      stream or None), "ofdis_smooth_path")
+
+    def smooth_path(self, xform, size, radius: int = 8, zoom: float = 1.0):
+        """The m pair transforms of ``fit_motion`` (torch.float64 CUDA tensor [m, 6]) to the m + 1 per-frame correction
+        transforms of a stabilised video of size = (width, height): the cumulative camera path, smoothed with a
+        triangular window of `radius` frames either side, and per frame the transform from the smoothed to the real
+        path, zoomed in by `zoom` about the frame centre.  Returns torch.float64 [m + 1, 6] for ``warp_affine``."""
+        import torch
+        if not xform.is_cuda or xform.dim() != 2 or xform.shape[1] != 6 or xform.dtype != torch.float64:
+            raise ValueError("expected a float64 CUDA tensor of transforms [m, 6]")
+        m, w, h = xform.shape[0], int(size[0]), int(size[1])
+        _path_checks("smooth_path", m, radius, zoom, w, h)
+        xform = xform.contiguous()
+        corr = torch.empty((m + 1, 6), dtype=torch.float64, device=xform.device)
+        self.smooth_path_ptr(xform.data_ptr(), m, int(radius), float(zoom), w, h, corr.data_ptr(),
+                             torch.cuda.current_stream(xform.device).cuda_stream)
+        return corr
+
+    def warp_affine_ptr(self, img_ptr: int, n: int, width: int, height: int, noc: int, xf_ptr: int, out_dtype: int,
+                        out_ptr: int, valid_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_warp_affine_u8`` on raw device pointers (valid_ptr 0: no mask); out_dtype IMG_U8 / IMG_F32."""
+        check(lib().ofdis_warp_affine_u8(self._h, img_ptr or None, n, width, height, noc, xf_ptr or None, out_dtype,
+                                         out_ptr or None, valid_ptr or None, stream or None), "ofdis_warp_affine_u8")
+
+    def warp_affine(self, img, xf, out_dtype=None, want_valid: bool = False):
+        """Each of n u8 frames (torch.uint8 CUDA tensor [n, h, w] or [n, h, w, 3]) pulled through its own transform xf
+        (torch.float64 CUDA tensor [n, 6]: output pixel (x, y) shows the input at M (x, y, 1)), with ``warp``'s
+        bilinear taps, replicated border and rounding.  Returns the frames in img's shape, torch.uint8 (the default) or
+        torch.float32; with want_valid the tuple (frames, valid uint8 [n, h, w])."""
+        import torch
+        if out_dtype not in (None, torch.uint8, torch.float32):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"warp_affine: out_dtype {out_dtype!r}")
+        i4 = img.unsqueeze(-1) if img.dim() == 3 else img
+        if i4.dim() != 4 or i4.shape[-1] not in (1, 3) or i4.dtype != torch.uint8 or not i4.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor [n, h, w] or [n, h, w, 3]")
+        n, h, w, noc = i4.shape
+        if not xf.is_cuda or tuple(xf.shape) != (n, 6) or xf.dtype != torch.float64:
+            raise ValueError(f"expected a float64 CUDA tensor of transforms [{n}, 6]")
+        f32 = out_dtype == torch.float32
+        i4, xf = i4.contiguous(), xf.contiguous()
+        out = torch.empty(img.shape, dtype=torch.float32 if f32 else torch.uint8, device=i4.device)
+        valid = torch.empty((n, h, w), dtype=torch.uint8, device=i4.device) if want_valid else None
+        self.warp_affine_ptr(i4.data_ptr(), n, w, h, noc, xf.data_ptr(), IMG_F32 if f32 else IMG_U8, out.data_ptr(),
+                             valid.data_ptr() if want_valid else 0, torch.cuda.current_stream(i4.device).cuda_stream)
+        return (out, valid) if want_valid else out
+
+    def run_sequence_stabilize_ptr(self, frames_ptr: int, nframes: int, width: int, height: int, p: Params, model: int,
+                                   step: int, tau: float, iters: int, radius: int, zoom: float, out_dtype: int,
+                                   out_ptr: int, valid_ptr: int = 0, xform_ptr: int = 0, corr_ptr: int = 0,
+                                   support_ptr: int = 0, fb: bool = False, alpha: float = 0.01, beta: float = 0.5,
+                                   stream: int = 0) -> None:
+        """``ofdis_run_sequence_stabilize_u8`` on raw device pointers, asynchronous on `stream`: frames u8
+        [nframes, h, w, noc] -> the stabilised frames (0: that optional output is not wanted)."""
+        check(lib().ofdis_run_sequence_stabilize_u8(self._h, frames_ptr or None, nframes, width, height, C.byref(p), model,
+                                                    step, tau, iters, int(bool(fb)), alpha, beta, radius, zoom, out_dtype,
+                                                    out_ptr or None, valid_ptr or None, xform_ptr or None,
+                                                    corr_ptr or None, support_ptr or None, stream or None),
+              "ofdis_run_sequence_stabilize_u8")
+
+    def run_sequence_stabilize(self, frames, p: Params, model: int = MOTION_SIMILARITY, step: int = 16, tau: float = 2.0,
+                               iters: int = 4, fb: bool = False, alpha: float = 0.01, beta: float = 0.5,
+                               radius: int = 8, zoom: float = 1.0, out_dtype=None, want_valid: bool = False,
+                               want_path: bool = False):
+        """The flows of a video, its camera path and the stabilised frames in one call: torch.uint8 CUDA tensor
+        [T, h, w] or [T, h, w, noc] -> the stabilised frames in that shape (torch.uint8, or torch.float32).  Bit for bit
+        ``warp_affine(frames, smooth_path(fit_motion(F, B if fb else None, ...), size, radius, zoom))`` on
+        ``run_sequence(frames, p, bidir=True)``'s flows -- but the flows stay on their level grids, the check runs at
+        the fit's samples alone and no full-resolution flow or mask is written.  want_valid adds valid uint8 [T, h, w];
+        want_path adds (xform float64 [T - 1, 6], corr float64 [T, 6], support int32 [T - 1])."""
+        import torch
+        if out_dtype not in (None, torch.uint8, torch.float32):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_sequence_stabilize: out_dtype {out_dtype!r}")
+        f4 = frames.unsqueeze(-1) if frames.dim() == 3 else frames
+        if f4.dim() != 4 or f4.shape[-1] != p.noc or f4.dtype != torch.uint8 or not f4.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor with noc channels")
+        t, h, w, _ = f4.shape
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_stabilize: a video needs two frames or more")
+        _motion_checks("run_sequence_stabilize", w, h, model, step, tau, iters)
+        _path_checks("run_sequence_stabilize", t - 1, radius, zoom, w, h)
+        f32 = out_dtype == torch.float32
+        f4 = f4.contiguous()
+        dev = f4.device
+        out = torch.empty(frames.shape, dtype=torch.float32 if f32 else torch.uint8, device=dev)
+        valid = torch.empty((t, h, w), dtype=torch.uint8, device=dev) if want_valid else None
+        xform = torch.empty((t - 1, 6), dtype=torch.float64, device=dev) if want_path else None
+        corr = torch.empty((t, 6), dtype=torch.float64, device=dev) if want_path else None
+        support = torch.empty((t - 1,), dtype=torch.int32, device=dev) if want_path else None
+        self.run_sequence_stabilize_ptr(f4.data_ptr(), t, w, h, p, int(model), int(step), float(tau), int(iters),
+                                        int(radius), float(zoom), IMG_F32 if f32 else IMG_U8, out.data_ptr(),
+                                        valid.data_ptr() if want_valid else 0, xform.data_ptr() if want_path else 0,
+                                        corr.data_ptr() if want_path else 0, support.data_ptr() if want_path else 0,
+                                        fb, alpha, beta, torch.cuda.current_stream(dev).cuda_stream)
+        res = [out] + ([valid] if want_valid else []) + ([xform, corr, support] if want_path else [])
+        return tuple(res) if len(res) > 1 else out
+
+    def run_sequence_stabilize_host(self, frames: np.ndarray, p: Params, model: int = MOTION_SIMILARITY, step: int = 16,
+                                    tau: float = 2.0, iters: int = 4, fb: bool = False, alpha: float = 0.01,
+                                    beta: float = 0.5, radius: int = 8, zoom: float = 1.0, out_dtype=np.uint8,
+                                    want_valid: bool = False, want_path: bool = False):
+        """run_sequence_stabilize on a numpy u8 array [T, h, w] or [T, h, w, noc]; synchronous."""
+        if out_dtype is not None and np.dtype(out_dtype) not in (np.dtype(np.uint8), np.dtype(_f32)):
+            raise OfdisError(ERR_INVALID_ARGUMENT, f"run_sequence_stabilize_host: out_dtype {out_dtype!r}")
+        f4 = np.ascontiguousarray(frames[..., None] if frames.ndim == 3 else frames, np.uint8)
+        if f4.ndim != 4 or f4.shape[-1] != p.noc:
+            raise ValueError("expected a uint8 array with noc channels")
+        t, h, w = f4.shape[:3]
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_stabilize_host: a video needs two frames or more")
+        _motion_checks("run_sequence_stabilize_host", w, h, model, step, tau, iters)
+        _path_checks("run_sequence_stabilize_host", t - 1, radius, zoom, w, h)
+        f32 = out_dtype is not None and np.dtype(out_dtype) == _f32
+        out = np.empty(frames.shape, _f32 if f32 else np.uint8)
+        valid = np.empty((t, h, w), np.uint8) if want_valid else None
+        xform = np.empty((t - 1, 6), np.float64) if want_path else None
+        corr = np.empty((t, 6), np.float64) if want_path else None
+        support = np.empty((t - 1,), np.int32) if want_path else None
+        check(lib().ofdis_run_sequence_stabilize_u8_host(
+            self._h, f4.ctypes.data, t, w, h, C.byref(p), int(model), int(step), float(tau), int(iters), int(bool(fb)),
+            alpha, beta, int(radius), float(zoom), IMG_F32 if f32 else IMG_U8, out.ctypes.data,
+            valid.ctypes.data if want_valid else None, xform.ctypes.data if want_path else None,
+            corr.ctypes.data if want_path else None, support.ctypes.data if want_path else None),
+            "ofdis_run_sequence_stabilize_u8_host")
+        res = [out] + ([valid] if want_valid else []) + ([xform, corr, support] if want_path else [])
+        return tuple(res) if len(res) > 1 else out
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
@@ -1170,6 +1355,46 @@ def pixel_grid(width: int, height: int, step: int = 1) -> np.ndarray:
     return np.ascontiguousarray(np.stack(np.meshgrid(xs, ys), axis=-1).reshape(-1, 2))
 
 
+def fit_lattice(width: int, height: int, step: int = 16) -> np.ndarray:
+    """The pixels (x, y) at which ``fit_motion`` samples a width x height field, row-major: int32 [ns, 2] -- columns
+    step // 2 + i * step below width, rows likewise.  Raises OfdisError(INVALID_ARGUMENT) for a size or step the
+    library refuses (a first sample outside the frame, more than FIT_MAX_SAMPLES samples)."""
+    width, height, step = int(width), int(height), int(step)
+    if width < 1 or height < 1 or step < 1 or step // 2 > min(width, height) - 1:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"fit_lattice: size {(width, height)} at step {step}")
+    half = step // 2
+    xs, ys = np.arange(half, width, step, dtype=np.int32), np.arange(half, height, step, dtype=np.int32)
+    if xs.size * ys.size > FIT_MAX_SAMPLES:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"fit_lattice: {xs.size * ys.size} samples, the most is {FIT_MAX_SAMPLES}")
+    return np.ascontiguousarray(np.stack(np.meshgrid(xs, ys), axis=-1).reshape(-1, 2))
+
+
+def _motion_checks(what: str, width: int, height: int, model, step, tau, iters) -> int:
+    """What the fitting calls refuse of their scalars, before any library call (ofdis_fit_motion's rules); returns the
+    number of samples."""
+    if model not in (MOTION_TRANSLATION, MOTION_SIMILARITY):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: model {model!r}")
+    t = float(tau)
+    if not (np.isfinite(t) and 1.0 / 1024.0 <= t <= 65536.0):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: tau {tau!r} is not in [1/1024, 65536]")
+    if int(iters) != iters or not 0 <= iters <= 16:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: iters {iters!r} is not in 0..16")
+    if int(step) != step:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: step {step!r}")
+    return fit_lattice(width, height, step).shape[0]
+
+
+def _path_checks(what: str, m: int, radius, zoom, width: int, height: int) -> None:
+    """What the path calls refuse of their scalars, before any library call (ofdis_smooth_path's rules)."""
+    if m < 1 or width < 1 or height < 1:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: {m} transforms of a {width} x {height} frame")
+    if int(radius) != radius or not 0 <= radius <= 256:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: radius {radius!r} is not in 0..256")
+    z = float(zoom)
+    if not (np.isfinite(z) and 1.0 <= z <= 16.0):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: zoom {zoom!r} is not in [1, 16]")
+
+
 def write_pnm(path: str, pixels: np.ndarray) -> None:
     """Binary PGM (u8 [h, w] or [h, w, 1]) / PPM (u8 [h, w, 3] in BGR order, written as RGB)."""
     pixels = np.ascontiguousarray(pixels, np.uint8)
@@ -1196,5 +1421,5 @@ def algorithmic_bytes(p: Params, width: int, height: int, kernel: str) -> float:
 
 __all__ = ["OFClass", "Context", "Params", "oppoint", "params_from_strings", "validate", "synth_pair", "synth_shift_pair",
            "write_flo", "write_pfm", "write_pnm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
-           "max_frames_per_launch", "out_geometry", "pixel_grid",
-           "MODE_OF", "MODE_DE"]
+           "max_frames_per_launch", "out_geometry", "pixel_grid", "fit_lattice",
+           "MODE_OF", "MODE_DE", "MOTION_TRANSLATION", "MOTION_SIMILARITY"]
