@@ -85,7 +85,15 @@ int ofdis_params_from_strings(ofdis_params *p, int count, const char *const *val
 
 /* Validation the reference never does: p even and >= 2, p*p*noc divisible by 4 (patch.cpp:230),
  * 0 <= sc_l <= sc_f, width/height divisible by 2^sc_f, costfct in {0,1,2}, noc in {1,3}, gradmag only
- * with noc = 1. */
+ * with noc = 1.
+ * With usetvref set, OFDIS_ERR_INVALID_ARGUMENT for the TV values under which the refinement is undefined
+ * (DESIGN.md section 5): tv_alpha that is not a finite number above 0, tv_gamma or tv_delta that is not a finite
+ * number >= 0, a tv_sor that is not finite.  Without a positive smoothness weight and non-negative data weights the
+ * 2x2 system of a pixel (solver.c:122-128) has no inverse wherever the warp mask or the image gradients are zero;
+ * its 0 / 0 spreads through the level, and the reference then takes (int)ceil(NaN) as a patch position
+ * (patch.cpp:345-350).  Zero tv_gamma or tv_delta, any finite tv_sor and zero tv_solverit / tv_innerit are defined.
+ * Finite weights so extreme that a system overflows or underflows in float (tv_alpha 1e-25, tv_gamma 1e30) end
+ * the same way; that depends on the images, and they are not refused. */
 int ofdis_params_validate(const ofdis_params *p, int width, int height, int imgpadding);
 
 /* ------------------------------------------------------------------ library boundary */

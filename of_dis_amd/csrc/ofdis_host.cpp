@@ -112,6 +112,14 @@ int ofdis_params_validate(const ofdis_params *p, int width, int height, int imgp
   if (p->max_iter < 0 || p->min_iter < 0 || p->tv_innerit < 0 || p->tv_solverit < 0)
     return OFDIS_ERR_INVALID_ARGUMENT;
   if (!(p->patove >= 0.0f && p->patove < 1.0f)) return OFDIS_ERR_INVALID_ARGUMENT;
+  if (p->usetvref) {
+    // the systems of the refinement have no inverse without these: NaN flow, which the next
+    // level's patch sampling would take as a position
+    if (!std::isfinite(p->tv_alpha) || !(p->tv_alpha > 0.0f)) return OFDIS_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(p->tv_gamma) || !(p->tv_gamma >= 0.0f)) return OFDIS_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(p->tv_delta) || !(p->tv_delta >= 0.0f)) return OFDIS_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(p->tv_sor)) return OFDIS_ERR_INVALID_ARGUMENT;
+  }
   if (width > 0 && height > 0) {
     const int d = 1 << p->sc_f;
     if ((width % d) || (height % d)) return OFDIS_ERR_INVALID_ARGUMENT;

@@ -309,6 +309,13 @@ static long g_patch_stats[ST_N];
 void ofo_patch_stats_reset(void) { memset(g_patch_stats, 0, sizeof g_patch_stats); }
 void ofo_patch_stats_get(long out[8]) { memcpy(out, g_patch_stats, sizeof g_patch_stats); }
 
+/* Why the stopping test of patch_err said stop (TEST INFRASTRUCTURE, as above; ofdis_oracle.h lists the slots). */
+enum { SR_STARTED, SR_STOP_CNT0, SR_STOP_MAXITER, SR_RES, SR_DP, SR_DR, SR_RES_CNT0, SR_RATE_FIRST, SR_PAST_FIRST,
+       SR_N };
+static long g_stop_stats[SR_N];
+void ofo_stop_stats_reset(void) { memset(g_stop_stats, 0, sizeof g_stop_stats); }
+void ofo_stop_stats_get(long out[9]) { memcpy(out, g_stop_stats, sizeof g_stop_stats); }
+
 /* Eigen LLT<2x2>.solve (unblocked llt_inplace + unrolled triangular solves). */
 static void llt2_solve(float H00, float H01, float H11, float b0, float b1, float *x0, float *x1) {
   float L00 = H00, L10 = H01, L11 = H11;
@@ -405,12 +412,24 @@ static void patch_err(const cam_t *c, const opt_t *o, const float *im_b, patch_t
   /* lpNorm<1> = cwiseAbs().sum() (into the pdiff-sized scratch, no allocation per iteration) */
   for (int i = 0; i < o->novals; ++i) P->scratch[i] = fabsf(P->pweight[i]);
   P->mares = ofo_eigen_sum(P->scratch, o->novals) / (float)o->novals;
-  int keep = (P->cnt < o->max_iter) & (P->mares > o->res_thresh) &
-             ((P->cnt < o->min_iter) | (P->sq / P->sq_init >= o->dp_thresh_sq)) &
-             ((P->cnt < o->min_iter) | (P->mares / P->mares_old <= o->dr_thresh));
+  if (P->cnt == o->min_iter + 1) g_stop_stats[SR_PAST_FIRST]++;
+  const int t_it = P->cnt < o->max_iter, t_res = P->mares > o->res_thresh;
+  const int t_dp = (P->cnt < o->min_iter) | (P->sq / P->sq_init >= o->dp_thresh_sq);
+  const int t_dr = (P->cnt < o->min_iter) | (P->mares / P->mares_old <= o->dr_thresh);
+  int keep = t_it & t_res & t_dp & t_dr;
   if (!keep) {
     P->converged = 1;
     if (P->cnt < o->max_iter) g_patch_stats[ST_EARLY_STOP]++;
+    if (P->cnt == 0) g_stop_stats[SR_STOP_CNT0]++;
+    if (!t_it) {
+      g_stop_stats[SR_STOP_MAXITER]++;
+    } else {
+      g_stop_stats[SR_RES] += !t_res;
+      g_stop_stats[SR_DP] += !t_dp;
+      g_stop_stats[SR_DR] += !t_dr;
+      if (P->cnt == 0) g_stop_stats[SR_RES_CNT0] += !t_res;
+      if (P->cnt == o->min_iter) g_stop_stats[SR_RATE_FIRST] += !t_dp | !t_dr;
+    }
   }
 }
 
@@ -490,6 +509,7 @@ static void patch_run(const cam_t *c, const opt_t *o, const float *im_a, const f
     P->mares = 1e5f;
     P->mares_old = (float)1e20;
     P->converged = 0;
+    g_stop_stats[SR_STARTED]++;
     patch_err(c, o, im_b, P);
   }
   /* OptimizeIter loop */

@@ -118,6 +118,17 @@ void ofo_sor_rb_de(float *du, const float *a11, const float *b1, const float *h,
 void ofo_patch_stats_reset(void);
 void ofo_patch_stats_get(long out[8]);
 
+/* Why patches stop, since the last reset (TEST INFRASTRUCTURE, unsynchronised like the counters above).  Counted in
+ * the stopping test of OptimizeComputeErrImg whenever it says stop, a patch that an outlier reset had already
+ * stopped included.  out[0..8]: started (patches whose start point is in bounds), stop_cnt0 (stops at cnt == 0, the
+ * evaluation of OptimizeStart), stop_max_iter (stops with cnt == max_iter), and among the stops with
+ * cnt < max_iter how often each term was the false one -- res (mares > res_thresh), dp (the step-size rate), dr (the
+ * residual rate); one stop may count under several -- then res_cnt0, the res stops at cnt == 0, and rate_first, the
+ * dp or dr stops at cnt == min_iter, the first iteration that evaluates the two rates, and past_first, the patches
+ * that iterate once more after it (evaluations with cnt == min_iter + 1). */
+void ofo_stop_stats_reset(void);
+void ofo_stop_stats_get(long out[9]);
+
 #ifdef __cplusplus
 }
 #endif

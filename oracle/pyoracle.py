@@ -90,6 +90,9 @@ def lib():
         L.ofo_patch_stats_reset.restype = None
         L.ofo_patch_stats_get.argtypes = [C.POINTER(C.c_long)]
         L.ofo_patch_stats_get.restype = None
+        L.ofo_stop_stats_reset.restype = None
+        L.ofo_stop_stats_get.argtypes = [C.POINTER(C.c_long)]
+        L.ofo_stop_stats_get.restype = None
         for f in ("ofo_params_oppoint", "ofo_build_pyramid", "ofo_build_pyramid_ex", "ofo_oflow", "ofo_upsample_crop", "ofo_run_u8",
                   "ofo_run_u8_init", "ofo_refine_level"):
             getattr(L, f).restype = C.c_int
@@ -128,6 +131,23 @@ def patch_stats() -> dict:
     out = (C.c_long * len(PATCH_STATS))()
     lib().ofo_patch_stats_get(out)
     return dict(zip(PATCH_STATS, (int(v) for v in out)))
+
+
+STOP_STATS = ("started", "stop_cnt0", "stop_max_iter", "res", "dp", "dr", "res_cnt0", "rate_first", "past_first")
+
+
+def stop_stats_reset() -> None:
+    lib().ofo_stop_stats_reset()
+
+
+def stop_stats() -> dict:
+    """Why patches stopped since stop_stats_reset() (ofdis_oracle.h): patches started in bounds, stops at cnt == 0
+    and at cnt == max_iter, and for the stops before max_iter how often each term of the stopping test was the
+    false one (res, dp, dr; res_cnt0: res at cnt == 0; rate_first: dp or dr at cnt == min_iter), and the patches
+    that went on past cnt == min_iter (past_first).  Unsynchronised, like patch_stats()."""
+    out = (C.c_long * len(STOP_STATS))()
+    lib().ofo_stop_stats_get(out)
+    return dict(zip(STOP_STATS, (int(v) for v in out)))
 
 
 def oppoint(op: int, width: int, mode: int = 1, noc: int = 1) -> Params:

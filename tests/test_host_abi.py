@@ -104,10 +104,41 @@ def test_params_from_strings_matches_readme_order():
     ({"patove": 1.0}, _lib.ERR_INVALID_ARGUMENT),
     ({"mode": 3}, _lib.ERR_INVALID_ARGUMENT),
     ({"noc": 2}, _lib.ERR_INVALID_ARGUMENT),
+    # TV values under which the refinement's systems have no inverse (ofdis.h)
+    ({"tv_alpha": 0.0}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_alpha": -0.0}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_alpha": -0.01}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_alpha": -10.0}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_alpha": float("nan")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_alpha": float("inf")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_alpha": float("-inf")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_gamma": -10.0}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_gamma": float("nan")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_gamma": float("inf")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_delta": -5.0}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_delta": float("nan")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_delta": float("inf")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_sor": float("nan")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_sor": float("inf")}, _lib.ERR_INVALID_ARGUMENT),
+    ({"tv_sor": float("-inf")}, _lib.ERR_INVALID_ARGUMENT),
 ])
 def test_validation_rejects(change, code):
     p = od.oppoint(2, 1920).copy(**change)
     assert od.validate(p, 1920, 1088, 8) == code
+    assert od.validate(p) == code
+
+
+@pytest.mark.parametrize("change", [
+    {"tv_alpha": 0.01}, {"tv_alpha": 25.0}, {"tv_gamma": 0.0}, {"tv_delta": 0.0}, {"tv_gamma": 0.0, "tv_delta": 0.0},
+    {"tv_gamma": -0.0}, {"tv_sor": 0.0}, {"tv_sor": -1.0}, {"tv_sor": 2.5}, {"tv_solverit": 0}, {"tv_innerit": 0},
+    {"res_thresh": 1e4}, {"max_iter": 0}, {"min_iter": 0}, {"min_iter": 9, "max_iter": 4},
+    # without the refinement the TV values are never read
+    {"usetvref": 0, "tv_alpha": 0.0}, {"usetvref": 0, "tv_sor": float("nan")},
+])
+def test_validation_accepts_the_defined_off_point_values(change):
+    """The refusals above take nothing that the reference defines: zero data weights, any finite relaxation factor,
+    zero sweep counts and every stopping parameter still validate."""
+    assert od.validate(od.oppoint(2, 1920).copy(**change), 1920, 1088, 8) == 0
 
 
 @pytest.mark.parametrize("noc", [1, 3])
