@@ -644,6 +644,72 @@ int ofdis_run_sequence_tfilter_u8_host(ofdis_context *ctx, const uint8_t *frames
                                        const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
                                        int out_dtype, void *out, uint8_t *used);
 
+/* ------------------------------------------------------------------ temporal denoising over a radius of frames
+ *
+ * Not in the reference.  ofdis_tfilter_u8 with up to R frames on each side instead of one: the position of a pixel is
+ * chained through the fields as ofdis_track_points chains a point, every frame it passes is sampled there and weighted
+ * as ofdis_tfilter_u8 weights its neighbours, and the forward-backward check runs inside the chain, step by step, so
+ * there are no mask inputs.
+ *
+ * ofdis_tfilter_radius_u8: frames, flow_fw, flow_bw, view, out and out_dtype are exactly ofdis_tfilter_u8's (a full view
+ * of any dtype and layout, or a level view, float32 interleaved only).  radius R in [1, 4].  used: u8
+ * [nframes][height][width] or NULL.  Occlusion handling is use_fb with alpha and beta.
+ *
+ * Definition, frame i, pixel (x, y); all arithmetic float32 in this order, every operation rounded on its own (no fused
+ * multiply-add), `/` the correctly rounded division.  inv, C, acc, wsum and bits start as in ofdis_tfilter_u8; S(G, px, py)
+ * and in(px, py) are ofdis_track_points's gather and predicate (in is false for NaN).  Two chains, the previous
+ * direction (d = 0) first, then the next (d = 1); in a direction k = 1 .. R while frame j exists:
+ *     previous: j = i - k >= 0;   step field F_k = flow_bw[j],    opposite field B_k = flow_fw[j]
+ *     next:     j = i + k <= T-1; step field F_k = flow_fw[j-1],  opposite field B_k = flow_bw[j-1]
+ *   start: P_0 = ((float)x, (float)y), alive, not failed
+ *   (fu, fv) = for k = 1 the pixel's own value of F_1 as the view defines it (exactly as ofdis_tfilter_u8 reads it);
+ *              for k >= 2 S(F_k, P_{k-1})
+ *   P_k = P_{k-1} + (fu, fv)                       one float add per component
+ *   if !in(P_k): the chain is dead -- this neighbour and every farther one of the direction contribute nothing, and
+ *                nothing further is read
+ *   with use_fb: (bu, bv) = S(B_k, P_k);  du = fu + bu;  dv = fv + bv;  err = du*du + dv*dv
+ *                mag = (fu*fu + fv*fv) + (bu*bu + bv*bv);  thr = alpha*mag + beta
+ *                failed = failed || !(err <= thr)      (a NaN fails; sticky along the chain; ofdis_track_points's step)
+ *   S[ch] = ofdis_warp_u8's val for image frames[j], pixel (0, 0), flow P_k, scale 1 -- the bilinear taps at the position
+ *           P_k itself (1 * p and 0 + p are p); for k = 1 this is ofdis_tfilter_u8's sample at (x + u, y + v)
+ *   ok = alive && !failed
+ *   d = |S[0] - C[0]|  (+ |S[1] - C[1]| + |S[2] - C[2]| in this order for noc = 3)
+ *   r = d * inv;   w = ok ? fmaxf(1 - r*r, 0) : 0
+ *   acc[ch] = acc[ch] + w * S[ch];   wsum = wsum + w;   if w > 0: bits |= 1 << (2 * (k - 1) + d)
+ *   val[ch] = acc[ch] / wsum;  the output conversions are ofdis_tfilter_u8's;  used = bits
+ * Without use_fb alpha and beta are ignored and flow_bw is read only as the previous direction's step fields.
+ * Consequences: val is always finite; identical frames with zero flows return the frames; positions never depend on the
+ * pictures, on sigma, on alpha and beta, or on the other direction; a failed step contributes a weight of 0 to every
+ * later step of its direction, which adds exact zeros, so an implementation may stop a chain there; R = 1 without use_fb
+ * is ofdis_tfilter_u8 without masks, bit for bit, `used` included; R = 1 with use_fb is ofdis_tfilter_u8 with the
+ * occ_fw / occ_bw of ofdis_fb_check(alpha, beta) on the same float32 fields (of ofdis_fb_check_level on the same
+ * grids), bit for bit; frames within R of an end have shorter chains.
+ * Refused before anything is enqueued (OFDIS_ERR_INVALID_ARGUMENT, the context stays usable): whatever ofdis_tfilter_u8
+ * refuses; radius outside [1, 4]; with use_fb, the threshold rules of ofdis_fb_check.  Stream and ordering rules are
+ * those of ofdis_tfilter_u8. */
+int ofdis_tfilter_radius_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, const void *flow_fw,
+                            const void *flow_bw, const ofdis_flow_view *view, int width, int height, int noc,
+                            int radius, float sigma, int use_fb, float alpha, float beta, int out_dtype, void *out,
+                            uint8_t *used, void *stream);
+
+/* The flows of a video and its frames filtered over a radius from one call.  By definition out / used ==
+ * ofdis_tfilter_radius_u8 on the fields of ofdis_run_sequence_u8(frames, stride 1) in both directions, bit for bit.
+ * Every pair's two flows leave the coarse-to-fine loop as float32 level grids, 2 * m * bytes_per_pair bytes in the buffer
+ * the context owns, and one launch filters all frames from the grids after the last chunk: no upsample and no
+ * forward-backward check launch runs, no mask plane and no full-resolution flow exists.
+ * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED, and so does a call while a stage capture is set.  No
+ * initial flow.  verbosity is ignored.  Argument errors are those of ofdis_run_sequence_tfilter_u8 and of
+ * ofdis_tfilter_radius_u8; stream, ordering, chunking, round-robin, graph and workspace rules are those of
+ * ofdis_run_batch_u8 (the graph is recorded anew when an output pointer, out_dtype, radius, sigma, use_fb, alpha or beta
+ * changes; a graph of another call kind is never replayed). */
+int ofdis_run_sequence_tfilter_radius_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                         const ofdis_params *p, int radius, float sigma, int use_fb, float alpha,
+                                         float beta, int out_dtype, void *out, uint8_t *used, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_sequence_tfilter_radius_u8_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int width,
+                                              int height, const ofdis_params *p, int radius, float sigma, int use_fb,
+                                              float alpha, float beta, int out_dtype, void *out, uint8_t *used);
+
 /* ------------------------------------------------------------------ global motion and video stabilisation
  *
  * Not in the reference.  The camera's motion between the frames of a video as one 2 x 3 transform per frame pair, fitted
@@ -871,7 +937,8 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * full-resolution flow views and as "track_level" with level-grid views; the temporal filter as "tfilter" with
  * full-resolution flow views and as "tfilter_level" with level-grid views; the motion fit as "fit_motion" with
  * full-resolution flow views and as "fit_motion_level" with level-grid views, the path kernel as "smooth_path" and the
- * affine warp as "warp_affine". */
+ * affine warp as "warp_affine"; the temporal filter over a radius as "tfilter_radius" with full-resolution flow views
+ * and as "tfilter_radius_level" with level-grid views. */
 const char *ofdis_kernel_names(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
@@ -892,8 +959,18 @@ const char *ofdis_kernel_names(void);
  * counted): the 8-byte value of a float32 view per sample, ns * 8; of a level grid the up to nine 8-byte cells a
  * sample's expansion reads, ns * 72.  "smooth_path": six doubles per pair in and per frame out, 96.  "warp_affine": per
  * frame, noc bytes of image read, noc bytes of u8 output and the mask byte per pixel and the six doubles --
- * W * H * (2 noc + 1) + 48. */
+ * W * H * (2 noc + 1) + 48.  "tfilter_radius" / "tfilter_radius_level": ofdis_tfilter_radius_bytes at radius 1 with a
+ * u8 picture (the counts of "tfilter" / "tfilter_level"). */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
+/* The same model for the temporal filter over a radius R (ofdis_tfilter_radius_u8), which depends on R and on the
+ * picture's dtype: per interior output frame, in "tfilter"'s convention, each of the 2 R steps reads one field once (8
+ * bytes per pixel of a full-resolution float32 view, or one level grid; the check's gathers are not counted, as in
+ * "track") and one neighbour's taps (noc), plus the frame itself (noc), the picture (noc as u8, 4 noc as float32) and
+ * the `used` byte -- W * H * (16 R + (2 R + 2) noc + 1) with full-resolution views (level = 0) and
+ * 2 R * gw * gh * 8 + W * H * ((2 R + 2) noc + 1) with level grids (level != 0); a float32 picture has 4 noc in place
+ * of the output's noc.  radius outside [1, 4] or an unknown out_dtype: OFDIS_ERR_INVALID_ARGUMENT. */
+int ofdis_tfilter_radius_bytes(const ofdis_params *p, int width, int height, int level, int radius, int out_dtype,
+                               double *bytes_per_frame);
 
 /* ------------------------------------------------------------------ files and inputs */
 

@@ -6,7 +6,8 @@ Drop-in for lordnn/OF_DIS's OFClass / run_dense pipeline.  The compute lives in 
 from ._lib import (FIT_LANES, FIT_MAX_SAMPLES, IMG_F32, IMG_U8, INTERP_MAX_T, MODE_DE, MODE_OF, MOTION_SIMILARITY,  # noqa: F401
                    MOTION_TRANSLATION, TRACK_LAST, FlowView, OfdisError, OutFormat, Params, build, lib, out_format)
 from .ofclass import (Context, OFClass, algorithmic_bytes, auto_first_scale, fit_lattice, kernel_names,  # noqa: F401
-                      max_frames_per_launch, oppoint, out_geometry, params_from_strings, pixel_grid, read_flo, read_image, synth_pair, synth_shift_pair, validate,
+                      max_frames_per_launch, oppoint, out_geometry, params_from_strings, pixel_grid, read_flo, read_image, synth_pair, synth_shift_pair,
+                      tfilter_radius_bytes, validate,
                       write_flo, write_pfm, write_pnm)
 
 __version__ = "0.1.0"

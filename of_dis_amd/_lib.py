@@ -176,6 +176,9 @@ def lib():
         "ofdis_tfilter_u8": ([vp, vp, i, vp, vp, V, i, i, i, f, vp, vp, i, vp, vp, vp], i),
         "ofdis_run_sequence_tfilter_u8": ([vp, vp, i, i, i, P, f, i, f, f, i, vp, vp, vp], i),
         "ofdis_run_sequence_tfilter_u8_host": ([vp, vp, i, i, i, P, f, i, f, f, i, vp, vp], i),
+        "ofdis_tfilter_radius_u8": ([vp, vp, i, vp, vp, V, i, i, i, i, f, i, f, f, i, vp, vp, vp], i),
+        "ofdis_run_sequence_tfilter_radius_u8": ([vp, vp, i, i, i, P, i, f, i, f, f, i, vp, vp, vp], i),
+        "ofdis_run_sequence_tfilter_radius_u8_host": ([vp, vp, i, i, i, P, i, f, i, f, f, i, vp, vp], i),
         "ofdis_fit_motion": ([vp, vp, vp, V, i, i, i, i, i, d, i, f, f, vp, vp, vp, vp], i),
         "ofdis_smooth_path": ([vp, vp, i, i, d, i, i, vp, vp], i),
         "ofdis_warp_affine_u8": ([vp, vp, i, i, i, i, vp, i, vp, vp, vp], i),
@@ -189,6 +192,7 @@ def lib():
         "ofdis_context_kernel_time": ([vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "ofdis_kernel_names": ([], C.c_char_p),
         "ofdis_algorithmic_bytes": ([P, i, i, C.c_char_p, C.POINTER(C.c_double)], i),
+        "ofdis_tfilter_radius_bytes": ([P, i, i, i, i, i, C.POINTER(C.c_double)], i),
         "ofdis_max_frames_per_launch": ([P, i, i, C.POINTER(i)], i),
         "ofdis_write_flo": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_write_pfm": ([C.c_char_p, vp, i, i], i),

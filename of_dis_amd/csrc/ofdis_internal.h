@@ -269,6 +269,15 @@ struct TfilterArgs {
   int srows, scols;              // level form: rows and columns of a staged window (set by launch_tfilter)
 };
 
+// Every frame averaged with up to `radius` motion-compensated frames on each side, the positions chained through the
+// fields and checked step by step (include/ofdis.h: ofdis_tfilter_radius_u8).
+struct TfilterRadiusArgs {
+  TfilterArgs f;      // the frames, chains, outputs and view; occ_fw / occ_bw stay NULL; `used` holds 2 * radius bits
+  int radius;         // 1 .. 4
+  int use_fb;         // every step runs the tracker's round-trip test at alpha, beta
+  float alpha, beta;
+};
+
 // A robust similarity or translation fitted to each of m flow fields (include/ofdis.h: ofdis_fit_motion).  One view
 // describes both chains.
 constexpr int kFitLanes = 256;         // OFDIS_FIT_LANES: one workgroup per pair, the pinned summation order
@@ -314,6 +323,7 @@ void launch_smooth_path(const PathArgs &a, hipStream_t s);
 void launch_warp_affine(const WarpAffineArgs &a, hipStream_t s);
 void launch_track(const TrackArgs &a, hipStream_t s);
 void launch_tfilter(const TfilterArgs &a, hipStream_t s);
+void launch_tfilter_radius(const TfilterRadiusArgs &a, hipStream_t s);
 void launch_interp(const InterpArgs &a, hipStream_t s);
 void launch_fb_check(const FbArgs &a, hipStream_t s);
 void launch_fb_check_level(const FbLevelArgs &a, hipStream_t s);

@@ -40,6 +40,8 @@
 //                thread per point (no reference code)
 //   tfilter      k_tfilter<OT, NOC, FT, PLANAR, PX>, k_tfilter_level<OT, NOC, PX>  every frame of a video averaged with
 //                its two motion-compensated neighbours, full-resolution fields / level grids (no reference code)
+//   tfilter_radius  k_tfilter_radius<OT, NOC, FT, PLANAR, PX>, k_tfilter_radius_level<OT, NOC, PX>  the same over up to
+//                four frames on each side, positions chained and checked step by step (no reference code)
 //   motion       k_fit_motion<FT, PLANAR, CACHE>, k_fit_motion_level<CACHE>  a robust similarity per flow field, float64,
 //                one workgroup per pair; k_smooth_path  pair transforms to per-frame corrections;
 //                k_warp_affine<OT, NOC, PX>  every frame through its own 2 x 3 transform (no reference code)
@@ -6804,9 +6806,11 @@ __global__ __launch_bounds__(256) void k_tfilter(TfilterArgs a) {
 // Block shape and dynamic-LDS staging of k_interp_level, for two grids of one geometry that belong to different pairs:
 // grid 0 is backward grid i - 1 (frame i -> i - 1), grid 1 forward grid i (frame i -> i + 1), both on frame i's pixel
 // grid.  An end frame stages and expands its one grid.
+// emit(f, x, y, pu, pv, nu, nv) gets the PX pixels (x .. x + PX - 1, y) of frame f with their own flows to the previous
+// and to the next frame (shared with k_tfilter_radius_level).
 extern __shared__ float tfilter_src[];  // [grid][row][comp][col]
-template <class OT, int NOC, int PX>
-__global__ __launch_bounds__(256) void k_tfilter_level(TfilterArgs a) {
+template <int PX, class Emit>
+__device__ __forceinline__ void tfilter_level_rows(const TfilterArgs &a, Emit &&emit) {
   constexpr int kCols = 256 * PX;
   auto src = [&](int g, int row, int comp) { return tfilter_src + ((g * a.srows + row) * 2 + comp) * a.scols; };
   const unsigned ncb = ((unsigned)a.W + kCols - 1) / kCols;
@@ -6831,7 +6835,7 @@ __global__ __launch_bounds__(256) void k_tfilter_level(TfilterArgs a) {
         if (has[0]) pu[i] = G[0][2 * o], pv[i] = G[0][2 * o + 1];
         if (has[1]) nu[i] = G[1][2 * o], nv[i] = G[1][2 * o + 1];
       }
-      tfilter_emit<OT, NOC, PX>(a, f, x, y, pu, pv, nu, nv);
+      emit(f, x, y, pu, pv, nu, nv);
     }
     return;
   }
@@ -6877,8 +6881,15 @@ __global__ __launch_bounds__(256) void k_tfilter_level(TfilterArgs a) {
         nv[i] = up_px_s(src(1, j0, 1), src(1, j1, 1), xt[i], b0, b1);
       }
     }
-    tfilter_emit<OT, NOC, PX>(a, f, x, y, pu, pv, nu, nv);
+    emit(f, x, y, pu, pv, nu, nv);
   }
+}
+
+template <class OT, int NOC, int PX>
+__global__ __launch_bounds__(256) void k_tfilter_level(TfilterArgs a) {
+  tfilter_level_rows<PX>(a, [&](int f, int x, int y, const float *pu, const float *pv, const float *nu, const float *nv) {
+    tfilter_emit<OT, NOC, PX>(a, f, x, y, pu, pv, nu, nv);
+  });
 }
 
 }  // namespace
@@ -6912,6 +6923,190 @@ void launch_tfilter(const TfilterArgs &a0, hipStream_t s) {
       else if (a.f16) k_tfilter<O, NOC, _Float16, false, PX><<<grid, 256, 0, s>>>(a);
       else if (a.planar) k_tfilter<O, NOC, float, true, PX><<<grid, 256, 0, s>>>(a);
       else k_tfilter<O, NOC, float, false, PX><<<grid, 256, 0, s>>>(a);
+    };
+    pick_noc(a.noc, [&](auto NOC) {
+      pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {
+        if (vec) go(OT, NOC, Int<4>{});
+        else go(OT, NOC, Int<1>{});
+      });
+    });
+  }
+}
+
+// ------------------------------------------------------------------------------ temporal filter over a radius
+// Every frame averaged with up to R frames on each side (include/ofdis.h: ofdis_tfilter_radius_u8).  A pixel's position
+// is chained through the fields: step 1 adds its own flow, step k >= 2 the tracker's gather of the next field at the
+// position reached so far, and with use_fb every step runs the tracker's round-trip test there -- fb_pixel's test at
+// step 1 -- so no mask plane exists.  A chain that leaves the frame or fails a test contributes nothing from that step
+// on (a weight of 0 adds exact zeros), so it stops there.  One direction is marched completely before the other, and
+// within a step the PX pixels of a thread go side by side: only one chain's state is live and the PX gathers of a step
+// are independent.  Steps k >= 2 land anywhere in the frame and gather from global memory (the level grids of a 1080p
+// field are 65 KB and stay in L2).
+//   k_tfilter_radius<OT, NOC, FT, PLANAR, PX>  the chains are full-resolution fields: own flows as k_tfilter, TrackFull
+//   k_tfilter_radius_level<OT, NOC, PX>        float32 interleaved level grids: own flows from k_tfilter_level's staged
+//                                              windows, the gathers through TrackLevel (level_taps)
+namespace {
+
+// The PX pixels (x .. x + PX - 1, y) of frame i from their own flows to the previous frame (pu, pv) and to the next one
+// (nu, nv); sample(base, j, px, py, u, v) is the tracker's gather of field j of a chain.  SKIP: below.
+template <class OT, int NOC, int PX, bool SKIP, class S>
+__device__ __forceinline__ void tfilter_radius_emit(const TfilterRadiusArgs &ra, const S &sample, int i, int x, int y,
+                                                    const float *pu, const float *pv, const float *nu, const float *nv) {
+  const TfilterArgs &a = ra.f;
+  const long plane = (long)a.W * a.H, o = (long)i * plane + (long)y * a.W + x;
+  const float wm = (float)(a.W - 1), hm = (float)(a.H - 1);
+  auto in = [&](float px, float py) { return px >= 0.f && px <= wm && py >= 0.f && py <= hm; };  // false for NaN
+  // the thread's own bytes of the frame (as tfilter_emit)
+  float C[PX * NOC], acc[PX * NOC], wsum[PX];
+  const uint8_t *Cp = a.frames + o * NOC;
+  if constexpr (PX == 4) {
+#pragma unroll
+    for (int j = 0; j < NOC; ++j) {
+      const unsigned w = *reinterpret_cast<const unsigned *>(Cp + 4 * j);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) C[4 * j + b] = (float)((w >> (8 * b)) & 0xffu);
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) C[c] = (float)Cp[c];
+  }
+#pragma unroll
+  for (int k = 0; k < PX * NOC; ++k) acc[k] = C[k];
+#pragma unroll
+  for (int px = 0; px < PX; ++px) wsum[px] = 1.f;
+  unsigned m = 0;
+#pragma unroll 1
+  for (int dir = 0; dir < 2; ++dir) {
+    // the chain's step fields and the opposite ones: previous flow_bw[j] / flow_fw[j], next flow_fw[j-1] / flow_bw[j-1]
+    const void *F = dir ? a.fw : a.bw, *B = dir ? a.bw : a.fw;
+    float qx[PX], qy[PX], fu[PX], fv[PX];
+    bool live[PX];
+#pragma unroll
+    for (int px = 0; px < PX; ++px) {
+      qx[px] = (float)(x + px), qy[px] = (float)y;
+      fu[px] = dir ? nu[px] : pu[px], fv[px] = dir ? nv[px] : pv[px];
+      live[px] = true;
+    }
+#pragma unroll 1
+    for (int k = 1; k <= ra.radius; ++k) {
+      const int j = dir ? i + k : i - k;
+      if (j < 0 || j >= a.T) break;
+      const int fi = dir ? j - 1 : j;  // in [0, T - 2]
+      const uint8_t *N = a.frames + (long)j * plane * NOC;
+      // SKIP: a chain that has ended branches round the rest of its step (the level gather is arithmetic, not worth
+      // running for nothing).  Else no branch around the gathers (as fb_pixel): an ended chain reads the taps of (0, 0)
+      // and drops the result, so the loads of a thread's PX pixels are all in flight together.
+      // The check's uniform branch stays outside the pixels' loop, which is straight-line code without SKIP.
+      bool any = false;
+      auto step = [&](auto FB) {
+#pragma unroll
+      for (int px = 0; px < PX; ++px) {
+        bool on = live[px];
+        if (SKIP && !on) continue;
+        if (k > 1) sample(F, fi, on ? qx[px] : 0.f, on ? qy[px] : 0.f, fu[px], fv[px]);
+        qx[px] = qx[px] + fu[px], qy[px] = qy[px] + fv[px];
+        on = on && in(qx[px], qy[px]);
+        live[px] = on;
+        if (SKIP && !on) continue;
+        if constexpr (decltype(FB)::value != 0) {  // track_point's test
+          float bu, bv;
+          sample(B, fi, on ? qx[px] : 0.f, on ? qy[px] : 0.f, bu, bv);
+          const float du = fu[px] + bu, dv = fv[px] + bv;
+          const float err = du * du + dv * dv;
+          const float mag = (fu[px] * fu[px] + fv[px] * fv[px]) + (bu * bu + bv * bv);
+          const float thr = ra.alpha * mag + ra.beta;
+          on = on && err <= thr;  // a NaN fails
+          live[px] = on;
+          if (SKIP && !on) continue;
+        }
+        any = any || on;
+        // warp_pixel from pixel (0, 0) along the "flow" (qx, qy) at scale 1: 1 * qx and 0 + qx are qx (as k_warp_affine)
+        float Sv[NOC];
+        warp_pixel<NOC>(N, a.W, a.H, 0, 0, on ? qx[px] : 0.f, on ? qy[px] : 0.f, 1.f, Sv);
+        float d = fabsf(Sv[0] - C[px * NOC]);
+#pragma unroll
+        for (int c = 1; c < NOC; ++c) d = d + fabsf(Sv[c] - C[px * NOC + c]);
+        const float r = d * a.inv;
+        const float w = on ? fmaxf(1.f - r * r, 0.f) : 0.f;  // (0 * Sv is an exact zero: Sv is finite)
+#pragma unroll
+        for (int c = 0; c < NOC; ++c) acc[px * NOC + c] = acc[px * NOC + c] + w * Sv[c];
+        wsum[px] = wsum[px] + w;
+        if (w > 0.f) m |= 1u << (8 * px + 2 * (k - 1) + dir);
+      }
+      };
+      if (ra.use_fb) step(Int<1>{});
+      else step(Int<0>{});
+      if (!any) break;
+    }
+  }
+  float val[PX * NOC];
+#pragma unroll
+  for (int px = 0; px < PX; ++px) {
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) {
+      const float v = acc[px * NOC + c] / wsum[px];
+      val[px * NOC + c] = std::is_same<OT, float>::value ? v : fminf(v, 255.f);
+    }
+  }
+  interp_store<OT, NOC, PX>(a.out, a.used, o, val, m);
+}
+
+// Thread layout and own-flow loads of k_tfilter.
+template <class OT, int NOC, class FT, bool PLANAR, int PX>
+__global__ __launch_bounds__(256) void k_tfilter_radius(TfilterRadiusArgs ra) {
+  const TfilterArgs &a = ra.f;
+  const int i = a.f0 + (int)blockIdx.z;
+  const unsigned wq = (unsigned)a.W / PX;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= wq * (unsigned)a.H) return;
+  const int y = (int)(q / wq), x = (int)(q - (unsigned)y * wq) * PX;
+  const long plane = (long)a.W * a.H, o = (long)y * a.W + x;
+  float pu[PX] = {}, pv[PX] = {}, nu[PX] = {}, nv[PX] = {};
+  if (i > 0) warp_own_flow<FT, PLANAR, PX>(reinterpret_cast<const FT *>(a.bw) + (long)(i - 1) * 2 * plane, o, plane, pu, pv);
+  if (i < a.T - 1) warp_own_flow<FT, PLANAR, PX>(reinterpret_cast<const FT *>(a.fw) + (long)i * 2 * plane, o, plane, nu, nv);
+  tfilter_radius_emit<OT, NOC, PX, false>(ra, TrackFull<FT, PLANAR>{a.W, a.H, 2 * plane}, i, x, y, pu, pv, nu, nv);
+}
+
+template <class OT, int NOC, int PX>
+__global__ __launch_bounds__(256) void k_tfilter_radius_level(TfilterRadiusArgs ra) {
+  const TfilterArgs &a = ra.f;
+  const TrackLevel sample{a.W, a.H, 2 * (long)a.gw * a.gh, LevelGeo{a.gw, a.gh, a.log2c, a.offx, a.offy},
+                          1.0 / (double)(1 << a.log2c)};
+  tfilter_level_rows<PX>(a, [&](int f, int x, int y, const float *pu, const float *pv, const float *nu, const float *nv) {
+    tfilter_radius_emit<OT, NOC, PX, true>(ra, sample, f, x, y, pu, pv, nu, nv);
+  });
+}
+
+}  // namespace
+// ---- launch
+// Slices, grids, staged windows and the conditions of the vector forms are launch_tfilter's (there are no masks).
+void launch_tfilter_radius(const TfilterRadiusArgs &ra0, hipStream_t s) {
+  const TfilterArgs &a0 = ra0.f;
+  const bool vec = a0.W % 4 == 0 && (a0.level || ((uintptr_t)a0.fw % 16 == 0 && (uintptr_t)a0.bw % 16 == 0)) &&
+                   (uintptr_t)a0.out % (a0.out_f32 ? 16 : 4) == 0 && (uintptr_t)a0.used % 4 == 0 &&
+                   (uintptr_t)a0.frames % 4 == 0;
+  const long frame = (long)a0.W * a0.H;
+  const int kSlice = 65535;  // grid z
+  for (int f0 = 0; f0 < a0.T; f0 += kSlice) {
+    TfilterRadiusArgs ra = ra0;
+    TfilterArgs &a = ra.f;
+    a.f0 = f0;
+    a.n = std::min(kSlice, a0.T - f0);
+    auto go = [&](auto OT, auto NOC, auto PX) {
+      using O = std::conditional_t<OT != 0, float, uint8_t>;
+      if (a.level) {
+        const dim3 grid(ceil_div(a.H, kWarpRows) * ceil_div(a.W, 256 * PX), 1, a.n);
+        a.srows = a.log2c ? std::min((kWarpRows >> a.log2c) + 3, kWarpSrcRows) : 0;
+        a.scols = a.log2c ? std::min(((256 * PX) >> a.log2c) + 3, kWarpSrcCols) : 0;
+        const size_t lds = sizeof(float) * 2 * a.srows * 2 * a.scols;
+        k_tfilter_radius_level<O, NOC, PX><<<grid, 256, lds, s>>>(ra);
+        return;
+      }
+      const dim3 grid(ceil_div(frame / PX, 256), 1, a.n);
+      if (a.f16 && a.planar) k_tfilter_radius<O, NOC, _Float16, true, PX><<<grid, 256, 0, s>>>(ra);
+      else if (a.f16) k_tfilter_radius<O, NOC, _Float16, false, PX><<<grid, 256, 0, s>>>(ra);
+      else if (a.planar) k_tfilter_radius<O, NOC, float, true, PX><<<grid, 256, 0, s>>>(ra);
+      else k_tfilter_radius<O, NOC, float, false, PX><<<grid, 256, 0, s>>>(ra);
     };
     pick_noc(a.noc, [&](auto NOC) {
       pick<0, 1>(a.out_f32 ? 1 : 0, [&](auto OT) {

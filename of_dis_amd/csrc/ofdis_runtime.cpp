@@ -48,7 +48,9 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     "tfilter", "tfilter_level",
                                     // the motion fit on full-resolution fields / on level grids, the path kernel
                                     // and the affine warp
-                                    "fit_motion", "fit_motion_level", "smooth_path", "warp_affine"};
+                                    "fit_motion", "fit_motion_level", "smooth_path", "warp_affine",
+                                    // the temporal filter over a radius on full-resolution fields / on level grids
+                                    "tfilter_radius", "tfilter_radius_level"};
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -119,7 +121,7 @@ struct ofdis_context {
   // payload of the call's family alone; the whole key is zeroed before it is filled and compared bytewise, padding
   // included, and the family tag keeps the keys of two families apart whatever their payloads hold.
   struct GraphKey {
-    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter, kStab };
+    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter, kStab, kTfilterRadius };
     // run_batch: ofdis_run_batch_u8*, bidir, stereo, sequence, the formatted calls and ofdis_run_warp_u8
     struct Batch {
       const void *flow_bw, *occ_fw, *occ_bw, *err_fw, *err_bw;  // the bidirectional / stereo call's extra outputs,
@@ -159,6 +161,12 @@ struct ofdis_context {
       float alpha, beta;
       double tau, zoom;
     };
+    // run_batch_tfilter_radius: the picture, its dtype and `used` bytes, sigma, the radius; with use_fb the thresholds
+    struct TfilterRadius {
+      const void *picture, *used;
+      int f32, radius, use_fb;
+      float sigma, alpha, beta;
+    };
     int family;
     int n, w, h;
     int seq, stride;  // a sequence call: `a` is one array of n + stride frames
@@ -171,6 +179,7 @@ struct ofdis_context {
       Track track;
       Tfilter tfilter;
       Stab stab;
+      TfilterRadius tfilter_radius;
     } u;
   } gkey{};
   hipGraphExec_t gexec = nullptr;
@@ -2458,6 +2467,8 @@ struct TfilterIo {
   const uint8_t *occ_fw = nullptr, *occ_bw = nullptr;  // the primitive's masks
   bool use_occ = false;                                // the fused call: masks from the chunks' grids at alpha, beta
   float alpha = 0.f, beta = 0.f;
+  int radius = 0;       // the radius calls (ofdis_tfilter_radius_u8, ...): 1 .. 4, and whether every chain step is
+  bool use_fb = false;  // checked at alpha, beta
   int f32 = 0;
   void *out = nullptr;
   uint8_t *used = nullptr;
@@ -2475,9 +2486,9 @@ bool tfilter_io_ok(const TfilterIo &io, const uint8_t *frames, int nframes, int 
   return f + in <= o || o + outb <= f;
 }
 
-// The T frames filtered along the two chains of view v (timer "tfilter_level" for a level-grid view, else "tfilter").
-int run_tfilter(ofdis_context *c, const uint8_t *frames, int nframes, const void *fw, const void *bw,
-                const ofdis_flow_view &v, int width, int height, int noc, const TfilterIo &io, hipStream_t s) {
+// The kernel arguments of a filtering call on the two chains of view v.
+TfilterArgs tfilter_args(const uint8_t *frames, int nframes, const void *fw, const void *bw, const ofdis_flow_view &v,
+                         int width, int height, int noc, const TfilterIo &io) {
   TfilterArgs ta{};
   ta.frames = frames;
   ta.fw = fw;
@@ -2502,7 +2513,27 @@ int run_tfilter(ofdis_context *c, const uint8_t *frames, int nframes, const void
     ta.offy = v.off_y;
     while ((1 << ta.log2c) < v.cell) ++ta.log2c;
   }
+  return ta;
+}
+
+// The T frames filtered along the two chains of view v (timer "tfilter_level" for a level-grid view, else "tfilter").
+int run_tfilter(ofdis_context *c, const uint8_t *frames, int nframes, const void *fw, const void *bw,
+                const ofdis_flow_view &v, int width, int height, int noc, const TfilterIo &io, hipStream_t s) {
+  const TfilterArgs ta = tfilter_args(frames, nframes, fw, bw, v, width, height, noc, io);
   timed(c, ta.level ? 28 : 27, s, [&] { launch_tfilter(ta, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// The same over io.radius frames on each side (timers "tfilter_radius_level" / "tfilter_radius").
+int run_tfilter_radius(ofdis_context *c, const uint8_t *frames, int nframes, const void *fw, const void *bw,
+                       const ofdis_flow_view &v, int width, int height, int noc, const TfilterIo &io, hipStream_t s) {
+  TfilterRadiusArgs ra{};
+  ra.f = tfilter_args(frames, nframes, fw, bw, v, width, height, noc, io);
+  ra.radius = io.radius;
+  ra.use_fb = io.use_fb;
+  ra.alpha = io.alpha;
+  ra.beta = io.beta;
+  timed(c, ra.f.level ? 34 : 33, s, [&] { launch_tfilter_radius(ra, s); });
   return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
 }
 
@@ -2547,6 +2578,40 @@ int run_batch_tfilter(ofdis_context *c, hipStream_t s, const uint8_t *frames, in
     fio.occ_bw = masks_bw;
     return run_tfilter(c, frames, m + 1, grids, grids_bw, v, width, height, p->noc, fio, q);
   });
+}
+
+// ofdis_run_sequence_tfilter_radius_u8 on stream s: run_batch_tfilter's plan without the mask planes and without the
+// check's launches -- every chunk writes its share of the 2 m level grids, then one filter launch on s over all frames.
+int run_batch_tfilter_radius(ofdis_context *c, hipStream_t s, const uint8_t *frames, int m, int width, int height,
+                             const ofdis_params *p, const TfilterIo &io) {
+  CallPlan cp;
+  int rc = prepare(c, p, m, width, height, false, false, cp, 1, 1);
+  if (rc) return rc;
+  const ofdis_flow_view v = level_view(first_plan(cp));
+  cp.out_pair = level_grid_bytes(first_plan(cp));
+  const size_t in_frame = (size_t)width * height * p->noc;
+  if ((rc = ensure_warp_buf(c, 2 * (size_t)m * cp.out_pair))) return rc;  // (drops the graph before it grows)
+  char *grids = c->warp_buf, *grids_bw = grids + (size_t)m * cp.out_pair;
+  GraphKey key = graph_key(GraphKey::kTfilterRadius, c, frames, nullptr, nullptr, grids, grids, m, width, height, 1, p);
+  GraphKey::TfilterRadius &kf = key.u.tfilter_radius;
+  kf.picture = io.out; kf.used = io.used; kf.f32 = io.f32; kf.radius = io.radius; kf.sigma = io.sigma;
+  kf.use_fb = io.use_fb;
+  if (io.use_fb) {
+    kf.alpha = io.alpha; kf.beta = io.beta;
+  }
+  return replay_or_record(c, s, cp, key, [&](hipStream_t q) {
+    const int err = for_each_chunk(c, cp, q, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      return run_chunk_grids(c, ws, P, p, frames + f0 * in_frame, nullptr, grids + f0 * cp.out_pair,
+                             grids_bw + f0 * cp.out_pair, ls);
+    });
+    if (err) return err;
+    return run_tfilter_radius(c, frames, m + 1, grids, grids_bw, v, width, height, p->noc, io, q);
+  });
+}
+
+// What the radius calls check beyond tfilter_io_ok.
+bool tfilter_radius_ok(const TfilterIo &io) {
+  return io.radius >= 1 && io.radius <= 4 && (!io.use_fb || fb_thresholds_ok(io.alpha, io.beta));
 }
 }  // namespace
 
@@ -2596,9 +2661,13 @@ int ofdis_run_sequence_tfilter_u8(ofdis_context *c, const uint8_t *frames, int n
   });
 }
 
-int ofdis_run_sequence_tfilter_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
-                                       const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
-                                       int out_dtype, void *out, uint8_t *used) {
+extern "C++" {  // (a template)
+namespace {
+// The host forms of the fused filters: the frames up, call(frames, out, used) on the context's stream, the picture and
+// the `used` bytes down (synchronous).
+template <class Call>
+int tfilter_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height, const ofdis_params *p,
+                 int out_dtype, void *out, uint8_t *used, Call &&call) {
   if (!c || !frames || !p || !out || nframes < 2 || width <= 0 || height <= 0 || !img_dtype_ok(out_dtype) ||
       (p->noc != 1 && p->noc != 3))
     return OFDIS_ERR_INVALID_ARGUMENT;
@@ -2614,8 +2683,7 @@ int ofdis_run_sequence_tfilter_u8_host(ofdis_context *c, const uint8_t *frames, 
     return rc == OFDIS_OK;
   };
   if (step(hipMemcpyAsync(d, frames, in, hipMemcpyHostToDevice, c->stream))) {
-    rc = ofdis_run_sequence_tfilter_u8(c, (const uint8_t *)d, nframes, width, height, p, sigma, use_occ, alpha, beta,
-                                       out_dtype, d + off_out, used ? (uint8_t *)(d + off_used) : nullptr, c->stream);
+    rc = call((const uint8_t *)d, (void *)(d + off_out), used ? (uint8_t *)(d + off_used) : nullptr);
     if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
       step(hipMemcpy(out, d + off_out, outb, hipMemcpyDeviceToHost));
       if (used) step(hipMemcpy(used, d + off_used, px, hipMemcpyDeviceToHost));
@@ -2623,6 +2691,76 @@ int ofdis_run_sequence_tfilter_u8_host(ofdis_context *c, const uint8_t *frames, 
   }
   hipFree(d);
   return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int ofdis_run_sequence_tfilter_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                       const ofdis_params *p, float sigma, int use_occ, float alpha, float beta,
+                                       int out_dtype, void *out, uint8_t *used) {
+  return tfilter_host(c, frames, nframes, width, height, p, out_dtype, out, used, [&](const uint8_t *d, void *dout, uint8_t *dused) {
+    return ofdis_run_sequence_tfilter_u8(c, d, nframes, width, height, p, sigma, use_occ, alpha, beta, out_dtype, dout,
+                                         dused, c->stream);
+  });
+}
+
+int ofdis_tfilter_radius_u8(ofdis_context *c, const uint8_t *frames, int nframes, const void *flow_fw,
+                            const void *flow_bw, const ofdis_flow_view *v, int width, int height, int noc, int radius,
+                            float sigma, int use_fb, float alpha, float beta, int out_dtype, void *out, uint8_t *used,
+                            void *stream) {
+  TfilterIo io;
+  io.sigma = sigma;
+  io.radius = radius;
+  io.use_fb = use_fb != 0;
+  io.alpha = alpha;
+  io.beta = beta;
+  io.f32 = out_dtype == OFDIS_IMG_F32;
+  io.out = out;
+  io.used = used;
+  if (!c || !flow_fw || !flow_bw || !v || !tfilter_io_ok(io, frames, nframes, width, height, noc, out_dtype) ||
+      !tfilter_radius_ok(io))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->grid == OFDIS_OUT_LEVEL && (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED))
+    return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_tfilter_u8)
+  if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    return run_tfilter_radius(c, frames, nframes, flow_fw, flow_bw, *v, width, height, noc, io, s);
+  });
+}
+
+int ofdis_run_sequence_tfilter_radius_u8(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                         const ofdis_params *p, int radius, float sigma, int use_fb, float alpha,
+                                         float beta, int out_dtype, void *out, uint8_t *used, void *stream) {
+  TfilterIo io;
+  io.sigma = sigma;
+  io.radius = radius;
+  io.use_fb = use_fb != 0;
+  io.alpha = alpha;
+  io.beta = beta;
+  io.f32 = out_dtype == OFDIS_IMG_F32;
+  io.out = out;
+  io.used = used;
+  if (!c || !p || !tfilter_io_ok(io, frames, nframes, width, height, p->noc, out_dtype) || !tfilter_radius_ok(io))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
+  return device_call(c, stream, true, [&](hipStream_t s) {
+    return run_batch_tfilter_radius(c, s, frames, nframes - 1, width, height, p, io);
+  });
+}
+
+int ofdis_run_sequence_tfilter_radius_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width,
+                                              int height, const ofdis_params *p, int radius, float sigma, int use_fb,
+                                              float alpha, float beta, int out_dtype, void *out, uint8_t *used) {
+  return tfilter_host(c, frames, nframes, width, height, p, out_dtype, out, used, [&](const uint8_t *d, void *dout, uint8_t *dused) {
+    return ofdis_run_sequence_tfilter_radius_u8(c, d, nframes, width, height, p, radius, sigma, use_fb, alpha, beta,
+                                                out_dtype, dout, dused, c->stream);
+  });
 }
 
 // ------------------------------------------------------------------ global motion and stabilisation (include/ofdis.h)
@@ -3032,6 +3170,20 @@ const char *ofdis_kernel_names(void) {
   return names.c_str();
 }
 
+// The filter over a radius per interior output frame, in "tfilter"'s convention: per pixel the frame and the taps of
+// its 2 R neighbours ((2 R + 1) noc), the picture (noc, or 4 noc as float32) and the `used` byte; each of the 2 R steps
+// reads one field once -- 8 bytes per pixel of a full-resolution float32 view (16 R), or a level grid (the opposite
+// fields of the check are gathers and are not counted, as in "track").
+int ofdis_tfilter_radius_bytes(const ofdis_params *p, int width, int height, int level, int radius, int out_dtype,
+                               double *bytes) {
+  if (!p || !bytes || radius < 1 || radius > 4 || !img_dtype_ok(out_dtype)) return OFDIS_ERR_INVALID_ARGUMENT;
+  const Plan P = batch_plan(p, 1, width, height);
+  const double px = (double)width * height, R = radius;
+  const double pic = (2.0 * R + 1.0) * P.noc + (out_dtype == OFDIS_IMG_F32 ? 4.0 : 1.0) * P.noc + 1.0;
+  *bytes = level ? 2.0 * R * P.lv[0].w * P.lv[0].h * 8.0 + px * pic : px * (16.0 * R + pic);
+  return OFDIS_OK;
+}
+
 // Byte model of SURVEY §8(d), per frame pair, for the roofline of each kernel family.
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes) {
   if (!p || !kernel || !bytes) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -3090,6 +3242,10 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   // two float32 flow views -- 16 bytes per pixel, or the two level grids
   if (k == "tfilter") b = (double)width * height * (16.0 + 4.0 * noc + 1.0);
   if (k == "tfilter_level") b = 2.0 * P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * (4.0 * noc + 1.0);
+  // the filter over a radius has the radius and the picture's dtype in its model (ofdis_tfilter_radius_bytes); here at
+  // radius 1 with a u8 picture, which is "tfilter"'s count
+  if (k == "tfilter_radius") return ofdis_tfilter_radius_bytes(p, width, height, 0, 1, OFDIS_IMG_U8, bytes);
+  if (k == "tfilter_radius_level") return ofdis_tfilter_radius_bytes(p, width, height, 1, 1, OFDIS_IMG_U8, bytes);
   // the motion fit per pair at the default lattice (step 16), in "track"'s convention (the check's gather not
   // counted): 8 bytes per sample of a full-resolution float32 view; of a level grid the up to nine 8-byte cells a
   // sample's expansion reads.  The path kernel moves 6 doubles per pair in and per frame out (charged per pair)

@@ -1086,6 +1086,122 @@ class Context:
               "ofdis_run_sequence_tfilter_u8_host")
         return (out, used) if want_used else out
 
+    def tfilter_radius_ptr(self, frames_ptr: int, nframes: int, fw_ptr: int, bw_ptr: int, view: FlowView, width: int,
+                           height: int, noc: int, radius: int, sigma: float, out_dtype: int, out_ptr: int,
+                           used_ptr: int = 0, fb: bool = False, alpha: float = 0.01, beta: float = 0.5,
+                           stream: int = 0) -> None:
+        """``ofdis_tfilter_radius_u8`` on raw device pointers (0: no `used` output); out_dtype IMG_U8 / IMG_F32."""
+        check(lib().ofdis_tfilter_radius_u8(self._h, frames_ptr or None, nframes, fw_ptr or None, bw_ptr or None,
+                                            None if view is None else C.byref(view), width, height, noc, radius, sigma,
+                                            int(bool(fb)), alpha, beta, out_dtype, out_ptr or None, used_ptr or None,
+                                            stream or None), "ofdis_tfilter_radius_u8")
+
+    def tfilter_radius(self, frames, flow_fw, flow_bw, sigma: float, radius: int, fb: bool = False, alpha: float = 0.01,
+                       beta: float = 0.5, out_dtype=None, want_used: bool = False, layout: str = "nhwc",
+                       grid: str = "full", p: Optional[Params] = None, size=None):
+        """``tfilter`` over `radius` (1 .. 4) frames on each side (the definition is in ofdis.h): a pixel's position is
+        chained through the fields as ``track_points`` chains a point, and every frame it passes is sampled there and
+        weighted as ``tfilter`` weights a neighbour.  With fb every chain step runs the forward-backward check at alpha,
+        beta, and a failed or out-of-frame step drops that frame and every farther one of its direction -- there are no
+        mask inputs.  frames, flow_fw, flow_bw, layout, grid, p, size and out_dtype are ``tfilter``'s.  Returns the
+        filtered frames, with want_used the tuple (frames, used uint8 [T, h, w]: bit 2 (k - 1) the k-th previous frame
+        contributed, bit 2 (k - 1) + 1 the k-th next)."""
+        import torch
+        _tfilter_checks("tfilter_radius", sigma, out_dtype, (None, torch.uint8, torch.float32))
+        _tfilter_radius_checks("tfilter_radius", radius, fb, alpha, beta)
+        gray = frames.dim() == 3
+        f4 = frames.unsqueeze(-1) if gray else frames
+        if (f4.dim() != 4 or f4.shape[-1] not in (1, 3) or f4.dtype != torch.uint8
+                or not (f4.is_cuda and flow_fw.is_cuda and flow_bw.is_cuda)):
+            raise ValueError("expected a uint8 CUDA tensor [T, h, w] or [T, h, w, 3] and two CUDA flow tensors")
+        t, h, w, noc = f4.shape
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "tfilter_radius: a video needs two frames or more")
+        if size is not None and (int(size[0]), int(size[1])) != (w, h):
+            raise ValueError(f"size {tuple(size)} is not the frames' {(w, h)}")
+        if flow_fw.dtype != flow_bw.dtype:
+            raise ValueError("the two flows must have one dtype")
+        fmt = out_format(flow_fw.dtype, layout, grid)
+        view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        if grid == "level":
+            if p is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT,
+                                 'tfilter_radius: grid="level" needs the parameters the flows were computed with')
+            g = out_geometry(p, w, h, False, flow_fw.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        want = (t - 1, 2, view.gh, view.gw) if fmt.layout else (t - 1, view.gh, view.gw, 2)
+        if tuple(flow_fw.shape) != want or tuple(flow_bw.shape) != want:
+            raise ValueError(f"flows have shapes {tuple(flow_fw.shape)} and {tuple(flow_bw.shape)}, expected {want}")
+        f32 = out_dtype == torch.float32
+        f4, flow_fw, flow_bw = f4.contiguous(), flow_fw.contiguous(), flow_bw.contiguous()
+        out = torch.empty(frames.shape, dtype=torch.float32 if f32 else torch.uint8, device=f4.device)
+        used = torch.empty((t, h, w), dtype=torch.uint8, device=f4.device) if want_used else None
+        self.tfilter_radius_ptr(f4.data_ptr(), t, flow_fw.data_ptr(), flow_bw.data_ptr(), view, w, h, noc, int(radius),
+                                float(sigma), IMG_F32 if f32 else IMG_U8, out.data_ptr(),
+                                used.data_ptr() if want_used else 0, fb, alpha, beta,
+                                torch.cuda.current_stream(f4.device).cuda_stream)
+        return (out, used) if want_used else out
+
+    def run_sequence_tfilter_radius_ptr(self, frames_ptr: int, nframes: int, width: int, height: int, p: Params,
+                                        radius: int, sigma: float, out_dtype: int, out_ptr: int, used_ptr: int = 0,
+                                        fb: bool = False, alpha: float = 0.01, beta: float = 0.5, stream: int = 0) -> None:
+        """``ofdis_run_sequence_tfilter_radius_u8`` on raw device pointers, asynchronous on `stream`: frames u8
+        [nframes, h, w, noc] -> the filtered frames (used_ptr 0: no `used` output); out_dtype IMG_U8 / IMG_F32."""
+        check(lib().ofdis_run_sequence_tfilter_radius_u8(self._h, frames_ptr or None, nframes, width, height, C.byref(p),
+                                                         radius, sigma, int(bool(fb)), alpha, beta, out_dtype,
+                                                         out_ptr or None, used_ptr or None, stream or None),
+              "ofdis_run_sequence_tfilter_radius_u8")
+
+    def run_sequence_tfilter_radius(self, frames, p: Params, sigma: float, radius: int, fb: bool = False,
+                                    alpha: float = 0.01, beta: float = 0.5, out_dtype=None, want_used: bool = False):
+        """The flows of a video and its frames filtered over `radius` frames on each side in one call: torch.uint8 CUDA
+        tensor [T, h, w] or [T, h, w, noc] -> the filtered frames in that shape (torch.uint8, or torch.float32), with
+        want_used the tuple (frames, used [T, h, w]).  Bit for bit
+        ``tfilter_radius(frames, *run_sequence(frames, p, bidir=True)[:2], sigma, radius, fb, alpha, beta)``, but the flows
+        stay on their level grids and the check runs inside the filter: no full-resolution flow and no mask is
+        written."""
+        import torch
+        _tfilter_checks("run_sequence_tfilter_radius", sigma, out_dtype, (None, torch.uint8, torch.float32))
+        _tfilter_radius_checks("run_sequence_tfilter_radius", radius, fb, alpha, beta)
+        f4 = frames.unsqueeze(-1) if frames.dim() == 3 else frames
+        if f4.dim() != 4 or f4.shape[-1] != p.noc or f4.dtype != torch.uint8 or not f4.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor with noc channels")
+        t, h, w, _ = f4.shape
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_tfilter_radius: a video needs two frames or more")
+        f32 = out_dtype == torch.float32
+        f4 = f4.contiguous()
+        out = torch.empty(frames.shape, dtype=torch.float32 if f32 else torch.uint8, device=f4.device)
+        used = torch.empty((t, h, w), dtype=torch.uint8, device=f4.device) if want_used else None
+        self.run_sequence_tfilter_radius_ptr(f4.data_ptr(), t, w, h, p, int(radius), float(sigma),
+                                             IMG_F32 if f32 else IMG_U8, out.data_ptr(),
+                                             used.data_ptr() if want_used else 0, fb, alpha, beta,
+                                             torch.cuda.current_stream(f4.device).cuda_stream)
+        return (out, used) if want_used else out
+
+    def run_sequence_tfilter_radius_host(self, frames: np.ndarray, p: Params, sigma: float, radius: int,
+                                         fb: bool = False, alpha: float = 0.01, beta: float = 0.5, out_dtype=np.uint8,
+                                         want_used: bool = False):
+        """run_sequence_tfilter_radius on a numpy u8 array [T, h, w] or [T, h, w, noc]; synchronous."""
+        _tfilter_checks("run_sequence_tfilter_radius_host", sigma, np.dtype(np.uint8 if out_dtype is None else out_dtype),
+                        (np.dtype(np.uint8), np.dtype(_f32)))
+        _tfilter_radius_checks("run_sequence_tfilter_radius_host", radius, fb, alpha, beta)
+        f4 = np.ascontiguousarray(frames[..., None] if frames.ndim == 3 else frames, np.uint8)
+        if f4.ndim != 4 or f4.shape[-1] != p.noc:
+            raise ValueError("expected a uint8 array with noc channels")
+        t, h, w = f4.shape[:3]
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_tfilter_radius_host: a video needs two frames or more")
+        f32 = out_dtype is not None and np.dtype(out_dtype) == _f32
+        out = np.empty(frames.shape, _f32 if f32 else np.uint8)
+        used = np.empty((t, h, w), np.uint8) if want_used else None
+        check(lib().ofdis_run_sequence_tfilter_radius_u8_host(self._h, f4.ctypes.data, t, w, h, C.byref(p), int(radius),
+                                                              float(sigma), int(bool(fb)), alpha, beta,
+                                                              IMG_F32 if f32 else IMG_U8, out.ctypes.data,
+                                                              used.ctypes.data if want_used else None),
+              "ofdis_run_sequence_tfilter_radius_u8_host")
+        return (out, used) if want_used else out
+
     def fit_motion_ptr(self, fw_ptr: int, bw_ptr: int, view: FlowView, m: int, width: int, height: int, model: int,
                        step: int, tau: float, iters: int, xform_ptr: int, support_ptr: int = 0, weights_ptr: int = 0,
                        alpha: float = 0.01, beta: float = 0.5, stream: int = 0) -> None:
@@ -1346,6 +1462,14 @@ def _tfilter_checks(what: str, sigma, out_dtype, dtypes) -> None:
         raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: out_dtype {out_dtype!r}")
 
 
+def _tfilter_radius_checks(what: str, radius, fb, alpha, beta) -> None:
+    """What the radius calls refuse beyond _tfilter_checks, before any library call (ofdis_tfilter_radius_u8's rules)."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 4:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: radius {radius!r} is not an integer in [1, 4]")
+    if fb and not (np.isfinite(float(alpha)) and np.isfinite(float(beta)) and float(alpha) >= 0 and float(beta) >= 0):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: thresholds alpha {alpha!r}, beta {beta!r}")
+
+
 def pixel_grid(width: int, height: int, step: int = 1) -> np.ndarray:
     """The pixel centres (x, y) of every `step`-th column and row of a width x height frame, row-major: float32 [N, 2],
     the points a dense tracking call starts from."""
@@ -1419,7 +1543,17 @@ def algorithmic_bytes(p: Params, width: int, height: int, kernel: str) -> float:
     return v.value
 
 
+def tfilter_radius_bytes(p: Params, width: int, height: int, radius: int, level: bool = False, f32: bool = False) -> float:
+    """``ofdis_tfilter_radius_bytes``: the byte model of the temporal filter over `radius` frames per interior output
+    frame, on full-resolution float32 views or (level) on level grids, with a u8 or (f32) a float32 picture."""
+    v = C.c_double()
+    check(lib().ofdis_tfilter_radius_bytes(C.byref(p), width, height, int(bool(level)), int(radius),
+                                           IMG_F32 if f32 else IMG_U8, C.byref(v)), "ofdis_tfilter_radius_bytes")
+    return v.value
+
+
 __all__ = ["OFClass", "Context", "Params", "oppoint", "params_from_strings", "validate", "synth_pair", "synth_shift_pair",
            "write_flo", "write_pfm", "write_pnm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
+           "tfilter_radius_bytes",
            "max_frames_per_launch", "out_geometry", "pixel_grid", "fit_lattice",
            "MODE_OF", "MODE_DE", "MOTION_TRANSLATION", "MOTION_SIMILARITY"]
