@@ -816,6 +816,76 @@ int ofdis_run_sequence_stabilize_u8_host(ofdis_context *ctx, const uint8_t *fram
                                          float alpha, float beta, int radius, double zoom, int out_dtype, void *out,
                                          uint8_t *valid, double *xform, double *corr, int32_t *support);
 
+/* ------------------------------------------------------------------ flow error against ground truth
+ *
+ * ofdis_flow_error scores n flow fields against n ground-truth fields on the device: the end-point error (EPE) sums,
+ * outlier counts, KITTI's Fl count, Sintel's speed classes, optionally the per-pixel error map and a histogram.  The
+ * definition fixes every operation and the order of every float64 sum, so the 16 numbers per pair are a pure function
+ * of the inputs, whatever the device does with the work (tests/test_flow_error.py restates it in numpy).
+ *
+ * flow / view: ofdis_track_points's rules -- a full view of either dtype and layout, or a level view that is float32
+ * interleaved (any other valid dtype / layout in a level view: OFDIS_ERR_UNSUPPORTED).  A level view stands for the
+ * float32 field it expands to, bit for bit, as ofdis_warp_u8 defines.  gt: float32 [n][H][W][2] -- the truth, or any
+ * other flow of a run when two estimates are compared.  mask: u8 [n][H][W] or NULL.  stats: double
+ * [n][OFDIS_FE_NSTATS].  err: float32 [n][H][W] or NULL.  hist: uint32 [n][OFDIS_FE_BINS] or NULL.  All device
+ * pointers.
+ *
+ * Per pixel, with (u, v) the estimate as float32 (binary16 converted exactly), (gu, gv) the truth and m the mask
+ * byte; all arithmetic float32, every operation rounded on its own (no fused multiply-add), sqrtf correctly rounded:
+ *   known   = fabsf(gu) <= 1e9f && fabsf(gv) <= 1e9f          (false for NaN; .flo files mark unknown flow with 1e10)
+ *   pass    = mask == NULL || (mask_eq < 0 ? m != 0 : m == mask_eq)
+ *             (mask_eq 0 with an occlusion mask of ofdis_run_bidir_u8: the consistent pixels, "EPE-noc"; -1 with a
+ *             KITTI-style valid mask: its nonzero pixels)
+ *   ok      = known && pass
+ *   fin     = isfinite(u) && isfinite(v)
+ *   du = u - gu;  dv = v - gv;  e = sqrtf(du * du + dv * dv);  g = sqrtf(gu * gu + gv * gv)
+ *   e       = fin ? e : +inf       (a select after the test: a non-finite estimate never reaches a sum)
+ *   counted = ok && fin
+ * stats of a pair (all counts exact integers stored as doubles):
+ *   [0] cnt = #ok                        [1] nonfinite = #(ok && !fin)
+ *   [2] Se = sum over counted of (double)e                [3] emax = max over counted of e (0 if none)
+ *   [4] #(ok && e > 1)   [5] #(ok && e > 3)   [6] #(ok && e > 5)      (a non-finite estimate counts in all three)
+ *   [7] fl = #(ok && e > 3 && e > 0.05f * g)              (KITTI's outlier rule without the division)
+ *   [8], [9]   count and sum of (double)e over counted pixels with g < 10
+ *   [10], [11] the same with 10 <= g < 40       [12], [13] the same with g >= 40       (Sintel's speed classes)
+ *   [14], [15] 0
+ * err: e at counted pixels, +inf where ok && !fin, -1 where !ok.
+ * hist: over ok pixels, bin e < 64 ? (int)(e * 16.0f) : OFDIS_FE_BINS - 1 -- bin 1023 also holds everything from
+ * 63.9375 px up and every non-finite estimate.  Integer counts: any order.
+ *
+ * Order of the four float64 sums ([2], [9], [11], [13]), L = OFDIS_FE_LANES.  A row y: for t in 0 .. L - 1,
+ * part[t] = ((0.0 + term(t)) + term(t + L)) + ... over the columns x = t + L k < W in ascending k; then for stride =
+ * L / 2, L / 4, ..., 1: part[i] = part[i] + part[i + stride] for every i < stride; the row's sum is part[0].  The
+ * frame: the same scheme over the row sums -- part[t] = ((0.0 + row[t]) + row[t + L]) + ..., the same tree, the sum is
+ * part[0].  A pixel that is not counted contributes nothing (every term is >= 0, so adding +0.0 for it gives the same
+ * bits).  No angular error: it needs acos, which numpy and the device do not share bit for bit.
+ *
+ * Refused before anything is enqueued (OFDIS_ERR_INVALID_ARGUMENT, the context stays usable): what
+ * ofdis_track_points refuses of a view and a size, NULL ctx / flow / view / gt / stats, n < 1, mask_eq outside
+ * -1 .. 255, width * height >= 2^31.  Stream and ordering rules are those of ofdis_fb_check; the per-row partial sums
+ * live in the context's workspace.  Timers "flow_error" (full views) / "flow_error_level" (level views) and
+ * "flow_error_sum" (the per-row partials to the 16 numbers). */
+#define OFDIS_FE_LANES  64     /* part of the definition: the summation order */
+#define OFDIS_FE_NSTATS 16
+#define OFDIS_FE_BINS   1024
+int ofdis_flow_error(ofdis_context *ctx, const void *flow, const ofdis_flow_view *view, const float *gt,
+                     const uint8_t *mask, int mask_eq, int n, int width, int height,
+                     double *stats, float *err, uint32_t *hist, void *stream);
+/* Flow and its error in one call: by definition ofdis_flow_error(ofdis_run_batch_u8(img_a, img_b), gt, ...) bit for
+ * bit.  The flow leaves the coarse-to-fine loop as the float32 level grid in the buffer the context owns, and the error
+ * launches follow the last chunk; no upsample runs and no full-resolution flow exists.  Optical flow only:
+ * OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED.  No initial flow.  A set stage capture is honoured as in
+ * ofdis_run_warp_u8.  Argument errors are those of ofdis_run_batch_u8 and of ofdis_flow_error; stream, ordering,
+ * chunking, round-robin, graph and workspace rules are those of ofdis_run_batch_u8 (the graph is recorded anew when an
+ * output pointer, the mask or mask_eq changes; a graph of another call kind is never replayed). */
+int ofdis_run_error_u8(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, const float *gt,
+                       const uint8_t *mask, int mask_eq, int n, int width, int height, const ofdis_params *p,
+                       double *stats, float *err, uint32_t *hist, void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_error_u8_host(ofdis_context *ctx, const uint8_t *img_a, const uint8_t *img_b, const float *gt,
+                            const uint8_t *mask, int mask_eq, int n, int width, int height, const ofdis_params *p,
+                            double *stats, float *err, uint32_t *hist);
+
 /* Device pyramid only (run_dense.cpp:131-179 + :299-312): writes, for each level s in [sc_l, sc_f],
  * padded image/dx/dy of frame 0 to host arrays (same layout as ofdis_oflow_compute's inputs). */
 int ofdis_pyramid_u8_host(ofdis_context *ctx, const uint8_t *img, int width, int height, const ofdis_params *p,
@@ -940,6 +1010,11 @@ int ofdis_context_kernel_time(ofdis_context *ctx, const char *name, double *tota
  * affine warp as "warp_affine"; the temporal filter over a radius as "tfilter_radius" with full-resolution flow views
  * and as "tfilter_radius_level" with level-grid views. */
 const char *ofdis_kernel_names(void);
+/* The names added after those of ofdis_kernel_names (whose list is closed: callers count it), comma-separated, in
+ * timer-slot order; ofdis_context_kernel_time and ofdis_algorithmic_bytes know both lists.  The flow error as
+ * "flow_error" with a full-resolution flow view and as "flow_error_level" with a level-grid view, and the reduction of
+ * its per-row partial sums as "flow_error_sum". */
+const char *ofdis_kernel_names_ext(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
  * bytes written ("level_out": the float32 level plane read and a float32 write).  "warp" / "warp_level": p->noc bytes
@@ -960,7 +1035,10 @@ const char *ofdis_kernel_names(void);
  * sample's expansion reads, ns * 72.  "smooth_path": six doubles per pair in and per frame out, 96.  "warp_affine": per
  * frame, noc bytes of image read, noc bytes of u8 output and the mask byte per pixel and the six doubles --
  * W * H * (2 noc + 1) + 48.  "tfilter_radius" / "tfilter_radius_level": ofdis_tfilter_radius_bytes at radius 1 with a
- * u8 picture (the counts of "tfilter" / "tfilter_level"). */
+ * u8 picture (the counts of "tfilter" / "tfilter_level").  "flow_error" / "flow_error_level": per pair, the float32
+ * estimate and the truth, W * H * 16 (the function has no mask argument: the mask byte, the error map and the
+ * histogram are not counted); with a level grid gw * gh * 8 + W * H * 8.  "flow_error_sum": the per-row partials read
+ * and the 16 doubles written, H * 80 + 128. */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 /* The same model for the temporal filter over a radius R (ofdis_tfilter_radius_u8), which depends on R and on the
  * picture's dtype: per interior output frame, in "tfilter"'s convention, each of the 2 R steps reads one field once (8

@@ -39,6 +39,10 @@ TRACK_LAST = 1
 MOTION_TRANSLATION, MOTION_SIMILARITY = 0, 1
 FIT_MAX_SAMPLES = 65536
 FIT_LANES = 256
+# ofdis_flow_error: OFDIS_FE_LANES (the summation order), OFDIS_FE_NSTATS, OFDIS_FE_BINS, and the slots of a pair's stats
+FE_LANES, FE_NSTATS, FE_BINS = 64, 16, 1024
+(FE_COUNT, FE_NONFINITE, FE_SUM, FE_MAX, FE_GT1, FE_GT3, FE_GT5, FE_FL,
+ FE_S0_COUNT, FE_S0_SUM, FE_S1_COUNT, FE_S1_SUM, FE_S2_COUNT, FE_S2_SUM) = range(14)
 
 
 class OfdisError(RuntimeError):
@@ -184,6 +188,10 @@ def lib():
         "ofdis_warp_affine_u8": ([vp, vp, i, i, i, i, vp, i, vp, vp, vp], i),
         "ofdis_run_sequence_stabilize_u8": ([vp, vp, i, i, i, P, i, i, d, i, i, f, f, i, d, i, vp, vp, vp, vp, vp, vp], i),
         "ofdis_run_sequence_stabilize_u8_host": ([vp, vp, i, i, i, P, i, i, d, i, i, f, f, i, d, i, vp, vp, vp, vp, vp], i),
+        "ofdis_flow_error": ([vp, vp, V, vp, vp, i, i, i, i, vp, vp, vp, vp], i),
+        "ofdis_run_error_u8": ([vp, vp, vp, vp, vp, i, i, i, i, P, vp, vp, vp, vp], i),
+        "ofdis_run_error_u8_host": ([vp, vp, vp, vp, vp, i, i, i, i, P, vp, vp, vp], i),
+        "ofdis_kernel_names_ext": ([], C.c_char_p),
         "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),

@@ -317,7 +317,35 @@ struct WarpAffineArgs {
   int out_f32;
 };
 
+// n flow fields scored against ground truth (include/ofdis.h: ofdis_flow_error).  The row kernel leaves one FeRow per
+// frame row in `rows`; launch_flow_error_sum folds them into the 16 numbers per pair.
+constexpr int kFeLanes = 64;   // OFDIS_FE_LANES: one wave per row, the pinned summation order
+constexpr int kFeStats = 16;   // OFDIS_FE_NSTATS
+constexpr int kFeBins = 1024;  // OFDIS_FE_BINS
+struct FeRow {
+  double sum[4];    // the row's tree sums: Se and the three speed classes' sums
+  uint32_t cnt[9];  // cnt, nonfinite, e > 1, e > 3, e > 5, fl, and the three speed classes' counts
+  float emax;
+  uint32_t pad[2];
+};
+static_assert(sizeof(FeRow) == 80, "the byte model and the workspace size count 80 bytes per row");
+struct FlowErrorArgs {
+  const void *flow;     // n fields back to back in the layouts of WarpArgs::flow
+  const float *gt;      // [n][H][W][2]
+  const uint8_t *mask;  // [n][H][W] or NULL
+  int mask_eq;          // < 0: nonzero bytes pass, else the bytes equal to it
+  FeRow *rows;          // [n][H]
+  double *stats;        // [n][16]
+  float *err;           // [n][H][W] or NULL
+  uint32_t *hist;       // [n][1024] or NULL, zeroed before the row kernel
+  int n, W, H;          // W * H < 2^31
+  int f16, planar, level;
+  int gw, gh, log2c, offx, offy;  // as WarpArgs
+};
+
 void launch_warp(const WarpArgs &a, hipStream_t s);
+void launch_flow_error(const FlowErrorArgs &a, hipStream_t s);
+void launch_flow_error_sum(const FlowErrorArgs &a, hipStream_t s);
 void launch_fit_motion(const FitArgs &a, hipStream_t s);
 void launch_smooth_path(const PathArgs &a, hipStream_t s);
 void launch_warp_affine(const WarpAffineArgs &a, hipStream_t s);

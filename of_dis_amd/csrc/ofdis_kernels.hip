@@ -45,6 +45,9 @@
 //   motion       k_fit_motion<FT, PLANAR, CACHE>, k_fit_motion_level<CACHE>  a robust similarity per flow field, float64,
 //                one workgroup per pair; k_smooth_path  pair transforms to per-frame corrections;
 //                k_warp_affine<OT, NOC, PX>  every frame through its own 2 x 3 transform (no reference code)
+//   flow error   k_flow_error<FT, PLANAR, MASK, HIST>, k_flow_error_level<MASK, HIST>  end-point error against ground
+//                truth, one wave per row, float64 sums in a pinned order; k_flow_error_sum  the rows of a pair to its
+//                16 numbers (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -7459,6 +7462,301 @@ void launch_warp_affine(const WarpAffineArgs &a0, hipStream_t s) {
     });
   }
 }
+
+// ------------------------------------------------------------------------------------------------ flow error
+// The score of include/ofdis.h (ofdis_flow_error): per pixel the end-point error against the truth in float32 (no
+// contraction, sqrt_nonneg is the correctly rounded sqrtf), per pair four float64 sums in a pinned order and ten
+// counts.  One wave owns one row: lane t takes the columns t, t + 64, ... in ascending order (consecutive lanes read
+// consecutive pixels), the 64 lane sums fold by lane shuffles in the definition's tree, and lane 0 leaves the row's
+// FeRow; k_flow_error_sum folds a pair's rows the same way.  Four rows per workgroup.
+//   k_flow_error<FT, PLANAR, MASK, HIST>  the estimate is a full-resolution field (float32 / binary16, interleaved / planar)
+//   k_flow_error_level<MASK, HIST>        the estimate is a float32 interleaved level grid: a pixel's (u, v) is the
+//                                         upsample's expression on its four cells (xtap, ytap, up_px_s's arithmetic), read
+//                                         at regular positions -- a wave's row touches two rows of cells
+//   k_flow_error_sum                      the per-row partials of a pair to its 16 numbers
+namespace {
+
+constexpr int kFeRowsPerBlock = 4;
+constexpr int kFeUnroll = 4;  // column steps whose loads are issued before the first of them is scored
+
+struct FeAcc {
+  double sum[4];
+  unsigned cnt[9];
+  float emax;
+};
+
+// One pixel into the lane's accumulators; returns what `err` holds for it.  bin: its histogram bin, -1 when !ok.
+__device__ __forceinline__ float fe_pixel(float u, float v, float gu, float gv, bool pass, FeAcc &A, int &bin) {
+  const bool known = fabsf(gu) <= 1e9f && fabsf(gv) <= 1e9f;  // false for NaN
+  const bool ok = known && pass;
+  const bool fin = __builtin_isfinite(u) && __builtin_isfinite(v);
+  const float du = u - gu, dv = v - gv;
+  const float e0 = sqrt_nonneg(du * du + dv * dv), g = sqrt_nonneg(gu * gu + gv * gv);
+  const float e = fin ? e0 : __builtin_inff();
+  const bool counted = ok && fin;
+  A.cnt[0] += ok;
+  A.cnt[1] += ok && !fin;
+  A.cnt[2] += ok && e > 1.0f;
+  A.cnt[3] += ok && e > 3.0f;
+  A.cnt[4] += ok && e > 5.0f;
+  A.cnt[5] += ok && e > 3.0f && e > 0.05f * g;
+  const int cls = g < 10.0f ? 0 : g < 40.0f ? 1 : 2;
+  if (counted) {  // (a pixel that is not counted contributes nothing)
+    const double ed = (double)e;
+    A.sum[0] = A.sum[0] + ed;
+    A.emax = fmaxf(A.emax, e);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (cls == k) {
+        A.cnt[6 + k] += 1;
+        A.sum[1 + k] = A.sum[1 + k] + ed;
+      }
+    }
+  }
+  bin = ok ? (e < 64.0f ? (int)(e * 16.0f) : kFeBins - 1) : -1;
+  return ok ? e : -1.0f;
+}
+
+// The definition's tree over the 64 lanes (part[i] += part[i + stride] for i < stride; the lanes from `stride` up hold
+// values nothing below them reads again), the counts and the maximum folded alongside; lane 0 stores the row.
+__device__ __forceinline__ void fe_fold_store(FeAcc &A, FeRow *row, int lane) {
+#pragma unroll
+  for (int stride = kFeLanes / 2; stride >= 1; stride >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) A.sum[k] = A.sum[k] + __shfl_down(A.sum[k], stride, kFeLanes);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) A.cnt[k] += __shfl_down(A.cnt[k], stride, kFeLanes);
+    A.emax = fmaxf(A.emax, __shfl_down(A.emax, stride, kFeLanes));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) row->sum[k] = A.sum[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) row->cnt[k] = A.cnt[k];
+    row->emax = A.emax;
+    row->pad[0] = row->pad[1] = 0u;
+  }
+}
+
+// The estimate of a full-resolution field at pixel o of a frame (plane = W H), binary16 converted exactly.
+template <class FT, bool PLANAR>
+struct FeFull {
+  const FT *F;
+  long plane;
+  __device__ __forceinline__ void at(int x, long o, float &u, float &v) const {
+    if constexpr (PLANAR) {
+      u = (float)F[o];
+      v = (float)F[plane + o];
+    } else if constexpr (std::is_same<FT, float>::value) {
+      const float2_u c = *reinterpret_cast<const float2_u *>(F + 2 * o);
+      u = c.x, v = c.y;
+    } else {
+      u = (float)F[2 * o];
+      v = (float)F[2 * o + 1];
+    }
+  }
+};
+
+// The estimate a level grid G ([gh][gw][2], the frame's) expands to in row y: k_warp_level's expression (xtap on column
+// x + off_x, ytap on row y + off_y, up_px_s) on cells read from the grid; cell = 1 the cell itself.
+struct FeLevel {
+  const float *R0, *R1;  // the two rows of cells of this output row (cell = 1: R0 is the row, from column off_x)
+  float b0, b1;
+  double scale;
+  int gw, log2c, offx;
+  __device__ __forceinline__ void row(const float *G, const FlowErrorArgs &a, int y) {
+    gw = a.gw, log2c = a.log2c, offx = a.offx;
+    scale = 1.0 / (double)(1 << a.log2c);
+    if (a.log2c == 0) {
+      R0 = R1 = G + 2 * ((long)(y + a.offy) * a.gw);
+      b0 = 1.f, b1 = 0.f;
+    } else {
+      const YTap yt = ytap(y + a.offy, scale, a.gh);
+      R0 = G + 2 * ((long)yt.r0 * a.gw);
+      R1 = G + 2 * ((long)yt.r1 * a.gw);
+      b0 = 1.f - yt.fy, b1 = yt.fy;
+    }
+  }
+  __device__ __forceinline__ void at(int x, long, float &u, float &v) const {
+    if (log2c == 0) {
+      const float2_u c = *reinterpret_cast<const float2_u *>(R0 + 2 * (long)(x + offx));
+      u = c.x, v = c.y;
+      return;
+    }
+    const XTap xt = xtap(x + offx, scale, gw);
+    const int sn = min(xt.sx + 1, gw - 1);  // (read only where xt.lin)
+    const float2_u s0 = *reinterpret_cast<const float2_u *>(R0 + 2 * xt.sx), n0 = *reinterpret_cast<const float2_u *>(R0 + 2 * sn);
+    const float2_u s1 = *reinterpret_cast<const float2_u *>(R1 + 2 * xt.sx), n1 = *reinterpret_cast<const float2_u *>(R1 + 2 * sn);
+    const float w0 = 1.f - xt.fx;
+    const float hu0 = xt.lin ? s0.x * w0 + n0.x * xt.fx : s0.x, hu1 = xt.lin ? s1.x * w0 + n1.x * xt.fx : s1.x;
+    const float hv0 = xt.lin ? s0.y * w0 + n0.y * xt.fx : s0.y, hv1 = xt.lin ? s1.y * w0 + n1.y * xt.fx : s1.y;
+    u = hu0 * b0 + hu1 * b1;
+    v = hv0 * b0 + hv1 * b1;
+  }
+};
+
+// Row y of frame f by the calling wave; src.at(x, o, u, v) gives the estimate at column x (o = y W + x).
+template <bool MASK, bool HIST, class S>
+__device__ __forceinline__ void fe_row(const FlowErrorArgs &a, const S &src, int f, int y, int lane, unsigned *bins) {
+  const long plane = (long)a.W * a.H, ro = (long)y * a.W;
+  const float *gt = a.gt + 2 * ((long)f * plane + ro);
+  const uint8_t *mk = MASK ? a.mask + (long)f * plane + ro : nullptr;
+  float *er = a.err ? a.err + (long)f * plane + ro : nullptr;
+  FeAcc A;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) A.sum[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) A.cnt[k] = 0u;
+  A.emax = 0.0f;
+  for (int x0 = lane; x0 < a.W; x0 += kFeLanes * kFeUnroll) {
+    float u[kFeUnroll], v[kFeUnroll], gu[kFeUnroll], gv[kFeUnroll];
+    unsigned m[kFeUnroll];
+#pragma unroll
+    for (int i = 0; i < kFeUnroll; ++i) {  // every load of the step before its arithmetic
+      const int x = x0 + i * kFeLanes;
+      u[i] = v[i] = gu[i] = gv[i] = 0.f;
+      m[i] = 0u;
+      if (x < a.W) {
+        src.at(x, ro + x, u[i], v[i]);
+        const float2_u g = *reinterpret_cast<const float2_u *>(gt + 2 * (long)x);
+        gu[i] = g.x, gv[i] = g.y;
+        if constexpr (MASK) m[i] = mk[x];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kFeUnroll; ++i) {  // scored in ascending column order: the lane's sum is the definition's chain
+      const int x = x0 + i * kFeLanes;
+      if (x < a.W) {
+        const bool pass = !MASK || (a.mask_eq < 0 ? m[i] != 0u : m[i] == (unsigned)a.mask_eq);
+        int bin;
+        const float e = fe_pixel(u[i], v[i], gu[i], gv[i], pass, A, bin);
+        if (er) er[x] = e;
+        if constexpr (HIST) {
+          if (bin >= 0) atomicAdd(&bins[bin], 1u);
+        }
+      }
+    }
+  }
+  fe_fold_store(A, a.rows + (long)f * a.H + y, lane);
+}
+
+// HIST: the workgroup's bins in LDS, then one global integer add per bin it filled.
+template <bool HIST>
+__device__ __forceinline__ void fe_hist_flush(const FlowErrorArgs &a, int f, const unsigned *bins) {
+  if constexpr (HIST) {
+    __syncthreads();
+    for (int b = threadIdx.x; b < kFeBins; b += 256)
+      if (bins[b]) atomicAdd(a.hist + (long)f * kFeBins + b, bins[b]);
+  }
+}
+
+template <class FT, bool PLANAR, bool MASK, bool HIST>
+__global__ __launch_bounds__(256) void k_flow_error(FlowErrorArgs a) {
+  __shared__ unsigned bins[HIST ? kFeBins : 1];
+  if constexpr (HIST) {
+    for (int b = threadIdx.x; b < kFeBins; b += 256) bins[b] = 0u;
+    __syncthreads();
+  }
+  const int f = blockIdx.z, lane = threadIdx.x & (kFeLanes - 1);
+  const int y = blockIdx.x * kFeRowsPerBlock + (threadIdx.x >> 6);
+  if (y < a.H) {
+    const long plane = (long)a.W * a.H;
+    const FeFull<FT, PLANAR> src{reinterpret_cast<const FT *>(a.flow) + (long)f * 2 * plane, plane};
+    fe_row<MASK, HIST>(a, src, f, y, lane, bins);
+  }
+  fe_hist_flush<HIST>(a, f, bins);
+}
+
+template <bool MASK, bool HIST>
+__global__ __launch_bounds__(256) void k_flow_error_level(FlowErrorArgs a) {
+  __shared__ unsigned bins[HIST ? kFeBins : 1];
+  if constexpr (HIST) {
+    for (int b = threadIdx.x; b < kFeBins; b += 256) bins[b] = 0u;
+    __syncthreads();
+  }
+  const int f = blockIdx.z, lane = threadIdx.x & (kFeLanes - 1);
+  const int y = blockIdx.x * kFeRowsPerBlock + (threadIdx.x >> 6);
+  if (y < a.H) {
+    FeLevel src;
+    src.row(reinterpret_cast<const float *>(a.flow) + (long)f * 2 * a.gw * a.gh, a, y);
+    fe_row<MASK, HIST>(a, src, f, y, lane, bins);
+  }
+  fe_hist_flush<HIST>(a, f, bins);
+}
+
+// One wave per pair: lane t chains the rows t, t + 64, ... in ascending order, then the row kernel's tree.
+__global__ __launch_bounds__(kFeLanes) void k_flow_error_sum(FlowErrorArgs a) {
+  const long f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const FeRow *rows = a.rows + f * a.H;
+  double sum[4] = {0.0, 0.0, 0.0, 0.0};
+  unsigned long long cnt[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) cnt[k] = 0ull;
+  float emax = 0.0f;
+  for (int y = lane; y < a.H; y += kFeLanes) {
+    const FeRow r = rows[y];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum[k] = sum[k] + r.sum[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cnt[k] += r.cnt[k];
+    emax = fmaxf(emax, r.emax);
+  }
+#pragma unroll
+  for (int stride = kFeLanes / 2; stride >= 1; stride >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum[k] = sum[k] + __shfl_down(sum[k], stride, kFeLanes);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cnt[k] += __shfl_down(cnt[k], stride, kFeLanes);
+    emax = fmaxf(emax, __shfl_down(emax, stride, kFeLanes));
+  }
+  if (lane == 0) {
+    double *o = a.stats + f * kFeStats;
+    o[0] = (double)cnt[0], o[1] = (double)cnt[1], o[2] = sum[0], o[3] = (double)emax;
+    o[4] = (double)cnt[2], o[5] = (double)cnt[3], o[6] = (double)cnt[4], o[7] = (double)cnt[5];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[8 + 2 * k] = (double)cnt[6 + k], o[9 + 2 * k] = sum[1 + k];
+    o[14] = o[15] = 0.0;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_flow_error_zero(uint32_t *hist, long count) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < count) hist[i] = 0u;
+}
+
+}  // namespace
+// ---- launch
+// The histogram is zeroed first (a kernel: the call may be recorded into a graph); frames go in grid z, 65535 per launch.
+void launch_flow_error(const FlowErrorArgs &a0, hipStream_t s) {
+  if (a0.hist) k_flow_error_zero<<<dim3(ceil_div((long)a0.n * kFeBins, 256)), 256, 0, s>>>(a0.hist, (long)a0.n * kFeBins);
+  const long frame = (long)a0.W * a0.H;
+  const long flow_frame = (a0.level ? (long)a0.gw * a0.gh : frame) * 2 * (a0.f16 ? 2 : 4);  // bytes
+  const int kSlice = 65535;  // grid z
+  for (int f0 = 0; f0 < a0.n; f0 += kSlice) {
+    FlowErrorArgs a = a0;
+    a.n = std::min(kSlice, a0.n - f0);
+    a.flow = (const char *)a0.flow + f0 * flow_frame;
+    a.gt += 2 * f0 * frame;
+    if (a.mask) a.mask += f0 * frame;
+    a.rows += (long)f0 * a0.H;
+    if (a.err) a.err += f0 * frame;
+    if (a.hist) a.hist += (long)f0 * kFeBins;
+    const dim3 grid(ceil_div(a.H, kFeRowsPerBlock), 1, a.n);
+    pick<0, 1>(a.mask ? 1 : 0, [&](auto MASK) {
+      pick<0, 1>(a.hist ? 1 : 0, [&](auto HIST) {
+        constexpr bool M = MASK != 0, Hs = HIST != 0;
+        if (a.level) k_flow_error_level<M, Hs><<<grid, 256, 0, s>>>(a);
+        else if (a.f16 && a.planar) k_flow_error<_Float16, true, M, Hs><<<grid, 256, 0, s>>>(a);
+        else if (a.f16) k_flow_error<_Float16, false, M, Hs><<<grid, 256, 0, s>>>(a);
+        else if (a.planar) k_flow_error<float, true, M, Hs><<<grid, 256, 0, s>>>(a);
+        else k_flow_error<float, false, M, Hs><<<grid, 256, 0, s>>>(a);
+      });
+    });
+  }
+}
+
+void launch_flow_error_sum(const FlowErrorArgs &a, hipStream_t s) { k_flow_error_sum<<<dim3(a.n), kFeLanes, 0, s>>>(a); }
 
 // Code-object warm-up: HIP loads a translation unit's code object on the first launch of any of its kernels, which
 // in a one-pair-per-process CLI would land inside the reference's first timer (TIME (Pyramide+Gradients),

@@ -51,6 +51,12 @@ const char *const kKernelNames[] = {"pyr_base", "pyr_down", "pyr_pad_grad", "pat
                                     "fit_motion", "fit_motion_level", "smooth_path", "warp_affine",
                                     // the temporal filter over a radius on full-resolution fields / on level grids
                                     "tfilter_radius", "tfilter_radius_level"};
+// The names after those (ofdis_kernel_names_ext): timer slots continue where kKernelNames ends.  The flow error on
+// full-resolution fields / on level grids, and the reduction of its per-row partials
+const char *const kKernelNamesExt[] = {"flow_error", "flow_error_level", "flow_error_sum"};
+constexpr int kNumKernelNames = (int)(sizeof(kKernelNames) / sizeof(kKernelNames[0]));
+constexpr int kSlotFlowError = kNumKernelNames, kSlotFlowErrorLevel = kNumKernelNames + 1,
+              kSlotFlowErrorSum = kNumKernelNames + 2;
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -121,7 +127,7 @@ struct ofdis_context {
   // payload of the call's family alone; the whole key is zeroed before it is filled and compared bytewise, padding
   // included, and the family tag keeps the keys of two families apart whatever their payloads hold.
   struct GraphKey {
-    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter, kStab, kTfilterRadius };
+    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter, kStab, kTfilterRadius, kError };
     // run_batch: ofdis_run_batch_u8*, bidir, stereo, sequence, the formatted calls and ofdis_run_warp_u8
     struct Batch {
       const void *flow_bw, *occ_fw, *occ_bw, *err_fw, *err_bw;  // the bidirectional / stereo call's extra outputs,
@@ -167,6 +173,11 @@ struct ofdis_context {
       int f32, radius, use_fb;
       float sigma, alpha, beta;
     };
+    // run_batch_error: the truth, the mask and its rule, the three outputs
+    struct Error {
+      const void *gt, *mask, *stats, *err, *hist;
+      int mask_eq;
+    };
     int family;
     int n, w, h;
     int seq, stride;  // a sequence call: `a` is one array of n + stride frames
@@ -180,6 +191,7 @@ struct ofdis_context {
       Tfilter tfilter;
       Stab stab;
       TfilterRadius tfilter_radius;
+      Error error;
     } u;
   } gkey{};
   hipGraphExec_t gexec = nullptr;
@@ -279,6 +291,8 @@ bool trace_on() {
 int kernel_index(const char *name) {
   for (int i = 0; i < (int)(sizeof(kKernelNames) / sizeof(kKernelNames[0])); ++i)
     if (std::strcmp(kKernelNames[i], name) == 0) return i;
+  for (int i = 0; i < (int)(sizeof(kKernelNamesExt) / sizeof(kKernelNamesExt[0])); ++i)
+    if (std::strcmp(kKernelNamesExt[i], name) == 0) return kNumKernelNames + i;
   return -1;
 }
 
@@ -3036,6 +3050,171 @@ int ofdis_run_sequence_stabilize_u8_host(ofdis_context *c, const uint8_t *frames
   return rc;
 }
 
+// ------------------------------------------------------------------ flow error against ground truth (include/ofdis.h)
+
+static_assert(OFDIS_FE_LANES == kFeLanes && OFDIS_FE_NSTATS == kFeStats && OFDIS_FE_BINS == kFeBins,
+              "the header's constants are the kernel's");
+
+namespace {
+// The truth, the mask rule and the outputs of an error call (ofdis_flow_error, ofdis_run_error_u8).
+struct ErrorIo {
+  const float *gt = nullptr;
+  const uint8_t *mask = nullptr;
+  int mask_eq = -1;
+  double *stats = nullptr;
+  float *err = nullptr;
+  uint32_t *hist = nullptr;
+};
+
+// What every error call checks of its size and scalars.
+bool error_io_ok(const ErrorIo &io, int n, int width, int height) {
+  return io.gt && io.stats && n >= 1 && width > 0 && height > 0 && (long)width * height <= 0x7fffffffL &&
+         io.mask_eq >= -1 && io.mask_eq <= 255;
+}
+
+// Bytes of the per-row partials of n pairs.
+size_t error_rows_bytes(int n, int height) { return (size_t)n * height * sizeof(FeRow); }
+
+// The n fields of view v scored (timer "flow_error_level" for a level-grid view, else "flow_error"), then their rows
+// folded ("flow_error_sum"); rows: error_rows_bytes of scratch.
+int run_flow_error(ofdis_context *c, const void *flow, const ofdis_flow_view &v, int n, int width, int height,
+                   const ErrorIo &io, void *rows, hipStream_t s) {
+  FlowErrorArgs fa{};
+  fa.flow = flow;
+  fa.gt = io.gt;
+  fa.mask = io.mask;
+  fa.mask_eq = io.mask_eq;
+  fa.rows = (FeRow *)rows;
+  fa.stats = io.stats;
+  fa.err = io.err;
+  fa.hist = io.hist;
+  fa.n = n;
+  fa.W = width;
+  fa.H = height;
+  fa.f16 = v.dtype == OFDIS_OUT_F16;
+  fa.planar = v.layout == OFDIS_OUT_PLANAR;
+  fa.level = v.grid == OFDIS_OUT_LEVEL;
+  if (fa.level) {
+    fa.gw = v.gw;
+    fa.gh = v.gh;
+    fa.offx = v.off_x;
+    fa.offy = v.off_y;
+    while ((1 << fa.log2c) < v.cell) ++fa.log2c;
+  }
+  timed(c, fa.level ? kSlotFlowErrorLevel : kSlotFlowError, s, [&] { launch_flow_error(fa, s); });
+  timed(c, kSlotFlowErrorSum, s, [&] { launch_flow_error_sum(fa, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// ofdis_run_error_u8 on stream s: run_batch's plan with the flow written as n float32 level grids into the context's
+// buffer and the per-row partials behind them.  Every chunk writes its share of the grids; after the chunks the two
+// error launches on s over all pairs.
+int run_batch_error(ofdis_context *c, hipStream_t s, const uint8_t *img_a, const uint8_t *img_b, int n, int width,
+                    int height, const ofdis_params *p, const ErrorIo &io) {
+  const bool capturing = !c->cap_dis.empty() || !c->cap_tv.empty();
+  CallPlan cp;
+  int rc = prepare(c, p, n, width, height, false, capturing, cp);
+  if (rc) return rc;
+  const ofdis_flow_view v = level_view(first_plan(cp));
+  cp.out_pair = level_grid_bytes(first_plan(cp));
+  const size_t grid_bytes = align_up((size_t)n * cp.out_pair);
+  if ((rc = ensure_warp_buf(c, grid_bytes + error_rows_bytes(n, height)))) return rc;  // (drops the graph before it grows)
+  char *grids = c->warp_buf, *rows = c->warp_buf + grid_bytes;
+  GraphKey key = graph_key(GraphKey::kError, c, img_a, img_b, nullptr, grids, grids, n, width, height, 0, p);
+  GraphKey::Error &ke = key.u.error;
+  ke.gt = io.gt; ke.mask = io.mask; ke.stats = io.stats; ke.err = io.err; ke.hist = io.hist;
+  ke.mask_eq = io.mask ? io.mask_eq : -1;  // (without a mask the rule is not read)
+  const size_t in_frame = (size_t)width * height * p->noc;
+  return replay_or_record(c, s, cp, key, [&](hipStream_t g) {
+    const int err = for_each_chunk(c, cp, g, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      return run_chunk_grids(c, ws, P, p, img_a + f0 * in_frame, img_b + f0 * in_frame, grids + f0 * cp.out_pair,
+                             nullptr, ls);
+    });
+    return err ? err : run_flow_error(c, grids, v, n, width, height, io, rows, g);
+  });
+}
+}  // namespace
+
+int ofdis_flow_error(ofdis_context *c, const void *flow, const ofdis_flow_view *v, const float *gt, const uint8_t *mask,
+                     int mask_eq, int n, int width, int height, double *stats, float *err, uint32_t *hist,
+                     void *stream) {
+  ErrorIo io;
+  io.gt = gt;
+  io.mask = mask;
+  io.mask_eq = mask_eq;
+  io.stats = stats;
+  io.err = err;
+  io.hist = hist;
+  if (!c || !flow || !v || !error_io_ok(io, n, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->grid == OFDIS_OUT_LEVEL && (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED))
+    return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_track_points)
+  if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  return device_call(c, stream, false, [&](hipStream_t s) {
+    const int rc = ensure_ws(c, error_rows_bytes(n, height));  // (the workspace is this call's until call_end)
+    return rc ? rc : run_flow_error(c, flow, *v, n, width, height, io, c->ws, s);
+  });
+}
+
+int ofdis_run_error_u8(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, const float *gt,
+                       const uint8_t *mask, int mask_eq, int n, int width, int height, const ofdis_params *p,
+                       double *stats, float *err, uint32_t *hist, void *stream) {
+  ErrorIo io;
+  io.gt = gt;
+  io.mask = mask;
+  io.mask_eq = mask_eq;
+  io.stats = stats;
+  io.err = err;
+  io.hist = hist;
+  if (!c || !img_a || !img_b || !p || !error_io_ok(io, n, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  const int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a disparity is not a flow view
+  return device_call(c, stream, false,
+                     [&](hipStream_t s) { return run_batch_error(c, s, img_a, img_b, n, width, height, p, io); });
+}
+
+int ofdis_run_error_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_t *img_b, const float *gt,
+                            const uint8_t *mask, int mask_eq, int n, int width, int height, const ofdis_params *p,
+                            double *stats, float *err, uint32_t *hist) {
+  if (!c || !img_a || !img_b || !gt || !stats || !p || n < 1 || width <= 0 || height <= 0 ||
+      (long)width * height > 0x7fffffffL || (p->noc != 1 && p->noc != 3))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t px = (size_t)n * width * height, in = px * p->noc;
+  // one device block: the two images, the truth, the mask, the numbers, the error map, the histogram (each at a
+  // multiple of 256 bytes)
+  const size_t off_b = align_up(in), off_gt = 2 * align_up(in), off_mask = off_gt + align_up(px * 8);
+  const size_t off_stats = off_mask + align_up(px), off_err = off_stats + align_up((size_t)n * kFeStats * 8);
+  const size_t off_hist = off_err + align_up(px * 4), hist_bytes = (size_t)n * kFeBins * 4;
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_hist + align_up(hist_bytes)));
+  int rc = OFDIS_OK;
+  auto step = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  if (step(hipMemcpyAsync(d, img_a, in, hipMemcpyHostToDevice, c->stream)) &&
+      step(hipMemcpyAsync(d + off_b, img_b, in, hipMemcpyHostToDevice, c->stream)) &&
+      step(hipMemcpyAsync(d + off_gt, gt, px * 8, hipMemcpyHostToDevice, c->stream)) &&
+      (!mask || step(hipMemcpyAsync(d + off_mask, mask, px, hipMemcpyHostToDevice, c->stream)))) {
+    rc = ofdis_run_error_u8(c, (const uint8_t *)d, (const uint8_t *)(d + off_b), (const float *)(d + off_gt),
+                            mask ? (const uint8_t *)(d + off_mask) : nullptr, mask_eq, n, width, height, p,
+                            (double *)(d + off_stats), err ? (float *)(d + off_err) : nullptr,
+                            hist ? (uint32_t *)(d + off_hist) : nullptr, c->stream);
+    if (rc == OFDIS_OK && step(hipStreamSynchronize(c->stream))) {
+      step(hipMemcpy(stats, d + off_stats, (size_t)n * kFeStats * 8, hipMemcpyDeviceToHost));
+      if (err) step(hipMemcpy(err, d + off_err, px * 4, hipMemcpyDeviceToHost));
+      if (hist) step(hipMemcpy(hist, d + off_hist, hist_bytes, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -3170,6 +3349,15 @@ const char *ofdis_kernel_names(void) {
   return names.c_str();
 }
 
+const char *ofdis_kernel_names_ext(void) {
+  static const std::string names = [] {
+    std::string r;
+    for (const char *k : kKernelNamesExt) r += (r.empty() ? "" : ",") + std::string(k);
+    return r;
+  }();
+  return names.c_str();
+}
+
 // The filter over a radius per interior output frame, in "tfilter"'s convention: per pixel the frame and the taps of
 // its 2 R neighbours ((2 R + 1) noc), the picture (noc, or 4 noc as float32) and the `used` byte; each of the 2 R steps
 // reads one field once -- 8 bytes per pixel of a full-resolution float32 view (16 R), or a level grid (the opposite
@@ -3192,8 +3380,7 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   const int novals = noc * p->p_samp_s * p->p_samp_s;
   double b = 0.0;
   const std::string k(kernel);
-  if (("," + std::string(ofdis_kernel_names()) + ",").find("," + k + ",") == std::string::npos)
-    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (kernel_index(kernel) < 0) return OFDIS_ERR_INVALID_ARGUMENT;
   for (const LevelGeom &g : P.lv) {
     const double px = (double)g.w * g.h;
     const int n_inner = p->usetvref ? p->tv_innerit * (g.level + 1) : 0;
@@ -3258,6 +3445,12 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   if (k == "smooth_path") b = 2.0 * 48.0;
   // the affine warp per frame: image taps and u8 picture (noc each) and the mask byte per pixel, and its six doubles
   if (k == "warp_affine") b = (double)width * height * (2.0 * noc + 1.0) + 48.0;
+  // the flow error per pair: the float32 estimate and the truth, 16 bytes per pixel (the function has no mask argument:
+  // the mask byte, the error map and the histogram are not counted); of a level grid its cells and the truth.  The
+  // reduction reads one FeRow per row and writes the 16 doubles
+  if (k == "flow_error") b = (double)width * height * 16.0;
+  if (k == "flow_error_level") b = (double)P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * 8.0;
+  if (k == "flow_error_sum") b = (double)height * sizeof(FeRow) + 8.0 * kFeStats;
   *bytes = b;
   return OFDIS_OK;
 }

@@ -14,9 +14,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, FIT_MAX_SAMPLES, IMG_F32, IMG_U8, MODE_DE, MODE_OF,
-                   MOTION_SIMILARITY, MOTION_TRANSLATION, TRACK_LAST, FlowView, OfdisError, OutFormat, Params, check, lib,
-                   out_format)
+from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, FE_BINS, FE_COUNT, FE_FL, FE_GT1, FE_GT3, FE_GT5, FE_MAX,
+                   FE_NONFINITE, FE_NSTATS, FE_S0_COUNT, FE_S0_SUM, FE_S1_COUNT, FE_S1_SUM, FE_S2_COUNT, FE_S2_SUM, FE_SUM,
+                   FIT_MAX_SAMPLES, IMG_F32, IMG_U8, MODE_DE, MODE_OF, MOTION_SIMILARITY, MOTION_TRANSLATION, TRACK_LAST,
+                   FlowView, OfdisError, OutFormat, Params, check, lib, out_format)
 
 _f32 = np.float32
 
@@ -1386,6 +1387,110 @@ class Context:
         res = [out] + ([valid] if want_valid else []) + ([xform, corr, support] if want_path else [])
         return tuple(res) if len(res) > 1 else out
 
+    def flow_error_ptr(self, flow_ptr: int, view: FlowView, gt_ptr: int, n: int, width: int, height: int,
+                       stats_ptr: int, mask_ptr: int = 0, mask_eq: int = -1, err_ptr: int = 0, hist_ptr: int = 0,
+                       stream: int = 0) -> None:
+        """``ofdis_flow_error`` on raw device pointers (0: no mask / that output is not wanted)."""
+        check(lib().ofdis_flow_error(self._h, flow_ptr or None, None if view is None else C.byref(view), gt_ptr or None,
+                                     mask_ptr or None, mask_eq, n, width, height, stats_ptr or None, err_ptr or None,
+                                     hist_ptr or None, stream or None), "ofdis_flow_error")
+
+    def flow_error(self, flow, gt, mask=None, mask_eq: int = -1, grid: str = "full", p: Optional[Params] = None,
+                   size=None, want_err: bool = False, want_hist: bool = False, layout: str = "nhwc"):
+        """n flow fields scored against ground truth on the device (the definition is in ofdis.h).  flow: any output of
+        ``run`` -- float32 or float16, layout "nhwc" / "nchw", grid "full" or "level" (float32 "nhwc" grids; needs `p`
+        and size = (width, height)).  gt: torch.float32 CUDA tensor [n, h, w, 2], unknown pixels marked by |value| >
+        1e9 or NaN.  mask: torch.uint8 [n, h, w] or None; mask_eq -1 keeps its nonzero pixels, 0 .. 255 the pixels
+        equal to it.  Returns stats, torch.float64 [n, 16] (indices ``FE_COUNT`` .. ``FE_S2_SUM``; ``error_summary``
+        reads them); with want_err also the error map float32 [n, h, w] (+inf: a non-finite estimate, -1: not scored),
+        with want_hist also uint32 counts [n, 1024] in bins of 1/16 px (as torch.int32 bits)."""
+        import torch
+        if not (flow.is_cuda and gt.is_cuda) or flow.dim() != 4 or gt.dim() != 4 or gt.dtype != torch.float32 or gt.shape[-1] != 2:
+            raise ValueError("expected a CUDA flow tensor of four dimensions and a float32 CUDA truth [n, h, w, 2]")
+        fmt = out_format(flow.dtype, layout, grid)
+        n, h, w, _ = gt.shape
+        if grid == "level":
+            if p is None or size is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'flow_error: grid="level" needs the parameters the flow was '
+                                 "computed with and the frame size")
+            if (int(size[0]), int(size[1])) != (w, h):
+                raise ValueError(f"size {tuple(size)} is not the truth's {(w, h)}")
+            g = out_geometry(p, w, h, False, flow.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        else:
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        want = (n, 2, view.gh, view.gw) if fmt.layout else (n, view.gh, view.gw, 2)
+        if tuple(flow.shape) != want:
+            raise ValueError(f"flow has shape {tuple(flow.shape)}, expected {want}")
+        mask = _error_mask(mask, (n, h, w), mask_eq, gt.device)
+        flow, gt = flow.contiguous(), gt.contiguous()
+        stats, err, hist = _error_outputs(n, h, w, want_err, want_hist, gt.device)
+        self.flow_error_ptr(flow.data_ptr(), view, gt.data_ptr(), n, w, h, stats.data_ptr(),
+                            mask.data_ptr() if mask is not None else 0, int(mask_eq), err.data_ptr() if want_err else 0,
+                            hist.data_ptr() if want_hist else 0, torch.cuda.current_stream(gt.device).cuda_stream)
+        res = [stats] + ([err] if want_err else []) + ([hist] if want_hist else [])
+        return tuple(res) if len(res) > 1 else stats
+
+    def run_error_ptr(self, a_ptr: int, b_ptr: int, gt_ptr: int, n: int, width: int, height: int, p: Params,
+                      stats_ptr: int, mask_ptr: int = 0, mask_eq: int = -1, err_ptr: int = 0, hist_ptr: int = 0,
+                      stream: int = 0) -> None:
+        """``ofdis_run_error_u8`` on raw device pointers, asynchronous on `stream` (0: no mask / output not wanted)."""
+        check(lib().ofdis_run_error_u8(self._h, a_ptr or None, b_ptr or None, gt_ptr or None, mask_ptr or None, mask_eq,
+                                       n, width, height, C.byref(p), stats_ptr or None, err_ptr or None,
+                                       hist_ptr or None, stream or None), "ofdis_run_error_u8")
+
+    def run_error(self, a, b, p: Params, gt, mask=None, mask_eq: int = -1, want_err: bool = False,
+                  want_hist: bool = False):
+        """Flow and its error in one call: torch.uint8 CUDA tensors [n, h, w] or [n, h, w, 3] and the truth as for
+        ``flow_error`` -> what ``flow_error(run(a, b, p), gt, ...)`` returns, bit for bit, but the flow stays on its
+        level grid: no full-resolution flow is written."""
+        import torch
+        a4, b4 = (a.unsqueeze(-1), b.unsqueeze(-1)) if a.dim() == 3 else (a, b)
+        if (a4.dim() != 4 or a4.shape[-1] != p.noc or a4.dtype != torch.uint8 or a.shape != b.shape
+                or b.dtype != torch.uint8 or not (a.is_cuda and b.is_cuda)):
+            raise ValueError("expected two uint8 CUDA tensors of one shape with noc channels")
+        n, h, w, _ = a4.shape
+        if not gt.is_cuda or gt.dtype != torch.float32 or tuple(gt.shape) != (n, h, w, 2):
+            raise ValueError(f"expected a float32 CUDA truth of shape {(n, h, w, 2)}")
+        mask = _error_mask(mask, (n, h, w), mask_eq, a.device)
+        a4, b4, gt = a4.contiguous(), b4.contiguous(), gt.contiguous()
+        stats, err, hist = _error_outputs(n, h, w, want_err, want_hist, a.device)
+        self.run_error_ptr(a4.data_ptr(), b4.data_ptr(), gt.data_ptr(), n, w, h, p, stats.data_ptr(),
+                           mask.data_ptr() if mask is not None else 0, int(mask_eq), err.data_ptr() if want_err else 0,
+                           hist.data_ptr() if want_hist else 0, torch.cuda.current_stream(a.device).cuda_stream)
+        res = [stats] + ([err] if want_err else []) + ([hist] if want_hist else [])
+        return tuple(res) if len(res) > 1 else stats
+
+    def run_error_host(self, a: np.ndarray, b: np.ndarray, p: Params, gt: np.ndarray, mask=None, mask_eq: int = -1,
+                       want_err: bool = False, want_hist: bool = False):
+        """run_error on numpy arrays; synchronous.  Images as for ``run_warp_host``; gt float32 [n, h, w, 2] ([h, w, 2]
+        for a single pair), mask u8 [n, h, w] or None.  stats is [n, 16], err [n, h, w], hist uint32 [n, 1024]."""
+        a = np.ascontiguousarray(a, np.uint8)
+        b = np.ascontiguousarray(b, np.uint8)
+        if a.shape != b.shape or a.ndim < 2 or a.ndim > 4:
+            raise ValueError("expected two uint8 arrays of one shape")
+        channels = a.ndim == 4 or (a.ndim == 3 and a.shape[-1] == p.noc and (p.noc == 3 or a.shape[-1] == 1))
+        if channels and a.shape[-1] != p.noc:
+            raise ValueError("expected noc channels")
+        h, w = a.shape[-3:-1] if channels else a.shape[-2:]
+        n = 1 if a.ndim == (3 if channels else 2) else a.shape[0]
+        gt = np.ascontiguousarray(gt, _f32)
+        if gt.size != n * h * w * 2:
+            raise ValueError(f"expected a truth of shape {(n, h, w, 2)}")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.size != n * h * w:
+                raise ValueError(f"expected a mask of shape {(n, h, w)}")
+        stats = np.empty((n, 16), np.float64)
+        err = np.empty((n, h, w), _f32) if want_err else None
+        hist = np.empty((n, 1024), np.uint32) if want_hist else None
+        check(lib().ofdis_run_error_u8_host(self._h, a.ctypes.data, b.ctypes.data, gt.ctypes.data,
+                                            mask.ctypes.data if mask is not None else None, int(mask_eq), n, w, h,
+                                            C.byref(p), stats.ctypes.data, err.ctypes.data if want_err else None,
+                                            hist.ctypes.data if want_hist else None), "ofdis_run_error_u8_host")
+        res = [stats] + ([err] if want_err else []) + ([hist] if want_hist else [])
+        return tuple(res) if len(res) > 1 else stats
+
     def pyramid_host(self, img: np.ndarray, p: Params, imgpadding: Optional[int] = None):
         """Device pyramid of one u8 image -> {scale: (img, dx, dy)} padded float arrays."""
         h, w = img.shape[:2]
@@ -1530,6 +1635,73 @@ def kernel_names():
     return lib().ofdis_kernel_names().decode().split(",")
 
 
+def kernel_names_ext():
+    """The timer names added after the closed list of ``kernel_names``, in slot order."""
+    return lib().ofdis_kernel_names_ext().decode().split(",")
+
+
+def _error_mask(mask, shape, mask_eq, device):
+    """The mask of an error call checked: torch.uint8 of `shape` on `device`, contiguous; mask_eq in -1 .. 255."""
+    import torch
+    if not -1 <= int(mask_eq) <= 255:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"mask_eq {mask_eq!r} is outside -1 .. 255")
+    if mask is None:
+        return None
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(shape) or mask.device != device:
+        raise ValueError(f"expected a uint8 mask of shape {tuple(shape)} on the truth's device")
+    return mask.contiguous()
+
+
+def _error_outputs(n: int, h: int, w: int, want_err: bool, want_hist: bool, device):
+    import torch
+    stats = torch.empty((n, FE_NSTATS), dtype=torch.float64, device=device)
+    err = torch.empty((n, h, w), dtype=torch.float32, device=device) if want_err else None
+    hist = torch.empty((n, FE_BINS), dtype=torch.int32, device=device) if want_hist else None  # (uint32 bits)
+    return stats, err, hist
+
+
+def error_summary(stats) -> dict:
+    """The readable figures of ``flow_error`` / ``run_error`` stats ([n, 16] or [16]; numpy, or a tensor copied to the
+    host).  Returns {"pairs": [one dict per pair], "pooled": dict}; pooling adds the pairs' sums, then their counts, in
+    ascending pair order.  Each dict: count, nonfinite, epe = Se / (count - nonfinite), r1 / r3 / r5 (the shares of
+    scored pixels with an error above 1, 3, 5 px) and fl (KITTI's outlier share) as fractions of count, epe_s0_10 /
+    epe_s10_40 / epe_s40 (Sintel's speed classes), max.  A figure whose denominator is 0 is NaN."""
+    s = np.asarray(stats.detach().cpu().numpy() if hasattr(stats, "detach") else stats, np.float64).reshape(-1, FE_NSTATS)
+
+    def one(r):
+        def div(a, b):
+            return float(a) / float(b) if b > 0 else float("nan")
+        return {"count": int(r[FE_COUNT]), "nonfinite": int(r[FE_NONFINITE]),
+                "epe": div(r[FE_SUM], r[FE_COUNT] - r[FE_NONFINITE]),
+                "r1": div(r[FE_GT1], r[FE_COUNT]), "r3": div(r[FE_GT3], r[FE_COUNT]), "r5": div(r[FE_GT5], r[FE_COUNT]),
+                "fl": div(r[FE_FL], r[FE_COUNT]),
+                "epe_s0_10": div(r[FE_S0_SUM], r[FE_S0_COUNT]), "epe_s10_40": div(r[FE_S1_SUM], r[FE_S1_COUNT]),
+                "epe_s40": div(r[FE_S2_SUM], r[FE_S2_COUNT]), "max": float(r[FE_MAX])}
+
+    pooled = np.zeros(FE_NSTATS, np.float64)
+    for r in s:  # ascending pair order: the pooled sums are a function of the stats alone
+        pooled = pooled + r
+    pooled[FE_MAX] = s[:, FE_MAX].max() if len(s) else 0.0
+    return {"pairs": [one(r) for r in s], "pooled": one(pooled)}
+
+
+def error_percentile(hist, q: float) -> float:
+    """The upper edge, in pixels, of the histogram bin holding the q-quantile (0 < q <= 1) of the scored errors: 1/16 px
+    resolution.  hist: [1024] or [n, 1024] counts (pooled over the pairs).  The last bin is open (63.9375 px and up, and
+    every non-finite estimate): its edge is +inf.  NaN for an empty histogram."""
+    if not 0.0 < q <= 1.0:
+        raise ValueError(f"q = {q!r} is outside (0, 1]")
+    h = np.asarray(hist.detach().cpu().numpy() if hasattr(hist, "detach") else hist)
+    h = h.view(np.uint32) if h.dtype == np.int32 else h
+    h = h.reshape(-1, FE_BINS).astype(np.uint64).sum(axis=0)
+    total = int(h.sum())
+    if total == 0:
+        return float("nan")
+    rank = max(int(np.ceil(q * total)), 1)  # the rank-th smallest error, 1-based
+    b = int(np.searchsorted(np.cumsum(h), rank, side="left"))
+    return float("inf") if b >= FE_BINS - 1 else (b + 1) / 16.0
+
+
 def max_frames_per_launch(p: Params, width: int, height: int) -> int:
     """Frames one launch of the refinement kernels takes at this size (32-bit plane-group offsets)."""
     v = C.c_int()
@@ -1554,6 +1726,6 @@ def tfilter_radius_bytes(p: Params, width: int, height: int, radius: int, level:
 
 __all__ = ["OFClass", "Context", "Params", "oppoint", "params_from_strings", "validate", "synth_pair", "synth_shift_pair",
            "write_flo", "write_pfm", "write_pnm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
-           "tfilter_radius_bytes",
+           "tfilter_radius_bytes", "kernel_names_ext", "error_summary", "error_percentile",
            "max_frames_per_launch", "out_geometry", "pixel_grid", "fit_lattice",
            "MODE_OF", "MODE_DE", "MOTION_TRANSLATION", "MOTION_SIMILARITY"]
