@@ -816,6 +816,75 @@ int ofdis_run_sequence_stabilize_u8_host(ofdis_context *ctx, const uint8_t *fram
                                          float alpha, float beta, int radius, double zoom, int out_dtype, void *out,
                                          uint8_t *valid, double *xform, double *corr, int32_t *support);
 
+/* ------------------------------------------------------------------ moving-object masks
+ *
+ * ofdis_motion_mask answers which pixels moved on their own: per pixel the distance of the flow estimate from the
+ * camera's flow there (the transform of ofdis_fit_motion), a threshold, and a binary median as clean-up.  All pointers
+ * are device pointers.  flow / view: ofdis_track_points's rules -- a full view of either dtype and layout; a level view
+ * must be float32 interleaved (any other valid enum value: OFDIS_ERR_UNSUPPORTED) and stands for the float32 field it
+ * expands to, as ofdis_warp_u8 defines.  xform: double [m][6] = (M00, M01, M02, M10, M11, M12), a position in frame j to
+ * frame j + 1.  occ: u8 [m][height][width] or NULL, ofdis_fb_check's occ_fw plane.  code: u8 [m][height][width]; res:
+ * float32 [m][height][width]; stats: int64 [m][OFDIS_MM_NSTATS]; each may be NULL, not all three.
+ *
+ * Per pixel (x, y) with the estimate (u, v) as float32 (binary16 converted exactly), every operation rounded on its own
+ * (no fused multiply-add), sqrtf correctly rounded:
+ *   pu = (float)(((M00 * (double)x + M01 * (double)y) + M02) - (double)x)     the bracket in float64
+ *   pv = (float)(((M10 * (double)x + M11 * (double)y) + M12) - (double)y)
+ *   du = u - pu;  dv = v - pv;  e = sqrtf(du * du + dv * dv);  g = sqrtf(pu * pu + pv * pv)
+ *   fin = isfinite(u) && isfinite(v);  e = fin ? e : +inf                    (a select after the test)
+ *   unknown = !fin || (occ != NULL && occ byte != 0)
+ *   b = !unknown && e > thr && e > rel * g                                   (false for a NaN e)
+ * Clean-up: over the (2 radius + 1)^2 window clipped to the frame (in-frame pixels only, no border replication), mov =
+ * the window pixels with b set, known = those that are not unknown, c = 2 * mov > known in integers; radius 0 gives
+ * c = b.
+ *   code = unknown ? 2 : (c ? 1 : 0)       the 0 / 1 / 2 conventions of the occlusion masks
+ *   res  = e                               +inf at a non-finite estimate, the canonical quiet NaN (0x7fc00000) for a NaN;
+ *                                          independent of occ and of the clean-up
+ *   stats of a pair, exact integers (any accumulation order gives the same values):
+ *     [0], [1], [2]   the counts of codes 0, 1, 2
+ *     [3] .. [6]      xmin, ymin, xmax, ymax of code 1; width, height, -1, -1 when there is none
+ *     [7]             the count of b, before the clean-up
+ *     [8], [9]        the sums of x and of y over code 1
+ *     [10], [11]      0
+ * Consequences: an exact similarity field under its own transform gives res of a few ulp of the flow's magnitude and
+ * all zeros in code; a NaN transform entry makes e NaN, hence b false and code 0 (2 where unknown), and res holds the
+ * NaN; rel plays the role of the 0.05 relative term in KITTI's Fl rule (a pixel of a fast pan moves on its own only if
+ * its residual also exceeds rel times the camera's flow there).
+ * Refused before anything is enqueued with OFDIS_ERR_INVALID_ARGUMENT (the context stays usable): whatever
+ * ofdis_track_points refuses of a view and a size; NULL ctx, flow, view or xform; all three outputs NULL; m < 1; thr not
+ * finite or outside [0, 65536]; rel not finite or outside [0, 16]; radius outside 0 .. 4; width * height >= 2^31.
+ * Stream and ordering rules are those of ofdis_fb_check; stats is reset on the stream before the kernel. */
+#define OFDIS_MM_NSTATS 12
+int ofdis_motion_mask(ofdis_context *ctx, const void *flow, const ofdis_flow_view *view, int m, int width, int height,
+                      const double *xform, const uint8_t *occ, float thr, float rel, int radius, uint8_t *code,
+                      float *res, int64_t *stats, void *stream);
+
+/* The flows of a video, its camera motion and the moving-object masks from one call: frames u8
+ * [nframes][height][width][noc], m = nframes - 1.  By definition code / res / stats / xform / support / occ ==
+ * ofdis_motion_mask(F, ofdis_fit_motion(F, use_fb ? B : NULL), use_fb ? occ_fw of ofdis_fb_check(F, B) : NULL) bit for
+ * bit, with F, B the fields of ofdis_run_sequence_u8(frames, stride 1) -- but every pair's flows leave the
+ * coarse-to-fine loop as float32 level grids in the buffer the context owns (without use_fb the forward chain alone is
+ * computed), and after the last chunk come the launches: the fit over all m pairs, with use_fb one ofdis_fb_check_level
+ * launch that writes occ_fw, and the mask kernel on the grids over all m pairs.  No upsample runs and no
+ * full-resolution flow exists.  xform [m][6], support [m] and occ [m][height][width] (written with use_fb alone) are
+ * optional outputs; those not asked for live behind the grids in that buffer.
+ * Optical flow only: OFDIS_MODE_DE returns OFDIS_ERR_UNSUPPORTED, and so does a call while a stage capture is set.  No
+ * initial flow.  verbosity is ignored.  Argument errors are those of ofdis_run_sequence_stabilize_u8's fit part
+ * (nframes < 2, the fit's scalars, with use_fb the threshold rules of ofdis_fb_check) and of ofdis_motion_mask; stream,
+ * ordering, chunking, round-robin, graph and workspace rules are those of ofdis_run_batch_u8 (the graph is recorded anew
+ * when an output pointer or any scalar of the call changes; a graph of another call kind is never replayed). */
+int ofdis_run_sequence_motion_mask_u8(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                      const ofdis_params *p, int model, int step, double tau, int iters, int use_fb,
+                                      float alpha, float beta, float thr, float rel, int radius, uint8_t *code,
+                                      float *res, int64_t *stats, double *xform, int32_t *support, uint8_t *occ,
+                                      void *stream);
+/* Same with host buffers (synchronous). */
+int ofdis_run_sequence_motion_mask_u8_host(ofdis_context *ctx, const uint8_t *frames, int nframes, int width, int height,
+                                           const ofdis_params *p, int model, int step, double tau, int iters,
+                                           int use_fb, float alpha, float beta, float thr, float rel, int radius,
+                                           uint8_t *code, float *res, int64_t *stats, double *xform, int32_t *support,
+                                           uint8_t *occ);
+
 /* ------------------------------------------------------------------ flow error against ground truth
  *
  * ofdis_flow_error scores n flow fields against n ground-truth fields on the device: the end-point error (EPE) sums,
@@ -1015,6 +1084,10 @@ const char *ofdis_kernel_names(void);
  * "flow_error" with a full-resolution flow view and as "flow_error_level" with a level-grid view, and the reduction of
  * its per-row partial sums as "flow_error_sum". */
 const char *ofdis_kernel_names_ext(void);
+/* Every timer name, comma-separated, in slot order: the two lists above and whatever later features add.  This list
+ * is open -- callers look names up in it and do not count it.  After the two lists: the motion mask as "motion_mask"
+ * with a full-resolution flow view and as "motion_mask_level" with a level-grid view (the reset of `stats` included). */
+const char *ofdis_kernel_names_all(void);
 
 /* Per-frame algorithmic byte counts of the §8(d) byte model for this workload.  The output kernels: the
  * bytes written ("level_out": the float32 level plane read and a float32 write).  "warp" / "warp_level": p->noc bytes
@@ -1038,7 +1111,9 @@ const char *ofdis_kernel_names_ext(void);
  * u8 picture (the counts of "tfilter" / "tfilter_level").  "flow_error" / "flow_error_level": per pair, the float32
  * estimate and the truth, W * H * 16 (the function has no mask argument: the mask byte, the error map and the
  * histogram are not counted); with a level grid gw * gh * 8 + W * H * 8.  "flow_error_sum": the per-row partials read
- * and the 16 doubles written, H * 80 + 128. */
+ * and the 16 doubles written, H * 80 + 128.  "motion_mask" / "motion_mask_level": per pair, the float32 estimate and
+ * the code byte, W * H * 9 (the function has no argument for them: the occlusion byte, one more per pixel, the residual
+ * map, four more, and the statistics are not counted); with a level grid gw * gh * 8 + W * H. */
 int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const char *kernel, double *bytes_per_frame);
 /* The same model for the temporal filter over a radius R (ofdis_tfilter_radius_u8), which depends on R and on the
  * picture's dtype: per interior output frame, in "tfilter"'s convention, each of the 2 R steps reads one field once (8

@@ -43,6 +43,8 @@ FIT_LANES = 256
 FE_LANES, FE_NSTATS, FE_BINS = 64, 16, 1024
 (FE_COUNT, FE_NONFINITE, FE_SUM, FE_MAX, FE_GT1, FE_GT3, FE_GT5, FE_FL,
  FE_S0_COUNT, FE_S0_SUM, FE_S1_COUNT, FE_S1_SUM, FE_S2_COUNT, FE_S2_SUM) = range(14)
+# ofdis_motion_mask: OFDIS_MM_NSTATS, the int64 numbers of a pair
+MM_NSTATS = 12
 
 
 class OfdisError(RuntimeError):
@@ -192,6 +194,10 @@ def lib():
         "ofdis_run_error_u8": ([vp, vp, vp, vp, vp, i, i, i, i, P, vp, vp, vp, vp], i),
         "ofdis_run_error_u8_host": ([vp, vp, vp, vp, vp, i, i, i, i, P, vp, vp, vp], i),
         "ofdis_kernel_names_ext": ([], C.c_char_p),
+        "ofdis_kernel_names_all": ([], C.c_char_p),
+        "ofdis_motion_mask": ([vp, vp, V, i, i, i, vp, vp, f, f, i, vp, vp, vp, vp], i),
+        "ofdis_run_sequence_motion_mask_u8": ([vp, vp, i, i, i, P, i, i, d, i, i, f, f, f, f, i, vp, vp, vp, vp, vp, vp, vp], i),
+        "ofdis_run_sequence_motion_mask_u8_host": ([vp, vp, i, i, i, P, i, i, d, i, i, f, f, f, f, i, vp, vp, vp, vp, vp, vp], i),
         "ofdis_write_pnm": ([C.c_char_p, vp, i, i, i], i),
         "ofdis_pyramid_u8_host":([vp, vp, i, i, P, i, vp, vp, vp], i),
         "ofdis_context_set_stage_capture": ([vp, vp, vp, i], i),

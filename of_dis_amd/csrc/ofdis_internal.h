@@ -343,7 +343,27 @@ struct FlowErrorArgs {
   int gw, gh, log2c, offx, offy;  // as WarpArgs
 };
 
+// m flow fields classified against the camera's motion (include/ofdis.h: ofdis_motion_mask).  A workgroup owns a
+// kMmTileW x kMmTileH tile of pixels and classifies it with a halo of `radius`.
+constexpr int kMmStats = 12;     // OFDIS_MM_NSTATS
+constexpr int kMmMaxRadius = 4;  // the halo the tile's LDS planes are sized for
+constexpr int kMmTileW = 64, kMmTileH = 16;
+struct MotionMaskArgs {
+  const void *flow;     // m fields back to back in the layouts of WarpArgs::flow
+  const double *xform;  // [m][6]
+  const uint8_t *occ;   // [m][H][W] or NULL
+  uint8_t *code;        // [m][H][W] or NULL
+  float *res;           // [m][H][W] or NULL
+  int64_t *stats;       // [m][12] or NULL, reset before the mask kernel
+  int m, W, H;          // W * H < 2^31
+  float thr, rel;
+  int radius;           // 0 .. kMmMaxRadius
+  int f16, planar, level;
+  int gw, gh, log2c, offx, offy;  // as WarpArgs
+};
+
 void launch_warp(const WarpArgs &a, hipStream_t s);
+void launch_motion_mask(const MotionMaskArgs &a, hipStream_t s);
 void launch_flow_error(const FlowErrorArgs &a, hipStream_t s);
 void launch_flow_error_sum(const FlowErrorArgs &a, hipStream_t s);
 void launch_fit_motion(const FitArgs &a, hipStream_t s);

@@ -48,6 +48,8 @@
 //   flow error   k_flow_error<FT, PLANAR, MASK, HIST>, k_flow_error_level<MASK, HIST>  end-point error against ground
 //                truth, one wave per row, float64 sums in a pinned order; k_flow_error_sum  the rows of a pair to its
 //                16 numbers (no reference code)
+//   motion mask  k_motion_mask<FT, PLANAR>, k_motion_mask_level  pixels that move against the camera's motion: a tile
+//                and its halo classified in LDS, a separable binary median, integer statistics (no reference code)
 //   k_init_area (initial flow, OpenCV resizeAreaFast) and k_warm_kernels (code-object warm-up) close the file
 #include "ofdis_internal.h"
 #include "ofdis_math.h"
@@ -7757,6 +7759,266 @@ void launch_flow_error(const FlowErrorArgs &a0, hipStream_t s) {
 }
 
 void launch_flow_error_sum(const FlowErrorArgs &a, hipStream_t s) { k_flow_error_sum<<<dim3(a.n), kFeLanes, 0, s>>>(a); }
+
+// ------------------------------------------------------------------------------------------------ motion mask
+// The segmentation of include/ofdis.h (ofdis_motion_mask): per pixel the distance of the estimate from the camera's
+// flow there (the transform's bracket in float64, the rest in float32, no contraction, sqrt_nonneg is the correctly
+// rounded sqrtf), a raw class, and a binary median over a clipped (2 radius + 1)^2 window.  A workgroup owns a
+// kMmTileW x kMmTileH tile.  Thread k classifies the cells k, k + 256, ... of the tile and its halo of `radius` in
+// row-major order (consecutive lanes read consecutive pixels) into one byte each in LDS -- bit 0: b, bit 1: known; a
+// cell outside the frame holds 0 and so counts in neither sum -- and keeps the tile's residuals in LDS.  The window
+// counts are separable: per halo row and tile column the row sums of both bits packed in 16 bits (b in the low byte,
+// known in the high one, at most 9 each), then each thread adds the 2 radius + 1 row sums above and below its four
+// pixels as one 64-bit integer (four 16-bit fields, at most 81 per byte: no carry) and stores four codes as one dword
+// and four residuals as one 16-byte vector (W % 4 == 0 and aligned pointers: launch_motion_mask; else pixel by pixel).
+// The class plane never reaches global memory.  stats: integer partials fold over the wave by lane shuffles, over the
+// four waves in LDS, and thread 0 leaves one 64-bit integer add or min / max per entry the tile changes.
+//   k_motion_mask<FT, PLANAR>  the estimate is a full-resolution field (float32 / binary16, interleaved / planar)
+//   k_motion_mask_level        the estimate is a float32 interleaved level grid: the cells under tile and halo are
+//                              staged in LDS and expanded with the upsample's taps (xtap, ytap, up_px_s)
+namespace {
+
+constexpr int kMmHaloW = kMmTileW + 2 * kMmMaxRadius, kMmHaloH = kMmTileH + 2 * kMmMaxRadius;
+constexpr int kMmSrcRows = kMmHaloH / 2 + 3;  // cell >= 2: the rows of cells under kMmHaloH pixel rows, both taps
+constexpr int kMmSrcCols = kMmHaloW / 2 + 4;  // the columns likewise; one spare
+static_assert(kMmTileW == 64 && kMmTileH * (kMmTileW / 4) == 256, "four pixels per thread, 256 threads per tile");
+
+// The LDS planes of a tile.
+struct MmLds {
+  alignas(16) unsigned short rs[kMmHaloH * kMmTileW];  // row sums, [halo row][tile column]; read four at a time
+  alignas(16) float e[kMmTileH * kMmTileW];            // the tile's residuals; read four at a time
+  uint8_t cls[kMmHaloH * kMmHaloW];                    // raw classes, [halo row][halo column] at the call's radius
+  long long red[4][2];                                 // the waves' partial sums of x and y
+  int redi[4][8];                                      // the waves' counts and box
+};
+
+// One pixel: bit 0 b, bit 1 known; e: what `res` holds for it (the canonical quiet NaN for a NaN).
+__device__ __forceinline__ unsigned mm_pixel(const double (&M)[6], int x, int y, float u, float v, bool occluded,
+                                             float thr, float rel, float &e) {
+  const double xd = (double)x, yd = (double)y;
+  const float pu = (float)(((M[0] * xd + M[1] * yd) + M[2]) - xd);
+  const float pv = (float)(((M[3] * xd + M[4] * yd) + M[5]) - yd);
+  const float du = u - pu, dv = v - pv;
+  const float e0 = sqrt_nonneg(du * du + dv * dv), g = sqrt_nonneg(pu * pu + pv * pv);
+  const bool fin = __builtin_isfinite(u) && __builtin_isfinite(v);
+  const float e1 = fin ? e0 : __builtin_inff();
+  e = e1 != e1 ? __builtin_nanf("") : e1;
+  const bool unknown = !fin || occluded;
+  const bool b = !unknown && e1 > thr && e1 > rel * g;  // (false for a NaN e1)
+  return (b ? 1u : 0u) | (unknown ? 0u : 2u);
+}
+
+template <class FT, bool PLANAR>
+struct MmFull {
+  FeFull<FT, PLANAR> f;
+  __device__ __forceinline__ void at(int x, int, long o, float &u, float &v) const { f.at(x, o, u, v); }
+};
+
+// The field a level grid expands to, from the cells staged for the tile at (tx0, ty0) and its halo: k_warp_level's
+// expression (xtap on column x + off_x, ytap on row y + off_y, up_px_s on the staged rows); cell = 1: the cell itself.
+struct MmLevel {
+  float (*src)[2][kMmSrcCols];  // [row][comp][col]
+  const float *G;               // the frame's grid
+  double scale;
+  int gw, gh, log2c, offx, offy, r_first, c_lo, nr;
+  __device__ __forceinline__ void stage(const MotionMaskArgs &a, int tx0, int ty0) {
+    gw = a.gw, gh = a.gh, log2c = a.log2c, offx = a.offx, offy = a.offy;
+    scale = 1.0 / (double)(1 << a.log2c);
+    r_first = c_lo = 0, nr = 1;
+    if (a.log2c == 0) return;
+    const int ya = max(ty0 - a.radius, 0), yb = min(ty0 + kMmTileH - 1 + a.radius, a.H - 1);
+    const int xa = max(tx0 - a.radius, 0), xb = min(tx0 + kMmTileW - 1 + a.radius, a.W - 1);
+    r_first = ytap(ya + offy, scale, gh).r0;
+    nr = min(ytap(yb + offy, scale, gh).r1 - r_first + 1, kMmSrcRows);
+    c_lo = xtap(xa + offx, scale, gw).sx;
+    const int ncol = min(min(xtap(xb + offx, scale, gw).sx + 1, gw - 1) - c_lo + 1, kMmSrcCols);
+    for (int k = threadIdx.x; k < nr * 2 * ncol; k += 256) {
+      const int col = k % ncol, rc = k / ncol;  // rc = row * 2 + comp
+      src[rc >> 1][rc & 1][col] = G[2 * ((long)(r_first + (rc >> 1)) * gw + (c_lo + col)) + (rc & 1)];
+    }
+    __syncthreads();
+  }
+  __device__ __forceinline__ void at(int x, int y, long, float &u, float &v) const {
+    if (log2c == 0) {
+      const float2_u c = *reinterpret_cast<const float2_u *>(G + 2 * ((long)(y + offy) * gw + (x + offx)));
+      u = c.x, v = c.y;
+      return;
+    }
+    XTap xt = xtap(x + offx, scale, gw);
+    xt.sx = min(max(xt.sx - c_lo, 0), kMmSrcCols - 2);  // (inside the staged window by construction)
+    const YTap yt = ytap(y + offy, scale, gh);
+    const int j0 = min(max(yt.r0 - r_first, 0), nr - 1), j1 = min(max(yt.r1 - r_first, 0), nr - 1);
+    const float b0 = 1.f - yt.fy, b1 = yt.fy;
+    u = up_px_s(src[j0][0], src[j1][0], xt, b0, b1);
+    v = up_px_s(src[j0][1], src[j1][1], xt, b0, b1);
+  }
+};
+
+// The tile at (tx0, ty0) of pair f; src.at(x, y, o, u, v) gives the estimate at pixel (x, y) of the frame (o = y W + x).
+template <class S>
+__device__ __forceinline__ void mm_tile(const MotionMaskArgs &a, const S &src, int f, int tx0, int ty0, int vec,
+                                        MmLds &L) {
+  const int W = a.W, H = a.H, R = a.radius, hw = kMmTileW + 2 * R, hh = kMmTileH + 2 * R;
+  const int tid = threadIdx.x;
+  const long plane = (long)W * H;
+  double M[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) M[k] = a.xform[(long)f * 6 + k];
+  const uint8_t *occ = a.occ ? a.occ + (long)f * plane : nullptr;
+  for (int k = tid; k < hw * hh; k += 256) {
+    const int ry = k / hw, rx = k - ry * hw;
+    const int x = tx0 - R + rx, y = ty0 - R + ry;
+    unsigned c = 0u;
+    if (x >= 0 && x < W && y >= 0 && y < H) {
+      const long o = (long)y * W + x;
+      float u, v, e;
+      src.at(x, y, o, u, v);
+      c = mm_pixel(M, x, y, u, v, occ && occ[o] != 0, a.thr, a.rel, e);
+      if (rx >= R && rx < R + kMmTileW && ry >= R && ry < R + kMmTileH) L.e[(ry - R) * kMmTileW + (rx - R)] = e;
+    }
+    L.cls[k] = (uint8_t)c;
+  }
+  __syncthreads();
+  for (int k = tid; k < hh * kMmTileW; k += 256) {
+    const int ry = k / kMmTileW, cx = k % kMmTileW;
+    unsigned s = 0u;
+    for (int d = 0; d <= 2 * R; ++d) {
+      const unsigned c = L.cls[ry * hw + cx + d];
+      s += (c & 1u) | ((c & 2u) << 7);
+    }
+    L.rs[k] = (unsigned short)s;
+  }
+  __syncthreads();
+  const int tcx = 4 * (tid & 15), trow = tid >> 4;
+  const int x0 = tx0 + tcx, y = ty0 + trow;
+  unsigned long long acc = 0ull;
+  for (int d = 0; d <= 2 * R; ++d) acc += *reinterpret_cast<const unsigned long long *>(&L.rs[(trow + d) * kMmTileW + tcx]);
+  unsigned codes = 0u, n[4] = {0u, 0u, 0u, 0u};  // the counts of codes 0, 1, 2 and of b
+  int bx0 = 0x7fffffff, by0 = 0x7fffffff, bx1 = -1, by1 = -1;
+  long long sx = 0, sy = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned s = (unsigned)(acc >> (16 * i)) & 0xffffu, mov = s & 0xffu, known = s >> 8;
+    const unsigned own = L.cls[(trow + R) * hw + tcx + i + R];
+    const unsigned code = own & 2u ? (2u * mov > known ? 1u : 0u) : 2u;
+    codes |= code << (8 * i);
+    if (y < H && x0 + i < W) {
+      n[0] += code == 0u, n[1] += code == 1u, n[2] += code == 2u;
+      n[3] += own & 1u;
+      if (code == 1u) {
+        bx0 = min(bx0, x0 + i), bx1 = max(bx1, x0 + i), by0 = min(by0, y), by1 = max(by1, y);
+        sx += x0 + i, sy += y;
+      }
+    }
+  }
+  if (y < H && x0 < W) {
+    const long o = (long)f * plane + (long)y * W + x0;
+    if (vec) {  // (W % 4 == 0: the four pixels are in the frame)
+      if (a.code) *reinterpret_cast<unsigned *>(a.code + o) = codes;
+      if (a.res) *reinterpret_cast<float4_v *>(a.res + o) = *reinterpret_cast<const float4_v *>(&L.e[trow * kMmTileW + tcx]);
+    } else {
+      for (int i = 0; i < 4 && x0 + i < W; ++i) {
+        if (a.code) a.code[o + i] = (uint8_t)(codes >> (8 * i));
+        if (a.res) a.res[o + i] = L.e[trow * kMmTileW + tcx + i];
+      }
+    }
+  }
+  if (!a.stats) return;  // (uniform)
+#pragma unroll
+  for (int stride = 32; stride >= 1; stride >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) n[k] += __shfl_down(n[k], stride, 64);
+    bx0 = min(bx0, __shfl_down(bx0, stride, 64)), by0 = min(by0, __shfl_down(by0, stride, 64));
+    bx1 = max(bx1, __shfl_down(bx1, stride, 64)), by1 = max(by1, __shfl_down(by1, stride, 64));
+    sx += __shfl_down(sx, stride, 64), sy += __shfl_down(sy, stride, 64);
+  }
+  if ((tid & 63) == 0) {
+    const int w = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) L.redi[w][k] = (int)n[k];
+    L.redi[w][4] = bx0, L.redi[w][5] = by0, L.redi[w][6] = bx1, L.redi[w][7] = by1;
+    L.red[w][0] = sx, L.red[w][1] = sy;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) n[k] += (unsigned)L.redi[w][k];
+      bx0 = min(bx0, L.redi[w][4]), by0 = min(by0, L.redi[w][5]);
+      bx1 = max(bx1, L.redi[w][6]), by1 = max(by1, L.redi[w][7]);
+      sx += L.red[w][0], sy += L.red[w][1];
+    }
+    long long *st = reinterpret_cast<long long *>(a.stats) + (long)f * kMmStats;
+    auto add = [&](int k, long long v) {
+      if (v) atomicAdd(reinterpret_cast<unsigned long long *>(st + k), (unsigned long long)v);
+    };
+    add(0, n[0]), add(1, n[1]), add(2, n[2]), add(7, n[3]);
+    if (n[1]) {
+      atomicMin(st + 3, (long long)bx0), atomicMin(st + 4, (long long)by0);
+      atomicMax(st + 5, (long long)bx1), atomicMax(st + 6, (long long)by1);
+      add(8, sx), add(9, sy);
+    }
+  }
+}
+
+template <class FT, bool PLANAR>
+__global__ __launch_bounds__(256) void k_motion_mask(MotionMaskArgs a, int vec) {
+  __shared__ MmLds L;
+  const unsigned ntx = ((unsigned)a.W + kMmTileW - 1) / kMmTileW;
+  const int f = blockIdx.z, tx0 = (int)(blockIdx.x % ntx) * kMmTileW, ty0 = (int)(blockIdx.x / ntx) * kMmTileH;
+  const long plane = (long)a.W * a.H;
+  const MmFull<FT, PLANAR> src{{reinterpret_cast<const FT *>(a.flow) + (long)f * 2 * plane, plane}};
+  mm_tile(a, src, f, tx0, ty0, vec, L);
+}
+
+__global__ __launch_bounds__(256) void k_motion_mask_level(MotionMaskArgs a, int vec) {
+  __shared__ MmLds L;
+  __shared__ float cells[kMmSrcRows][2][kMmSrcCols];
+  const unsigned ntx = ((unsigned)a.W + kMmTileW - 1) / kMmTileW;
+  const int f = blockIdx.z, tx0 = (int)(blockIdx.x % ntx) * kMmTileW, ty0 = (int)(blockIdx.x / ntx) * kMmTileH;
+  MmLevel src;
+  src.src = cells;
+  src.G = reinterpret_cast<const float *>(a.flow) + (long)f * 2 * a.gw * a.gh;
+  src.stage(a, tx0, ty0);
+  mm_tile(a, src, f, tx0, ty0, vec, L);
+}
+
+// stats before the tiles: zero counts and sums, the empty box (W, H, -1, -1).
+__global__ __launch_bounds__(256) void k_motion_mask_reset(int64_t *stats, long count, int W, int H) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const int k = (int)(i % kMmStats);
+  stats[i] = k == 3 ? W : k == 4 ? H : (k == 5 || k == 6) ? -1 : 0;
+}
+
+}  // namespace
+// ---- launch
+// stats is reset first (a kernel: the call may be recorded into a graph); pairs go in grid z, 65535 per launch, a
+// frame's tiles in grid x.
+void launch_motion_mask(const MotionMaskArgs &a0, hipStream_t s) {
+  if (a0.stats)
+    k_motion_mask_reset<<<dim3(ceil_div((long)a0.m * kMmStats, 256)), 256, 0, s>>>(a0.stats, (long)a0.m * kMmStats, a0.W, a0.H);
+  const long frame = (long)a0.W * a0.H;
+  const long flow_frame = (a0.level ? (long)a0.gw * a0.gh : frame) * 2 * (a0.f16 ? 2 : 4);  // bytes
+  const int vec = a0.W % 4 == 0 && (uintptr_t)a0.code % 4 == 0 && (uintptr_t)a0.res % 16 == 0;
+  const int kSlice = 65535;  // grid z
+  for (int f0 = 0; f0 < a0.m; f0 += kSlice) {
+    MotionMaskArgs a = a0;
+    a.m = std::min(kSlice, a0.m - f0);
+    a.flow = (const char *)a0.flow + f0 * flow_frame;
+    a.xform += (long)f0 * 6;
+    if (a.occ) a.occ += f0 * frame;
+    if (a.code) a.code += f0 * frame;
+    if (a.res) a.res += f0 * frame;
+    if (a.stats) a.stats += (long)f0 * kMmStats;
+    const dim3 grid(ceil_div(a.W, kMmTileW) * ceil_div(a.H, kMmTileH), 1, a.m);
+    if (a.level) k_motion_mask_level<<<grid, 256, 0, s>>>(a, vec);
+    else if (a.f16 && a.planar) k_motion_mask<_Float16, true><<<grid, 256, 0, s>>>(a, vec);
+    else if (a.f16) k_motion_mask<_Float16, false><<<grid, 256, 0, s>>>(a, vec);
+    else if (a.planar) k_motion_mask<float, true><<<grid, 256, 0, s>>>(a, vec);
+    else k_motion_mask<float, false><<<grid, 256, 0, s>>>(a, vec);
+  }
+}
 
 // Code-object warm-up: HIP loads a translation unit's code object on the first launch of any of its kernels, which
 // in a one-pair-per-process CLI would land inside the reference's first timer (TIME (Pyramide+Gradients),

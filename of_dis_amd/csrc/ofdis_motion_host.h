@@ -1,6 +1,7 @@
 // ofdis_motion_host.h -- the host-side arithmetic of the motion calls (include/ofdis.h: ofdis_fit_motion,
-// ofdis_smooth_path): the sample lattice, the scalar refusals and the annealed thresholds.  No device code and no HIP
-// header: tools/motion_host_check.cpp builds these functions alone, under the host sanitizers.
+// ofdis_smooth_path, ofdis_motion_mask): the sample lattice, the scalar refusals and the annealed thresholds.  No device
+// code and no HIP header: tools/motion_host_check.cpp and tools/motion_mask_host_check.cpp build these functions alone,
+// under the host sanitizers.
 #ifndef OFDIS_MOTION_HOST_H
 #define OFDIS_MOTION_HOST_H
 
@@ -53,6 +54,15 @@ inline void fit_inv_table(double tau, int iters, double *inv) {
 inline bool path_scalars_ok(int m, int radius, double zoom, int W, int H) {
   if (m < 1 || radius < 0 || radius > 256 || W < 1 || H < 1) return false;
   return zoom >= 1.0 && zoom <= 16.0;  // (false for NaN)
+}
+
+// What ofdis_motion_mask refuses of its scalars: m < 1, thr not finite or outside [0, 65536], rel not finite or outside
+// [0, 16], radius outside 0 .. 4, a non-positive size, W * H >= 2^31.
+constexpr int kMotionMaskMaxRadius = 4;
+inline bool mask_scalars_ok(int m, float thr, float rel, int radius, int W, int H) {
+  if (m < 1 || W < 1 || H < 1 || (long long)W * H > 0x7fffffffLL) return false;
+  if (!(thr >= 0.0f && thr <= 65536.0f) || !(rel >= 0.0f && rel <= 16.0f)) return false;  // (false for NaN)
+  return radius >= 0 && radius <= kMotionMaskMaxRadius;
 }
 
 }  // namespace ofdis

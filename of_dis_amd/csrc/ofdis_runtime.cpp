@@ -57,6 +57,11 @@ const char *const kKernelNamesExt[] = {"flow_error", "flow_error_level", "flow_e
 constexpr int kNumKernelNames = (int)(sizeof(kKernelNames) / sizeof(kKernelNames[0]));
 constexpr int kSlotFlowError = kNumKernelNames, kSlotFlowErrorLevel = kNumKernelNames + 1,
               kSlotFlowErrorSum = kNumKernelNames + 2;
+// The names after both lists (ofdis_kernel_names_ext is closed at its three as well; ofdis_kernel_names_all lists every
+// slot and stays open).  The motion mask on full-resolution fields / on level grids
+const char *const kKernelNamesMore[] = {"motion_mask", "motion_mask_level"};
+constexpr int kNumKernelNamesExt = (int)(sizeof(kKernelNamesExt) / sizeof(kKernelNamesExt[0]));
+constexpr int kSlotMotionMask = kNumKernelNames + kNumKernelNamesExt, kSlotMotionMaskLevel = kSlotMotionMask + 1;
 
 // Output format of a call's forward flow (ofdis_out_format, validated); all zero: the plain format.
 struct OutFmt {
@@ -127,7 +132,7 @@ struct ofdis_context {
   // payload of the call's family alone; the whole key is zeroed before it is filled and compared bytewise, padding
   // included, and the family tag keeps the keys of two families apart whatever their payloads hold.
   struct GraphKey {
-    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter, kStab, kTfilterRadius, kError };
+    enum Family : int { kNone = 0, kBatch, kInterp, kTrack, kTfilter, kStab, kTfilterRadius, kError, kMotionMask };
     // run_batch: ofdis_run_batch_u8*, bidir, stereo, sequence, the formatted calls and ofdis_run_warp_u8
     struct Batch {
       const void *flow_bw, *occ_fw, *occ_bw, *err_fw, *err_bw;  // the bidirectional / stereo call's extra outputs,
@@ -178,6 +183,14 @@ struct ofdis_context {
       const void *gt, *mask, *stats, *err, *hist;
       int mask_eq;
     };
+    // run_batch_motion_mask: the outputs (the caller's arrays or their place in the context's buffer), the fit's and the
+    // mask's scalars; with use_fb the thresholds
+    struct MotionMask {
+      const void *code, *res, *stats, *xform, *support, *occ;
+      int model, step, iters, use_fb, radius;
+      float alpha, beta, thr, rel;
+      double tau;
+    };
     int family;
     int n, w, h;
     int seq, stride;  // a sequence call: `a` is one array of n + stride frames
@@ -192,6 +205,7 @@ struct ofdis_context {
       Stab stab;
       TfilterRadius tfilter_radius;
       Error error;
+      MotionMask motion_mask;
     } u;
   } gkey{};
   hipGraphExec_t gexec = nullptr;
@@ -293,6 +307,8 @@ int kernel_index(const char *name) {
     if (std::strcmp(kKernelNames[i], name) == 0) return i;
   for (int i = 0; i < (int)(sizeof(kKernelNamesExt) / sizeof(kKernelNamesExt[0])); ++i)
     if (std::strcmp(kKernelNamesExt[i], name) == 0) return kNumKernelNames + i;
+  for (int i = 0; i < (int)(sizeof(kKernelNamesMore) / sizeof(kKernelNamesMore[0])); ++i)
+    if (std::strcmp(kKernelNamesMore[i], name) == 0) return kSlotMotionMask + i;
   return -1;
 }
 
@@ -3215,6 +3231,213 @@ int ofdis_run_error_u8_host(ofdis_context *c, const uint8_t *img_a, const uint8_
   return rc;
 }
 
+// ------------------------------------------------------------------ moving-object masks (include/ofdis.h)
+
+static_assert(OFDIS_MM_NSTATS == kMmStats && kMmMaxRadius == kMotionMaskMaxRadius,
+              "the header's constant and the host helpers' limit are the kernel's");
+
+namespace {
+// The transforms, the occlusion plane, the scalars and the outputs of a mask (ofdis_motion_mask,
+// ofdis_run_sequence_motion_mask_u8).
+struct MaskIo {
+  const double *xform = nullptr;
+  const uint8_t *occ = nullptr;
+  float thr = 0.f, rel = 0.f;
+  int radius = 0;
+  uint8_t *code = nullptr;
+  float *res = nullptr;
+  int64_t *stats = nullptr;
+};
+
+// The m fields of view v classified (timer "motion_mask_level" for a level-grid view, else "motion_mask").
+int run_motion_mask(ofdis_context *c, const void *flow, const ofdis_flow_view &v, int m, int width, int height,
+                    const MaskIo &io, hipStream_t s) {
+  MotionMaskArgs ma{};
+  ma.flow = flow;
+  ma.xform = io.xform;
+  ma.occ = io.occ;
+  ma.code = io.code;
+  ma.res = io.res;
+  ma.stats = io.stats;
+  ma.m = m;
+  ma.W = width;
+  ma.H = height;
+  ma.thr = io.thr;
+  ma.rel = io.rel;
+  ma.radius = io.radius;
+  ma.f16 = v.dtype == OFDIS_OUT_F16;
+  ma.planar = v.layout == OFDIS_OUT_PLANAR;
+  ma.level = v.grid == OFDIS_OUT_LEVEL;
+  if (ma.level) {
+    ma.gw = v.gw;
+    ma.gh = v.gh;
+    ma.offx = v.off_x;
+    ma.offy = v.off_y;
+    while ((1 << ma.log2c) < v.cell) ++ma.log2c;
+  }
+  timed(c, ma.level ? kSlotMotionMaskLevel : kSlotMotionMask, s, [&] { launch_motion_mask(ma, s); });
+  return hipGetLastError() == hipSuccess ? OFDIS_OK : OFDIS_ERR_DEVICE;
+}
+
+// ofdis_run_sequence_motion_mask_u8 on stream s (no stage capture is set): run_batch_stabilize's plan; the m forward
+// level grids in the context's buffer, with use_fb the m backward ones, and behind them the outputs the caller did not
+// ask for (transforms, supports, with use_fb the forward occlusion planes).  Every chunk writes its share of the grids;
+// after the chunks the launches on s over all pairs: the fit, with use_fb the check on the grids, the mask.
+int run_batch_motion_mask(ofdis_context *c, hipStream_t s, const uint8_t *frames, int m, int width, int height,
+                          const ofdis_params *p, const FitIo &fit, const FitLattice &L, const MaskIo &io,
+                          uint8_t *occ_out) {
+  CallPlan cp;
+  int rc = prepare(c, p, m, width, height, false, false, cp, fit.use_fb ? 1 : 0, 1);
+  if (rc) return rc;
+  const ofdis_flow_view v = level_view(first_plan(cp));
+  cp.out_pair = level_grid_bytes(first_plan(cp));
+  const size_t px = (size_t)width * height;
+  const size_t grid_bytes = align_up((fit.use_fb ? 2 : 1) * (size_t)m * cp.out_pair);
+  const size_t xf_bytes = align_up((size_t)m * 48), sup_bytes = align_up((size_t)m * 4);
+  const size_t occ_bytes = fit.use_fb && !occ_out ? (size_t)m * px : 0;
+  if ((rc = ensure_warp_buf(c, grid_bytes + xf_bytes + sup_bytes + occ_bytes))) return rc;  // (drops the graph before it grows)
+  char *grids = c->warp_buf, *grids_bw = fit.use_fb ? grids + (size_t)m * cp.out_pair : nullptr;
+  char *tail = c->warp_buf + grid_bytes;
+  FitIo q = fit;  // the call's own arrays where the caller gives none
+  if (!q.xform) q.xform = (double *)tail;
+  if (!q.support) q.support = (int32_t *)(tail + xf_bytes);
+  uint8_t *occ = fit.use_fb ? (occ_out ? occ_out : (uint8_t *)(tail + xf_bytes + sup_bytes)) : nullptr;
+  MaskIo mio = io;
+  mio.xform = q.xform;
+  mio.occ = occ;
+  GraphKey key = graph_key(GraphKey::kMotionMask, c, frames, nullptr, nullptr, grids, grids, m, width, height, 1, p);
+  GraphKey::MotionMask &km = key.u.motion_mask;
+  km.code = io.code; km.res = io.res; km.stats = io.stats; km.xform = q.xform; km.support = q.support; km.occ = occ;
+  km.model = q.model; km.step = q.step; km.iters = q.iters; km.tau = q.tau;
+  km.radius = io.radius; km.thr = io.thr; km.rel = io.rel;
+  if (q.use_fb) {
+    km.use_fb = 1; km.alpha = q.alpha; km.beta = q.beta;
+  }
+  const size_t in_frame = px * p->noc;
+  return replay_or_record(c, s, cp, key, [&](hipStream_t g) {
+    int err = for_each_chunk(c, cp, g, [&](size_t f0, char *ws, const Plan &P, hipStream_t ls) {
+      return run_chunk_grids(c, ws, P, p, frames + f0 * in_frame, nullptr, grids + f0 * cp.out_pair,
+                             grids_bw ? grids_bw + f0 * cp.out_pair : nullptr, ls);
+    });
+    if (err) return err;
+    if ((err = run_fit(c, grids, grids_bw, v, m, width, height, q, L, g))) return err;
+    if (q.use_fb) {
+      BidirOut bo;
+      bo.occ_fw = occ;
+      bo.alpha = q.alpha;
+      bo.beta = q.beta;
+      if ((err = run_fb_check_level(c, (const float *)grids, (const float *)grids_bw, v, m, width, height, bo, g)))
+        return err;
+    }
+    return run_motion_mask(c, grids, v, m, width, height, mio, g);
+  });
+}
+}  // namespace
+
+int ofdis_motion_mask(ofdis_context *c, const void *flow, const ofdis_flow_view *v, int m, int width, int height,
+                      const double *xform, const uint8_t *occ, float thr, float rel, int radius, uint8_t *code,
+                      float *res, int64_t *stats, void *stream) {
+  MaskIo io;
+  io.xform = xform;
+  io.occ = occ;
+  io.thr = thr;
+  io.rel = rel;
+  io.radius = radius;
+  io.code = code;
+  io.res = res;
+  io.stats = stats;
+  if (!c || !flow || !v || !xform || (!code && !res && !stats) || !mask_scalars_ok(m, thr, rel, radius, width, height))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if ((v->dtype != OFDIS_OUT_F32 && v->dtype != OFDIS_OUT_F16) ||
+      (v->layout != OFDIS_OUT_INTERLEAVED && v->layout != OFDIS_OUT_PLANAR) ||
+      (v->grid != OFDIS_OUT_FULL && v->grid != OFDIS_OUT_LEVEL))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  if (v->grid == OFDIS_OUT_LEVEL && (v->dtype != OFDIS_OUT_F32 || v->layout != OFDIS_OUT_INTERLEAVED))
+    return OFDIS_ERR_UNSUPPORTED;  // level grids: float32 interleaved alone (as ofdis_track_points)
+  if (!flow_view_ok(v, width, height)) return OFDIS_ERR_INVALID_ARGUMENT;
+  return device_call(c, stream, false,
+                     [&](hipStream_t s) { return run_motion_mask(c, flow, *v, m, width, height, io, s); });
+}
+
+int ofdis_run_sequence_motion_mask_u8(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                      const ofdis_params *p, int model, int step, double tau, int iters, int use_fb,
+                                      float alpha, float beta, float thr, float rel, int radius, uint8_t *code,
+                                      float *res, int64_t *stats, double *xform, int32_t *support, uint8_t *occ,
+                                      void *stream) {
+  FitIo fit;
+  fit.model = model;
+  fit.step = step;
+  fit.tau = tau;
+  fit.iters = iters;
+  fit.use_fb = use_fb != 0;
+  fit.alpha = alpha;
+  fit.beta = beta;
+  fit.xform = xform;
+  fit.support = support;
+  MaskIo io;
+  io.thr = thr;
+  io.rel = rel;
+  io.radius = radius;
+  io.code = code;
+  io.res = res;
+  io.stats = stats;
+  FitLattice L;
+  if (!c || !frames || !p || nframes < 2 || (p->noc != 1 && p->noc != 3) || (!code && !res && !stats) ||
+      !fit_io_ok(fit, width, height, L) || !mask_scalars_ok(nframes - 1, thr, rel, radius, width, height))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  const int rc = validate_call(p, width, height, false);
+  if (rc) return rc;
+  if (p->mode != OFDIS_MODE_OF) return OFDIS_ERR_UNSUPPORTED;  // a stereo pair is not a sequence
+  return device_call(c, stream, true, [&](hipStream_t s) {
+    return run_batch_motion_mask(c, s, frames, nframes - 1, width, height, p, fit, L, io, fit.use_fb ? occ : nullptr);
+  });
+}
+
+int ofdis_run_sequence_motion_mask_u8_host(ofdis_context *c, const uint8_t *frames, int nframes, int width, int height,
+                                           const ofdis_params *p, int model, int step, double tau, int iters,
+                                           int use_fb, float alpha, float beta, float thr, float rel, int radius,
+                                           uint8_t *code, float *res, int64_t *stats, double *xform, int32_t *support,
+                                           uint8_t *occ) {
+  if (!c || !frames || !p || nframes < 2 || width <= 0 || height <= 0 || (long)width * height > 0x7fffffffL ||
+      (p->noc != 1 && p->noc != 3) || (!code && !res && !stats))
+    return OFDIS_ERR_INVALID_ARGUMENT;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t m = (size_t)nframes - 1, px = m * width * height, in = (size_t)nframes * width * height * p->noc;
+  const bool want_occ = occ && use_fb;
+  // one device block: the frames, the codes, the residuals, the statistics, the transforms, the supports, the occlusion
+  // planes (each at a multiple of 256 bytes)
+  const size_t off_code = align_up(in), off_res = off_code + align_up(px), off_stats = off_res + align_up(px * 4);
+  const size_t off_xf = off_stats + align_up(m * kMmStats * 8), off_sup = off_xf + align_up(m * 48);
+  const size_t off_occ = off_sup + align_up(m * 4);
+  char *d = nullptr;
+  HIP_OK(hipMalloc(&d, off_occ + align_up(px)));
+  int rc = OFDIS_OK;
+  auto step_ok = [&](hipError_t e) {
+    if (e != hipSuccess && rc == OFDIS_OK) rc = e == hipErrorOutOfMemory ? OFDIS_ERR_OUT_OF_MEMORY : OFDIS_ERR_DEVICE;
+    return rc == OFDIS_OK;
+  };
+  if (step_ok(hipMemcpyAsync(d, frames, in, hipMemcpyHostToDevice, c->stream))) {
+    rc = ofdis_run_sequence_motion_mask_u8(c, (const uint8_t *)d, nframes, width, height, p, model, step, tau, iters,
+                                           use_fb, alpha, beta, thr, rel, radius,
+                                           code ? (uint8_t *)(d + off_code) : nullptr,
+                                           res ? (float *)(d + off_res) : nullptr,
+                                           stats ? (int64_t *)(d + off_stats) : nullptr,
+                                           xform ? (double *)(d + off_xf) : nullptr,
+                                           support ? (int32_t *)(d + off_sup) : nullptr,
+                                           want_occ ? (uint8_t *)(d + off_occ) : nullptr, c->stream);
+    if (rc == OFDIS_OK && step_ok(hipStreamSynchronize(c->stream))) {
+      if (code) step_ok(hipMemcpy(code, d + off_code, px, hipMemcpyDeviceToHost));
+      if (res) step_ok(hipMemcpy(res, d + off_res, px * 4, hipMemcpyDeviceToHost));
+      if (stats) step_ok(hipMemcpy(stats, d + off_stats, m * kMmStats * 8, hipMemcpyDeviceToHost));
+      if (xform) step_ok(hipMemcpy(xform, d + off_xf, m * 48, hipMemcpyDeviceToHost));
+      if (support) step_ok(hipMemcpy(support, d + off_sup, m * 4, hipMemcpyDeviceToHost));
+      if (want_occ) step_ok(hipMemcpy(occ, d + off_occ, px, hipMemcpyDeviceToHost));
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+
 int ofdis_pyramid_u8_host(ofdis_context *c, const uint8_t *img, int width, int height, const ofdis_params *p,
                           int imgpadding, float *const *img_pyr, float *const *dx_pyr, float *const *dy_pyr) {
   if (!c || !img || !p || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
@@ -3358,6 +3581,17 @@ const char *ofdis_kernel_names_ext(void) {
   return names.c_str();
 }
 
+const char *ofdis_kernel_names_all(void) {
+  static const std::string names = [] {
+    std::string r;
+    for (const char *k : kKernelNames) r += (r.empty() ? "" : ",") + std::string(k);
+    for (const char *k : kKernelNamesExt) r += "," + std::string(k);
+    for (const char *k : kKernelNamesMore) r += "," + std::string(k);
+    return r;
+  }();
+  return names.c_str();
+}
+
 // The filter over a radius per interior output frame, in "tfilter"'s convention: per pixel the frame and the taps of
 // its 2 R neighbours ((2 R + 1) noc), the picture (noc, or 4 noc as float32) and the `used` byte; each of the 2 R steps
 // reads one field once -- 8 bytes per pixel of a full-resolution float32 view (16 R), or a level grid (the opposite
@@ -3451,6 +3685,11 @@ int ofdis_algorithmic_bytes(const ofdis_params *p, int width, int height, const 
   if (k == "flow_error") b = (double)width * height * 16.0;
   if (k == "flow_error_level") b = (double)P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height * 8.0;
   if (k == "flow_error_sum") b = (double)height * sizeof(FeRow) + 8.0 * kFeStats;
+  // the motion mask per pair: the float32 estimate and the code byte, 9 bytes per pixel (the function has no argument
+  // for them: the occlusion byte, the residual map and the statistics are not counted); of a level grid its cells and
+  // the code byte
+  if (k == "motion_mask") b = (double)width * height * 9.0;
+  if (k == "motion_mask_level") b = (double)P.lv[0].w * P.lv[0].h * 8.0 + (double)width * height;
   *bytes = b;
   return OFDIS_OK;
 }

@@ -16,7 +16,7 @@ import numpy as np
 
 from ._lib import (ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, FE_BINS, FE_COUNT, FE_FL, FE_GT1, FE_GT3, FE_GT5, FE_MAX,
                    FE_NONFINITE, FE_NSTATS, FE_S0_COUNT, FE_S0_SUM, FE_S1_COUNT, FE_S1_SUM, FE_S2_COUNT, FE_S2_SUM, FE_SUM,
-                   FIT_MAX_SAMPLES, IMG_F32, IMG_U8, MODE_DE, MODE_OF, MOTION_SIMILARITY, MOTION_TRANSLATION, TRACK_LAST,
+                   FIT_MAX_SAMPLES, IMG_F32, IMG_U8, MM_NSTATS, MODE_DE, MODE_OF, MOTION_SIMILARITY, MOTION_TRANSLATION, TRACK_LAST,
                    FlowView, OfdisError, OutFormat, Params, check, lib, out_format)
 
 _f32 = np.float32
@@ -1387,6 +1387,146 @@ class Context:
         res = [out] + ([valid] if want_valid else []) + ([xform, corr, support] if want_path else [])
         return tuple(res) if len(res) > 1 else out
 
+    def motion_mask_ptr(self, flow_ptr: int, view: FlowView, m: int, width: int, height: int, xform_ptr: int,
+                        occ_ptr: int, thr: float, rel: float, radius: int, code_ptr: int = 0, res_ptr: int = 0,
+                        stats_ptr: int = 0, stream: int = 0) -> None:
+        """``ofdis_motion_mask`` on raw device pointers (0: no occlusion plane / that output is not wanted)."""
+        check(lib().ofdis_motion_mask(self._h, flow_ptr or None, None if view is None else C.byref(view), m, width,
+                                      height, xform_ptr or None, occ_ptr or None, thr, rel, radius, code_ptr or None,
+                                      res_ptr or None, stats_ptr or None, stream or None), "ofdis_motion_mask")
+
+    def motion_mask(self, flow, xform, occ=None, thr: float = 1.0, rel: float = 0.05, radius: int = 1,
+                    want_res: bool = False, want_stats: bool = False, layout: str = "nhwc", grid: str = "full",
+                    p: Optional[Params] = None, size=None):
+        """The pixels that moved on their own (the definition is in ofdis.h): per pixel the distance e of the estimate
+        from the camera's flow under xform (``fit_motion``'s float64 [m, 6]), raw class e > thr and e > rel * |camera
+        flow|, and a binary median over the clipped (2 radius + 1)^2 window.  flow: described as for ``track_points``
+        (grid "level" takes float32 "nhwc" grids and needs `p` and size = (width, height)).  occ: ``fb_check``'s forward
+        plane, torch.uint8 [m, h, w], or None; its nonzero pixels and non-finite estimates are unknown.  Returns code,
+        torch.uint8 [m, h, w] (0 static, 1 moving, 2 unknown); with want_res also e as float32 [m, h, w]; with
+        want_stats also int64 [m, 12] (``motion_summary`` reads them)."""
+        import torch
+        if not flow.is_cuda or flow.dim() != 4:
+            raise ValueError("expected the m fields as one CUDA tensor of four dimensions")
+        fmt = out_format(flow.dtype, layout, grid)
+        m = flow.shape[0]
+        if grid == "level":
+            if p is None or size is None:
+                raise OfdisError(ERR_INVALID_ARGUMENT, 'motion_mask: grid="level" needs the parameters the flows were '
+                                 "computed with and the frame size")
+            w, h = int(size[0]), int(size[1])
+        else:
+            h, w = (flow.shape[2], flow.shape[3]) if fmt.layout else (flow.shape[1], flow.shape[2])
+        _mask_checks("motion_mask", m, thr, rel, radius, w, h)
+        if grid == "level":
+            g = out_geometry(p, w, h, False, flow.dtype, layout, grid)
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, g["out_w"], g["out_h"], g["cell"], g["off_x"], g["off_y"])
+        else:
+            view = FlowView(fmt.dtype, fmt.layout, fmt.grid, w, h, 1, 0, 0)
+        want = (m, 2, view.gh, view.gw) if fmt.layout else (m, view.gh, view.gw, 2)
+        if tuple(flow.shape) != want:
+            raise ValueError(f"flow has shape {tuple(flow.shape)}, expected {want}")
+        if not xform.is_cuda or tuple(xform.shape) != (m, 6) or xform.dtype != torch.float64:
+            raise ValueError(f"expected a float64 CUDA tensor of transforms [{m}, 6]")
+        if occ is not None and (occ.dtype != torch.uint8 or tuple(occ.shape) != (m, h, w) or not occ.is_cuda):
+            raise ValueError(f"expected a uint8 CUDA occlusion plane of shape {(m, h, w)}")
+        flow, xform = flow.contiguous(), xform.contiguous()
+        occ = occ.contiguous() if occ is not None else None
+        dev = flow.device
+        code = torch.empty((m, h, w), dtype=torch.uint8, device=dev)
+        res = torch.empty((m, h, w), dtype=torch.float32, device=dev) if want_res else None
+        stats = torch.empty((m, MM_NSTATS), dtype=torch.int64, device=dev) if want_stats else None
+        self.motion_mask_ptr(flow.data_ptr(), view, m, w, h, xform.data_ptr(), occ.data_ptr() if occ is not None else 0,
+                             float(thr), float(rel), int(radius), code.data_ptr(), res.data_ptr() if want_res else 0,
+                             stats.data_ptr() if want_stats else 0, torch.cuda.current_stream(dev).cuda_stream)
+        out = [code] + ([res] if want_res else []) + ([stats] if want_stats else [])
+        return tuple(out) if len(out) > 1 else code
+
+    def run_sequence_motion_mask_ptr(self, frames_ptr: int, nframes: int, width: int, height: int, p: Params, model: int,
+                                     step: int, tau: float, iters: int, thr: float, rel: float, radius: int,
+                                     code_ptr: int = 0, res_ptr: int = 0, stats_ptr: int = 0, xform_ptr: int = 0,
+                                     support_ptr: int = 0, occ_ptr: int = 0, fb: bool = False, alpha: float = 0.01,
+                                     beta: float = 0.5, stream: int = 0) -> None:
+        """``ofdis_run_sequence_motion_mask_u8`` on raw device pointers, asynchronous on `stream`: frames u8
+        [nframes, h, w, noc] -> the masks (0: that output is not wanted)."""
+        check(lib().ofdis_run_sequence_motion_mask_u8(self._h, frames_ptr or None, nframes, width, height, C.byref(p),
+                                                      model, step, tau, iters, int(bool(fb)), alpha, beta, thr, rel,
+                                                      radius, code_ptr or None, res_ptr or None, stats_ptr or None,
+                                                      xform_ptr or None, support_ptr or None, occ_ptr or None,
+                                                      stream or None), "ofdis_run_sequence_motion_mask_u8")
+
+    def run_sequence_motion_mask(self, frames, p: Params, model: int = MOTION_SIMILARITY, step: int = 16,
+                                 tau: float = 2.0, iters: int = 4, fb: bool = False, alpha: float = 0.01,
+                                 beta: float = 0.5, thr: float = 1.0, rel: float = 0.05, radius: int = 1,
+                                 want_res: bool = False, want_stats: bool = False, want_xform: bool = False,
+                                 want_occ: bool = False):
+        """The flows of a video, its camera motion and the moving-object masks in one call: torch.uint8 CUDA tensor
+        [T, h, w] or [T, h, w, noc] -> code uint8 [T - 1, h, w].  Bit for bit ``motion_mask(F, fit_motion(F, B if fb
+        else None, ...), occ_fw if fb else None, ...)`` on ``run_sequence(frames, p, bidir=fb)``'s flows and masks --
+        but the flows stay on their level grids and no full-resolution flow is written.  want_res adds float32
+        [T - 1, h, w], want_stats int64 [T - 1, 12], want_xform (xform float64 [T - 1, 6], support int32 [T - 1]),
+        want_occ (with fb) the forward occlusion planes uint8 [T - 1, h, w]."""
+        import torch
+        f4 = frames.unsqueeze(-1) if frames.dim() == 3 else frames
+        if f4.dim() != 4 or f4.shape[-1] != p.noc or f4.dtype != torch.uint8 or not f4.is_cuda:
+            raise ValueError("expected a uint8 CUDA tensor with noc channels")
+        t, h, w, _ = f4.shape
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_motion_mask: a video needs two frames or more")
+        if want_occ and not fb:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_motion_mask: want_occ needs fb")
+        _motion_checks("run_sequence_motion_mask", w, h, model, step, tau, iters)
+        _mask_checks("run_sequence_motion_mask", t - 1, thr, rel, radius, w, h)
+        f4 = f4.contiguous()
+        dev = f4.device
+        code = torch.empty((t - 1, h, w), dtype=torch.uint8, device=dev)
+        res = torch.empty((t - 1, h, w), dtype=torch.float32, device=dev) if want_res else None
+        stats = torch.empty((t - 1, MM_NSTATS), dtype=torch.int64, device=dev) if want_stats else None
+        xform = torch.empty((t - 1, 6), dtype=torch.float64, device=dev) if want_xform else None
+        support = torch.empty((t - 1,), dtype=torch.int32, device=dev) if want_xform else None
+        occ = torch.empty((t - 1, h, w), dtype=torch.uint8, device=dev) if want_occ else None
+        self.run_sequence_motion_mask_ptr(f4.data_ptr(), t, w, h, p, int(model), int(step), float(tau), int(iters),
+                                          float(thr), float(rel), int(radius), code.data_ptr(),
+                                          res.data_ptr() if want_res else 0, stats.data_ptr() if want_stats else 0,
+                                          xform.data_ptr() if want_xform else 0, support.data_ptr() if want_xform else 0,
+                                          occ.data_ptr() if want_occ else 0, fb, alpha, beta,
+                                          torch.cuda.current_stream(dev).cuda_stream)
+        out = ([code] + ([res] if want_res else []) + ([stats] if want_stats else [])
+               + ([xform, support] if want_xform else []) + ([occ] if want_occ else []))
+        return tuple(out) if len(out) > 1 else code
+
+    def run_sequence_motion_mask_host(self, frames: np.ndarray, p: Params, model: int = MOTION_SIMILARITY,
+                                      step: int = 16, tau: float = 2.0, iters: int = 4, fb: bool = False,
+                                      alpha: float = 0.01, beta: float = 0.5, thr: float = 1.0, rel: float = 0.05,
+                                      radius: int = 1, want_res: bool = False, want_stats: bool = False,
+                                      want_xform: bool = False, want_occ: bool = False):
+        """run_sequence_motion_mask on a numpy u8 array [T, h, w] or [T, h, w, noc]; synchronous."""
+        f4 = np.ascontiguousarray(frames[..., None] if frames.ndim == 3 else frames, np.uint8)
+        if f4.ndim != 4 or f4.shape[-1] != p.noc:
+            raise ValueError("expected a uint8 array with noc channels")
+        t, h, w = f4.shape[:3]
+        if t < 2:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_motion_mask_host: a video needs two frames or more")
+        if want_occ and not fb:
+            raise OfdisError(ERR_INVALID_ARGUMENT, "run_sequence_motion_mask_host: want_occ needs fb")
+        _motion_checks("run_sequence_motion_mask_host", w, h, model, step, tau, iters)
+        _mask_checks("run_sequence_motion_mask_host", t - 1, thr, rel, radius, w, h)
+        code = np.empty((t - 1, h, w), np.uint8)
+        res = np.empty((t - 1, h, w), _f32) if want_res else None
+        stats = np.empty((t - 1, MM_NSTATS), np.int64) if want_stats else None
+        xform = np.empty((t - 1, 6), np.float64) if want_xform else None
+        support = np.empty((t - 1,), np.int32) if want_xform else None
+        occ = np.empty((t - 1, h, w), np.uint8) if want_occ else None
+        check(lib().ofdis_run_sequence_motion_mask_u8_host(
+            self._h, f4.ctypes.data, t, w, h, C.byref(p), int(model), int(step), float(tau), int(iters), int(bool(fb)),
+            alpha, beta, float(thr), float(rel), int(radius), code.ctypes.data, res.ctypes.data if want_res else None,
+            stats.ctypes.data if want_stats else None, xform.ctypes.data if want_xform else None,
+            support.ctypes.data if want_xform else None, occ.ctypes.data if want_occ else None),
+            "ofdis_run_sequence_motion_mask_u8_host")
+        out = ([code] + ([res] if want_res else []) + ([stats] if want_stats else [])
+               + ([xform, support] if want_xform else []) + ([occ] if want_occ else []))
+        return tuple(out) if len(out) > 1 else code
+
     def flow_error_ptr(self, flow_ptr: int, view: FlowView, gt_ptr: int, n: int, width: int, height: int,
                        stats_ptr: int, mask_ptr: int = 0, mask_eq: int = -1, err_ptr: int = 0, hist_ptr: int = 0,
                        stream: int = 0) -> None:
@@ -1624,6 +1764,35 @@ def _path_checks(what: str, m: int, radius, zoom, width: int, height: int) -> No
         raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: zoom {zoom!r} is not in [1, 16]")
 
 
+def _mask_checks(what: str, m: int, thr, rel, radius, width: int, height: int) -> None:
+    """What the mask calls refuse of their scalars, before any library call (ofdis_motion_mask's rules)."""
+    if m < 1 or width < 1 or height < 1 or width * height >= 2 ** 31:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: {m} fields of a {width} x {height} frame")
+    t, r = float(thr), float(rel)
+    if not (np.isfinite(t) and 0.0 <= t <= 65536.0):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: thr {thr!r} is not in [0, 65536]")
+    if not (np.isfinite(r) and 0.0 <= r <= 16.0):
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: rel {rel!r} is not in [0, 16]")
+    if int(radius) != radius or not 0 <= radius <= 4:
+        raise OfdisError(ERR_INVALID_ARGUMENT, f"{what}: radius {radius!r} is not in 0..4")
+
+
+def motion_summary(stats) -> list:
+    """The readable figures of ``motion_mask`` / ``run_sequence_motion_mask`` stats ([m, 12] or [12]; numpy, or a
+    tensor copied to the host): one dict per pair with static / moving / unknown (the counts of codes 0, 1, 2),
+    moving_share = moving / (static + moving) (NaN when every pixel is unknown), raw (the count before the clean-up),
+    bbox = (xmin, ymin, xmax, ymax) of the moving pixels and centroid = (mean x, mean y), both None when none moves."""
+    s = np.asarray(stats.detach().cpu().numpy() if hasattr(stats, "detach") else stats, np.int64).reshape(-1, MM_NSTATS)
+    out = []
+    for r in s:
+        n0, n1, n2 = int(r[0]), int(r[1]), int(r[2])
+        out.append({"static": n0, "moving": n1, "unknown": n2, "raw": int(r[7]),
+                    "moving_share": n1 / (n0 + n1) if n0 + n1 > 0 else float("nan"),
+                    "bbox": tuple(int(v) for v in r[3:7]) if n1 else None,
+                    "centroid": (int(r[8]) / n1, int(r[9]) / n1) if n1 else None})
+    return out
+
+
 def write_pnm(path: str, pixels: np.ndarray) -> None:
     """Binary PGM (u8 [h, w] or [h, w, 1]) / PPM (u8 [h, w, 3] in BGR order, written as RGB)."""
     pixels = np.ascontiguousarray(pixels, np.uint8)
@@ -1638,6 +1807,12 @@ def kernel_names():
 def kernel_names_ext():
     """The timer names added after the closed list of ``kernel_names``, in slot order."""
     return lib().ofdis_kernel_names_ext().decode().split(",")
+
+
+def kernel_names_all():
+    """Every timer name in slot order: ``kernel_names``, ``kernel_names_ext`` and the names later features add (an
+    open list: look names up in it, do not count it)."""
+    return lib().ofdis_kernel_names_all().decode().split(",")
 
 
 def _error_mask(mask, shape, mask_eq, device):
@@ -1726,6 +1901,7 @@ def tfilter_radius_bytes(p: Params, width: int, height: int, radius: int, level:
 
 __all__ = ["OFClass", "Context", "Params", "oppoint", "params_from_strings", "validate", "synth_pair", "synth_shift_pair",
            "write_flo", "write_pfm", "write_pnm", "read_flo", "read_image", "auto_first_scale", "kernel_names", "algorithmic_bytes",
-           "tfilter_radius_bytes", "kernel_names_ext", "error_summary", "error_percentile",
+           "tfilter_radius_bytes", "kernel_names_ext", "kernel_names_all", "error_summary", "error_percentile",
+           "motion_summary",
            "max_frames_per_launch", "out_geometry", "pixel_grid", "fit_lattice",
            "MODE_OF", "MODE_DE", "MOTION_TRANSLATION", "MOTION_SIMILARITY"]
