@@ -1056,8 +1056,13 @@ int ofdis_context_set_stage_capture(ofdis_context *ctx, float *const *dis_flow, 
  * OFDIS_ERR_INVALID_ARGUMENT.  Apart from "sor_mode", results never depend on these settings. */
 int ofdis_context_set_option(ofdis_context *ctx, const char *key, int value);
 
-/* Largest number of frame pairs one launch of the refinement kernels takes at this size (their plane groups
- * are addressed with 32-bit offsets: frames * noc * plane < 2^30 floats); larger batches are chunked.
+/* Largest number of frame pairs one launch takes at this size; larger batches are chunked.  Two rules, the smaller
+ * one holds.  The refinement kernels address their plane groups with 32-bit offsets: frames * noc * plane < 2^30
+ * floats (with usetvref 0 this rule sets no bound).  And no launch puts more than 65535 in grid y or z: a pair is two
+ * frames of the pyramid kernels' grid z, and with the refinement on, noc rows of its derivative launches' grid y, so
+ * at most 65535 / max(2, noc) pairs (32767 grey, 21845 colour).  A stereo call takes half of this value in stereo
+ * pairs; a sequence chunk of m pairs builds m + stride frames, so its bound is min(plane rule, 65535 / noc
+ * with the refinement on, 65535 - stride) pairs.  An explicit "chunk" option above the bound is clamped to it.
  * A size at which one frame alone exceeds that (e.g. ~20k x 20k RGB with sc_l 0) returns
  * OFDIS_ERR_INVALID_ARGUMENT here and from every run entry point. */
 int ofdis_max_frames_per_launch(const ofdis_params *p, int width, int height, int *frames);

@@ -1318,6 +1318,23 @@ int tv_frame_cap(const ofdis_params *p, int width, int height) {
   return (int)std::min((long)(1 << 30), ((1L << 30) - 1) / per);  // 0: one frame alone is too large
 }
 
+// Pairs per launch such that no grid y or z exceeds 65535, the limit the sliced launchers (kSlice) assume.  What a
+// chunk of m pairs puts there: the pyramid base's z holds every frame (2m of two arrays, m + stride of a sequence);
+// the refinement's separate derivative launches (colour with "prepd" < 2) put m * noc in y; aggregation, prep, the
+// two-launch system, the red-black SOR, final, upsample and level-out put m in y or z.  (Patch, SOR and the fused
+// system kernels count frames in grid x.)  The derivative term is taken whatever "prepd" says, so that the bound
+// depends on the parameters alone.  A stride of 65535 or more leaves nothing: < 1.
+constexpr int kGridYZ = 65535;
+int grid_frame_cap(const ofdis_params *p, int stride) {
+  const int per_pair = std::max(stride > 0 ? 1 : 2, p->usetvref ? p->noc : 1);
+  return std::min(kGridYZ / per_pair, stride > 0 ? kGridYZ - stride : kGridYZ);
+}
+
+// Both rules: the pairs one launch takes (stride > 0: of a sequence chunk).
+int frame_cap(const ofdis_params *p, int width, int height, int stride = 0) {
+  return std::min(tv_frame_cap(p, width, height), grid_frame_cap(p, stride));
+}
+
 // How one call is issued: the whole batch on one stream and workspace (single), or chunks round-robin over
 // lanes (round robin).  Everything the issue needs -- workspaces, lane streams, events -- is allocated by
 // prepare(), before any capture begins.  (Round 5's software pipeline over a streaming stream and chain lanes,
@@ -1347,7 +1364,8 @@ int prepare(ofdis_context *c, const ofdis_params *p, int n, int width, int heigh
   const int nstreams = capturing ? 1 : stream_count(c, c->call_frames);
   int chunk = capturing ? n : c->opt_chunk > 0 ? std::min(c->opt_chunk, n) : (n + nstreams - 1) / nstreams;
   // chunks count stereo pairs: two flow pairs of the launch-size cap each, four frames of the pyramid kernels' grid z
-  chunk = std::min(chunk, stereo ? std::min(tv_frame_cap(p, width, height) / 2, 16383) : tv_frame_cap(p, width, height));
+  // (half the pair call's cap bounds both: 4 * (cap / 2) <= 2 * cap)
+  chunk = std::min(chunk, stereo ? frame_cap(p, width, height) / 2 : frame_cap(p, width, height, stride));
   if (chunk < 1) return OFDIS_ERR_INVALID_ARGUMENT;
   cp.chunk = chunk;
   cp.nchunks = (n + chunk - 1) / chunk;
@@ -3765,7 +3783,7 @@ int ofdis_max_frames_per_launch(const ofdis_params *p, int width, int height, in
   if (!p || !frames || width <= 0 || height <= 0) return OFDIS_ERR_INVALID_ARGUMENT;
   const int rc = ofdis_params_validate(p, -1, -1, -1);
   if (rc) return rc;
-  *frames = tv_frame_cap(p, width, height);
+  *frames = frame_cap(p, width, height);
   return *frames >= 1 ? OFDIS_OK : OFDIS_ERR_INVALID_ARGUMENT;
 }
 

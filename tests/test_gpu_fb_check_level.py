@@ -207,14 +207,15 @@ def test_unaligned_outputs_take_the_scalar_form(ctx, geom, occ_off, err_off):
 
 
 def test_one_frame_above_the_launch_slice(ctx):
-    """32768 frames of 4 x 2 on a 2 x 1 grid of cell 2: the second launch holds the last frame alone."""
-    n = 32768
+    """32768 frames of 4 x 2 on a 2 x 1 grid of cell 2: the second launch holds the last frame alone.  65535 frames: three
+    launches, the middle one full."""
     W, H, g = 4, 2, {"cell": 2, "off_x": 0, "off_y": 0, "out_w": 2, "out_h": 1}
-    gf, gb, alpha, beta = make_grids("smooth", 2, 1, n, 99)
-    want = fb_reference(expand_level(gf, g, W, H), expand_level(gb, g, W, H), alpha, beta)
-    got = gpu_level_check(ctx, gf, gb, g, W, H, alpha, beta)
-    assert_check_equal(got, want, "32768 frames")
-    assert (want[0][-1] != want[0][0]).any() or (want[2][-1] != want[2][0]).any()  # (the last frame is its own)
+    for n in (32768, 65535):
+        gf, gb, alpha, beta = make_grids("smooth", 2, 1, n, 99)
+        want = fb_reference(expand_level(gf, g, W, H), expand_level(gb, g, W, H), alpha, beta)
+        got = gpu_level_check(ctx, gf, gb, g, W, H, alpha, beta)
+        assert_check_equal(got, want, f"{n} frames")
+        assert (want[0][-1] != want[0][0]).any() or (want[2][-1] != want[2][0]).any()  # (the last frame is its own)
 
 
 # --------------------------------------------------------------------------------------------- refusals

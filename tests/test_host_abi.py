@@ -265,11 +265,21 @@ def test_oflow_hpp_dropin_compiles(tmp_path):
     assert os.access(build_dropin(tmp_path), os.X_OK)
 
 
-@pytest.mark.parametrize("w,h,noc,op,sc_l", [(640, 480, 3, 2, 0), (960, 540, 1, 2, 0), (1920, 1080, 1, 2, None),
-                                           (3840, 2160, 1, 4, None)])
+GRID_YZ = 65535  # the largest grid y or z any launch may use (the sliced launchers' kSlice)
+
+
+# (w, h, noc, op-point, sc_l or None for the op-point's own)
+PLANE_BINDS = [(640, 480, 3, 2, 0), (960, 540, 1, 2, 0), (1920, 1080, 1, 2, 0), (3840, 2160, 1, 4, None)]
+# small frames, and 1080p at op-point 2's own sc_l = 4 (a 120 x 68 plane)
+GRID_BINDS = [(8, 8, 1, 2, 0), (16, 16, 1, 2, 0), (96, 64, 3, 2, 0), (8, 8, 3, 2, 0), (1920, 1080, 1, 2, None)]
+
+
+@pytest.mark.parametrize("w,h,noc,op,sc_l", PLANE_BINDS + GRID_BINDS)
 def test_max_frames_per_launch_keeps_plane_groups_below_2_30(w, h, noc, op, sc_l):
-    """The refinement kernels address a plane group (frames * noc * skewed plane floats) with 32-bit byte
-    offsets; the runtime chunks a batch so that no launch exceeds 2^30 floats per group."""
+    """Two rules bound a launch, and the smaller holds exactly.  Plane rule: the refinement kernels address a plane
+    group (frames * noc * skewed plane floats) with 32-bit byte offsets, so no launch exceeds 2^30 floats per group.
+    Grid rule: a pair is two frames of the pyramid kernels' grid z, and with the refinement on noc rows of the
+    derivative launches' grid y; neither may pass 65535."""
     p = od.oppoint(op, w, 1, noc)
     if sc_l is not None:
         p.sc_l = sc_l
@@ -281,6 +291,12 @@ def test_max_frames_per_launch_keeps_plane_groups_below_2_30(w, h, noc, op, sc_l
         lw, lh = wp >> s, hp >> s
         slots = lw * lh if lh <= lw else (lw + lh - 1) * lh
         plane = max(plane, (slots + 64 + 3) // 4 * 4)
-    assert cap >= 1 and cap * noc * plane < 2 ** 30 <= (cap + 1) * noc * plane
-    p.usetvref = 0
-    assert od.max_frames_per_launch(p, w, h) == 2 ** 30
+    plane_cap = (2 ** 30 - 1) // (noc * plane)
+    assert plane_cap >= 1 and plane_cap * noc * plane < 2 ** 30 <= (plane_cap + 1) * noc * plane
+    grid_cap = GRID_YZ // max(2, noc)
+    assert 2 * grid_cap <= GRID_YZ and noc * grid_cap <= GRID_YZ
+    assert (2 * (grid_cap + 1) > GRID_YZ) or (noc * (grid_cap + 1) > GRID_YZ)
+    assert cap == min(plane_cap, grid_cap)
+    assert (plane_cap < grid_cap) == ((w, h, noc, op, sc_l) in PLANE_BINDS)
+    p.usetvref = 0  # no refinement: no plane groups, and a pair's noc no longer counts
+    assert od.max_frames_per_launch(p, w, h) == min(2 ** 30, GRID_YZ // 2) == 32767

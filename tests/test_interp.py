@@ -398,17 +398,19 @@ def test_gpu_interp_unaligned(ctx, off, noc, f32out):
 
 @pytest.mark.gpu
 def test_gpu_interp_one_frame_above_the_launch_slice(ctx):
-    """launch_interp puts 65535 frames in one launch (grid z): 65536 frames of 8 x 4 take two."""
+    """launch_interp puts 65535 frames in one launch (grid z): 65536 frames of 8 x 4 take two, 131071 take three with a
+    full middle one."""
     import torch
-    n, w, h = 65536, 8, 4
-    rng = np.random.default_rng(5)
-    a = rng.integers(0, 256, (n, h, w), dtype=np.uint8)
-    b = rng.integers(0, 256, (n, h, w), dtype=np.uint8)
-    F = rng.uniform(-3, 3, (n, h, w, 2)).astype(f32)
-    B = rng.uniform(-3, 3, (n, h, w, 2)).astype(f32)
-    want, want_valid = interp_reference(a, b, F, B, 0.5)
-    got, valid = ctx.interp(*(torch.from_numpy(x).cuda() for x in (a, b, F, B)), 0.5, want_valid=True)
-    torch.cuda.synchronize()
-    assert_picture(got.cpu().numpy(), want, "65536 frames")
-    assert_picture(valid.cpu().numpy(), want_valid, "65536 frames (valid)")
-    assert not np.array_equal(want[-1], want[0])
+    w, h = 8, 4
+    for n in (65536, 131071):
+        rng = np.random.default_rng(5)
+        a = rng.integers(0, 256, (n, h, w), dtype=np.uint8)
+        b = rng.integers(0, 256, (n, h, w), dtype=np.uint8)
+        F = rng.uniform(-3, 3, (n, h, w, 2)).astype(f32)
+        B = rng.uniform(-3, 3, (n, h, w, 2)).astype(f32)
+        want, want_valid = interp_reference(a, b, F, B, 0.5)
+        got, valid = ctx.interp(*(torch.from_numpy(x).cuda() for x in (a, b, F, B)), 0.5, want_valid=True)
+        torch.cuda.synchronize()
+        assert_picture(got.cpu().numpy(), want, f"{n} frames")
+        assert_picture(valid.cpu().numpy(), want_valid, f"{n} frames (valid)")
+        assert not np.array_equal(want[-1], want[0]) and not np.array_equal(want[65535], want[0])

@@ -357,15 +357,17 @@ def test_gpu_warp_unaligned(ctx, off, noc, f32out):
 
 @pytest.mark.gpu
 def test_gpu_warp_one_frame_above_the_launch_slice(ctx):
-    """launch_warp puts 65535 frames in one launch (grid z): 65536 frames of 8 x 4 take two."""
+    """launch_warp puts 65535 frames in one launch (grid z): 65536 frames of 8 x 4 take two, 131071 take three with a
+    full middle one."""
     import torch
-    n, w, h = 65536, 8, 4
-    rng = np.random.default_rng(5)
-    img = rng.integers(0, 256, (n, h, w), dtype=np.uint8)
-    flow = rng.uniform(-3, 3, (n, h, w, 2)).astype(f32)
-    want, want_valid = warp_reference(img, flow)
-    got, valid = ctx.warp(torch.from_numpy(img).cuda(), torch.from_numpy(flow).cuda(), want_valid=True)
-    torch.cuda.synchronize()
-    assert_picture(got.cpu().numpy(), want, "65536 frames")
-    assert_picture(valid.cpu().numpy(), want_valid, "65536 frames (valid)")
-    assert not np.array_equal(want[-1], want[0])
+    w, h = 8, 4
+    for n in (65536, 131071):
+        rng = np.random.default_rng(5)
+        img = rng.integers(0, 256, (n, h, w), dtype=np.uint8)
+        flow = rng.uniform(-3, 3, (n, h, w, 2)).astype(f32)
+        want, want_valid = warp_reference(img, flow)
+        got, valid = ctx.warp(torch.from_numpy(img).cuda(), torch.from_numpy(flow).cuda(), want_valid=True)
+        torch.cuda.synchronize()
+        assert_picture(got.cpu().numpy(), want, f"{n} frames")
+        assert_picture(valid.cpu().numpy(), want_valid, f"{n} frames (valid)")
+        assert not np.array_equal(want[-1], want[0]) and not np.array_equal(want[65535], want[0])
